@@ -14,9 +14,14 @@ N > 1: one process per GPU, independent replicas (seeds shard with no data-path 
 run_experiment.py:57-78) -> weak scaling; torch.distributed (RCCL) only for the barrier + max-time.  The ranks come
 either from the launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`: RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the env) or, when `--gpus N` is given WITHOUT a RANK in the env, from bench.py itself: it
-spawns N copies of itself, one per GPU, on 127.0.0.1 and relays rank 0's JSON line.  With N > 1 the line also carries
+spawns N copies of itself, one per GPU, on 127.0.0.1 and relays rank 0's JSON line.  With N > 1 and --full the line also carries
 `split_run`: ONE run split over the N GPUs (B/N rows per rank, RCCL all-reduce of the gradient arena on the library's
 stream between backward and update) — the only leg with a data-path collective, never `value`.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the headline line.  Everything else
+this file measures — the roofline legs (per-kernel HIP-event timing, replay gather in and beyond the Infinity Cache), co-resident
+seeds, configs 3 / 4 / 5, the CPU baselines and the split-run leg — runs under `--full` only; the `--no-*` switches thin that out.
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0) as DIR/<name>.npy before any other leg runs.
 """
 import argparse
 import ctypes as C
@@ -529,11 +534,32 @@ def split_run_leg(R, n=400):
                 collective="ncclAllReduce(float32, sum) x2 per step on the ctx stream (librccl via dlopen)")
 
 
+def dump_outputs(out_dir, tr, ro, rb):
+    """What a caller of the timed step holds after its last step: the trainer's five parameter vectors and log alpha, the 4096 envs'
+    simulator state, and the replay rows that step's rollout inserted (float32 / float64, about 3 MB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {k: tr.get_params(k) for k in tr.WHICH}
+    out["log_alpha"] = np.array([tr.log_alpha], np.float64)
+    out["env_qpos"], out["env_qvel"] = ro.env.get_state()
+    top = rb._top
+    rows = rb._gather((np.arange(top - N_ENV, top) + REPLAY_CAP) % REPLAY_CAP,
+                      keys=("observations", "actions", "rewards", "terminals", "next_observations"))
+    for k, v in rows.items():
+        out["last_step_" + k] = v.astype(np.float32)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg (roofline, co-resident seeds, configs 3 / 4 / 5, CPU baselines, split run); "
+                         "the --no-* switches below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--full-cpu-baseline", action="store_true",
                     help="time the CPU leg on BASELINE.md §3's protocol (1k warm-up + 3 x 10k timed steps, ~3 min) instead of the short one")
@@ -621,13 +647,15 @@ def main():
     per_rank_ms = R.gather(1e3 * dt / args.steps)
     dt, t_sample, t_train = R.max_over_ranks([dt, t_sample, t_train])
     phase_timed = tr.phase_state()   # read HERE: the legs below put other contexts' kernels on this GPU, and a window that meets them falls back
-    want_split = (world > 1 or os.environ.get("ILSX_BENCH_FORCE_DIST")) and not args.no_split_run
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, ro, rb)   # before the roofline leg below takes more gradient steps on `tr`
+    want_split = args.full and (world > 1 or os.environ.get("ILSX_BENCH_FORCE_DIST")) and not args.no_split_run
 
     # ---- roofline leg (rank 0): HIP events around every kernel launch (library instrumentation; graph bypassed).  BEFORE the legs below: they
     # put other contexts' kernels on this GPU, a train window that meets them is rolled back to one launch per stage and stays there, and the
     # kernel this leg names would no longer be the one the timed loop ran (round 6's first lines named k_mlp2_fwd_split for that reason)
     prof = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         _lib.check(lib.ilsx_prof_reset(ctx.h))
         _lib.check(lib.ilsx_prof_enable(ctx.h, 1))
         tr.train_from_replay(rb, 200, B)
@@ -645,9 +673,9 @@ def main():
     multi = world > 1 or bool(os.environ.get("ILSX_BENCH_FORCE_DIST"))   # the override runs the every-rank form of the legs on a one-rank group
     # each leg holds two one-word collectives (a barrier in front of its timed loop, the max of the ranks' times behind it): Ranks.leg keeps a
     # rank whose leg raised in step with the others
-    if not args.no_seeds:
+    if args.full and not args.no_seeds:
         legs["co_resident_seeds"] = R.leg(lambda: co_resident_seeds(R=R if multi else None), 2 if multi else 0)
-    if multi and not args.no_aux:
+    if args.full and multi and not args.no_aux:
         import bench_aux
 
         def humanoid_leg():
@@ -662,6 +690,27 @@ def main():
     if rank == 0:
         grad_total = world * args.steps * GRAD_PER_CALL
         env_total = world * args.steps * N_ENV
+        result = dict(
+            metric="env-steps/s + SAC grad-steps/s, Hopper-v2 4096 envs", value=grad_total / dt, unit="grad-steps/s",
+            n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=1e3 * dt / args.steps,
+            higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
+            config=dict(workload="SAC Hopper-v2 dims (o=11,a=3), 4096 parallel envs, 256-256 MLP, batch 256, "
+                                 "replay 1e6 rows; step = 1 vec-env step (4096 env-steps) + 1000 grad steps "
+                                 "(sac_hopper.yaml:17-20)", env=ro.describe(), replicas=world,
+                        parallelism=f"{world} independent replicas (seed sharding, no collective)"),
+            env_steps_per_s=env_total / dt, env_steps_per_s_sample_phase=env_total / t_sample,
+            grad_steps_per_s_train_phase=grad_total / t_train,
+            # which step path the timed loop ran on: the merged phase kernels (4 launches per step) unless a window had to be rolled back
+            # (another process's kernels on this GPU) and the agent fell back to one launch per stage (include/ilsx.h ilsx_sac_phase_state)
+            phase_kernels=phase_timed,
+            # per-rank step times behind the max-over-ranks `value` (the driver computes efficiency itself from its per-N runs); the
+            # replica leg has NO data-path collective, so a slow rank is a placement / clock matter, not a communication one
+            scaling_detail=dict(per_rank_ms=per_rank_ms, max_over_min=max(per_rank_ms) / min(per_rank_ms), numa_rank0=numa,
+                                rccl_env={k: os.environ[k] for k in RCCL_ENV_KEYS if k in os.environ},
+                                note="RCCL is used for the barrier + max-time of this leg and for the gradient all-reduce of `split_run` "
+                                     "only; message sizes there are 0.55 MB (critics) and 0.28 MB (actor | alpha): latency-bound on "
+                                     "xGMI, so NCCL_ALGO / NCCL_PROTO are left to RCCL's tuner unless set in the environment"))
+    if rank == 0 and args.full:
         fl = flops_per_step()
         # a slot's algorithmic FLOPs per step: the merged phase kernels (one launch = three stages) carry their own count
         def slot_flops(k):
@@ -723,26 +772,8 @@ def main():
         gbs_big = alg_bytes / (ms.value * 1e-3 / nl.value) / 1e9
         roofline_replay["beyond_infinity_cache"] = dict(ring_bytes=4_000_000 * rec.value * 4, achieved=gbs_big, frac=gbs_big / PEAK_HBM_GBS,
                                                          avg_launch_us=ms.value * 1e3 / nl.value)
-        result = dict(
-            metric="env-steps/s + SAC grad-steps/s, Hopper-v2 4096 envs", value=grad_total / dt, unit="grad-steps/s",
-            n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=1e3 * dt / args.steps,
-            higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
-            config=dict(workload="SAC Hopper-v2 dims (o=11,a=3), 4096 parallel envs, 256-256 MLP, batch 256, "
-                                 "replay 1e6 rows; step = 1 vec-env step (4096 env-steps) + 1000 grad steps "
-                                 "(sac_hopper.yaml:17-20)", env=ro.describe(), replicas=world,
-                        parallelism=f"{world} independent replicas (seed sharding, no collective)"),
-            env_steps_per_s=env_total / dt, env_steps_per_s_sample_phase=env_total / t_sample,
-            grad_steps_per_s_train_phase=grad_total / t_train, roofline=roofline, roofline_replay=roofline_replay,
-            # which step path the timed loop ran on: the merged phase kernels (4 launches per step) unless a window had to be rolled back
-            # (another process's kernels on this GPU) and the agent fell back to one launch per stage (include/ilsx.h ilsx_sac_phase_state)
-            phase_kernels=phase_timed, phase_kernels_roofline_leg=phase_roofline, phase_kernels_after_legs=tr.phase_state(),
-            # per-rank step times behind the max-over-ranks `value` (the driver computes efficiency itself from its per-N runs); the
-            # replica leg has NO data-path collective, so a slow rank is a placement / clock matter, not a communication one
-            scaling_detail=dict(per_rank_ms=per_rank_ms, max_over_min=max(per_rank_ms) / min(per_rank_ms), numa_rank0=numa,
-                                rccl_env={k: os.environ[k] for k in RCCL_ENV_KEYS if k in os.environ},
-                                note="RCCL is used for the barrier + max-time of this leg and for the gradient all-reduce of `split_run` "
-                                     "only; message sizes there are 0.55 MB (critics) and 0.28 MB (actor | alpha): latency-bound on "
-                                     "xGMI, so NCCL_ALGO / NCCL_PROTO are left to RCCL's tuner unless set in the environment"))
+        result.update(roofline=roofline, roofline_replay=roofline_replay, phase_kernels_roofline_leg=phase_roofline,
+                      phase_kernels_after_legs=tr.phase_state())
         result.update(legs)
         if world == 1 and not args.no_aux:
             # BASELINE.json configs 3, 4, 5 (their single-GPU shapes) beside the headline, each with the roofline block of its dominant

@@ -8,7 +8,7 @@ ROOT=$(pwd)
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 python -m pytest tests -m gpu -q > $OUT/gpu_tests.log 2>&1; tail -3 $OUT/gpu_tests.log
-timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 timeout 600 python bench_aux.py td3 seeds > $OUT/bench_aux.log 2>&1
 ILSX_NO_PHASE=1 timeout 200 python tools/step_gantt.py > $OUT/step_gantt_8launch.txt 2>&1
 timeout 200 python tools/phase_gantt.py > $OUT/phase_gantt.txt 2>&1
@@ -20,7 +20,7 @@ timeout 100 python tools/rollout_overhead.py 8192 >> $OUT/rollout_overhead.txt 2
 : > $OUT/split_run_1rank.jsonl
 for form in "phase_kernels:ILSX_SPLIT_SEGMENTS=0" "one_launch_per_stage:ILSX_SPLIT_NO_PHASE=1" "graph_segments:ILSX_SPLIT_SEGMENTS=1" "whole_step_graph:ILSX_SPLIT_GRAPH=1"; do
   label=${form%%:*}; kv=${form#*:}
-  env $kv ILSX_BENCH_FORCE_DIST=1 timeout 300 python bench.py --no-aux --no-cpu-baseline --no-seeds --steps 5 --warmup 2 2> /dev/null | grep '^{' | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(dict(form='$label', **(d.get('split_run') or {}))))" >> $OUT/split_run_1rank.jsonl 2>&1
+  env $kv ILSX_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --no-aux --no-cpu-baseline --no-seeds --steps 5 --warmup 2 2> /dev/null | grep '^{' | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(dict(form='$label', **(d.get('split_run') or {}))))" >> $OUT/split_run_1rank.jsonl 2>&1
 done
 timeout 120 python tools/discbn_rate.py > $OUT/discbn_rate.txt 2>&1
 timeout 200 bash tools/ppo_ab.sh ILSX_DW_BIG=1 ILSX_DW_BIG=0 > $OUT/ppo_ab.txt 2>&1
@@ -42,7 +42,7 @@ timeout 300 bash tools/ab_dw_low.sh > $OUT/dw_low_ab.txt 2>&1
 hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -shared -fPIC tools/ubench/env3d_phases.hip -o /tmp/libe3p.so 2> /dev/null
 (python tools/ubench/env3d_phases.py humanoid 1024 8; python tools/ubench/env3d_phases.py ant 1024 8) > $OUT/env3d_phases.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-ILSX_NO_GRAPH=1 timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/rocprof -o $TAG -- python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-split-run --no-aux > $ROOT/$OUT/rocprof.log 2>&1
+ILSX_NO_GRAPH=1 timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/rocprof -o $TAG -- python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-split-run --no-aux > $ROOT/$OUT/rocprof.log 2>&1
 cd $ROOT
 f=$(find $OUT/rocprof -name "*.db" | head -1)
 python tools/rocpd_summary.py "$f" > $OUT/kernel_stats.csv 2> $OUT/summary.err

@@ -8,7 +8,7 @@ python -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1; tail -5 $OUT/gpu_
 timeout 120 python tools/discbn_rate.py > $OUT/discbn_rate.txt 2>&1; cat $OUT/discbn_rate.txt
 split() {  # $1 = label, rest = env
   label=$1; shift
-  env "$@" ILSX_BENCH_FORCE_DIST=1 timeout 300 python bench.py --no-aux --no-cpu-baseline --no-seeds --steps 5 --warmup 2 2> $OUT/split_$label.err | grep '^{' | \
+  env "$@" ILSX_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --no-aux --no-cpu-baseline --no-seeds --steps 5 --warmup 2 2> $OUT/split_$label.err | grep '^{' | \
     python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(dict(form='$label', headline=d.get('value'), **(d.get('split_run') or {}))))"
 }
 : > $OUT/split_run_1rank.jsonl
