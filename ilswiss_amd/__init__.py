@@ -10,3 +10,4 @@ from .networks import (FlattenMlp, MakeDeterministic, Mlp,  # noqa: F401
                        ReparamTanhMultivariateGaussianPolicy)
 from .replay import EnvReplayBuffer, SimpleReplayBuffer  # noqa: F401
 from .sac import SoftActorCritic, SoftActorCriticGroup, Trainer  # noqa: F401
+from .mbpo import BNN, MBPO, BNNTrainer, FakeEnv  # noqa: F401

@@ -129,6 +129,12 @@ class OptMeta(C.Structure):  # ilsx_opt_meta
     _fields_ = [("t", C.c_int64), ("rng_step", C.c_uint64), ("n_train_steps", C.c_int64)]
 
 
+class BnnCfg(C.Structure):  # ilsx_bnn_cfg
+    _fields_ = [("ensemble", C.c_int32), ("in_dim", C.c_int32), ("out_dim", C.c_int32), ("hidden", C.c_int32), ("n_hidden", C.c_int32),
+                ("max_batch", C.c_int32), ("lr", C.c_float), ("reward_scale", C.c_float), ("init_w", C.c_float),
+                ("weight_decay", C.c_float * 9)]
+
+
 class DiscStats(C.Structure):
     _fields_ = [("ce_loss", C.c_float), ("grad_pen", C.c_float), ("accuracy", C.c_float)]
 
@@ -286,6 +292,23 @@ PROTOTYPES = {
     "ilsx_sac_phase_state": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ilsx_sac_debug_break_phase": (C.c_int, [vp]),
     "ilsx_sac_set_alpha_opt": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, C.c_uint64]),
+    "ilsx_bnn_create": (C.c_int, [vp, C.POINTER(BnnCfg), C.POINTER(vp)]),
+    "ilsx_bnn_destroy": (C.c_int, [vp]),
+    "ilsx_bnn_num_params": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
+    "ilsx_bnn_init": (C.c_int, [vp, C.c_uint64]),
+    "ilsx_bnn_get_params": (C.c_int, [vp, vp, C.c_size_t]),
+    "ilsx_bnn_set_params": (C.c_int, [vp, vp, C.c_size_t]),
+    "ilsx_bnn_get_opt": (C.c_int, [vp, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
+    "ilsx_bnn_set_opt": (C.c_int, [vp, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
+    "ilsx_bnn_set_normalizer": (C.c_int, [vp, vp, vp]),
+    "ilsx_bnn_get_normalizer": (C.c_int, [vp, vp, vp]),
+    "ilsx_bnn_fit_stats": (C.c_int, [vp, vp, vp, C.c_int]),
+    "ilsx_bnn_train_batch": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, vp]),
+    "ilsx_bnn_mse": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp]),
+    "ilsx_bnn_predict": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int]),
+    "ilsx_bnn_debug_padding": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "ilsx_mbpo_model_step": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                       C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -649,6 +649,64 @@ int ilsx_rollout_step_relabel(ilsx_vecenv* env, ilsx_net* pi, ilsx_net* expert, 
 /* finished episodes and the sum of their returns since the last reset of the counters */
 int ilsx_rollout_stats(ilsx_vecenv* env, double* episodes, double* return_sum, int reset);
 
+
+/* ---------------------------------------------------------------- MBPO: probabilistic ensemble dynamics model (ilswiss_amd/csrc/bnn.h)
+ * BNN (rlkit/torch/common/networks.py:149-279): E members of n_hidden SiLU layers of `hidden` units and a head [mean | raw] of
+ * 2 * out_dim, raw soft-clamped to a log-variance in [-10, 0.5]; inputs normalised by FixedNormalizer (normalizer.py:81-114).
+ * BNNTrainer (mbpo/bnn_trainer.py:71-87,141-154): Adam (0.9, 0.999, 1e-8) with per-layer L2 weight decay.  Rows come from a replay
+ * ring's records: inputs [obs | act], targets [reward_scale * rew | next_obs - obs], built on the device.  Parameters cross the ABI in
+ * the reference's named_parameters() order, per layer weight[E, in, out] then bias[E, 1, out] (HOST fp32); padding is invisible. */
+typedef struct ilsx_bnn ilsx_bnn;
+#define ILSX_BNN_MAX_HID 8
+typedef struct {
+  int32_t ensemble;     /* num_nets */
+  int32_t in_dim;       /* obs_dim + act_dim */
+  int32_t out_dim;      /* obs_dim + 1 (BNN output_size; the head is 2 * out_dim wide) */
+  int32_t hidden;       /* net_size (<= 256) */
+  int32_t n_hidden;     /* num_hidden_layers, 1..ILSX_BNN_MAX_HID */
+  int32_t max_batch;    /* largest ilsx_bnn_train_batch B */
+  float lr, reward_scale, init_w;
+  float weight_decay[ILSX_BNN_MAX_HID + 1];   /* per layer (hidden layers, then the head), on weights and biases */
+} ilsx_bnn_cfg;
+int ilsx_bnn_create(ilsx_ctx* ctx, const ilsx_bnn_cfg* cfg, ilsx_bnn** out);
+int ilsx_bnn_destroy(ilsx_bnn* bnn);
+int ilsx_bnn_num_params(const ilsx_bnn* bnn, size_t* n);
+/* hidden weights U(+-1/sqrt(in*out)) (fanin_init on [E,in,out], pytorch_util.py:20-29), hidden biases 0.1, head weight / bias
+ * U(+-init_w); host RNG seeded by `seed` */
+int ilsx_bnn_init(ilsx_bnn* bnn, uint64_t seed);
+int ilsx_bnn_get_params(const ilsx_bnn* bnn, float* dst_host, size_t n);
+int ilsx_bnn_set_params(ilsx_bnn* bnn, const float* src_host, size_t n);
+/* Adam exp_avg / exp_avg_sq in the parameter layout; meta.t = the shared step count, meta.rng_step = the model-step Philox counter */
+int ilsx_bnn_get_opt(const ilsx_bnn* bnn, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);
+int ilsx_bnn_set_opt(ilsx_bnn* bnn, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
+/* FixedNormalizer mean / std (HOST fp32 [in_dim]; std as stored, its 1e-8 included) */
+int ilsx_bnn_set_normalizer(ilsx_bnn* bnn, const float* mean_host, const float* std_host);
+int ilsx_bnn_get_normalizer(const ilsx_bnn* bnn, float* mean_host, float* std_host);
+/* bnn_trainer.py:113-118: mean and unbiased std of the inputs of ring rows idx[0..n) (device int32 ring slots); std < 1e-12 -> 1;
+ * then + 1e-8 (normalizer.py:101-103).  Sets the normaliser. */
+int ilsx_bnn_fit_stats(ilsx_bnn* bnn, ilsx_replay* rb, const int32_t* idx, int n);
+/* One BNNTrainer batch (bnn_trainer.py:136-154): member e trains on ring rows idx[e * idx_member_stride + 0..B) (device int32);
+ * loss_host (nullable, [E]): each member's mean((mu - t)^2 e^-lv) + mean(lv) before the step (synchronises). */
+int ilsx_bnn_train_batch(ilsx_bnn* bnn, ilsx_replay* rb, const int32_t* idx, int64_t idx_member_stride, int B, float* loss_host);
+/* BNNTrainer.compute_loss (bnn_trainer.py:71-87) per member over ring rows idx[e * idx_member_stride + 0..n): add_var = 0 is the
+ * holdout / train MSE; out_host[E]; fixed reduction order (deterministic).  idx_member_stride = 0: the same rows for every member. */
+int ilsx_bnn_mse(ilsx_bnn* bnn, ilsx_replay* rb, const int32_t* idx, int64_t idx_member_stride, int n, int add_var, float* out_host);
+/* BNN.predict(x, factored=True) (networks.py:265-275): x[n, in_dim] (device) -> mean[E, n, out_dim], var (or log-var when
+ * ret_log_var) [E, n, out_dim] (device). */
+int ilsx_bnn_predict(ilsx_bnn* bnn, const float* x, int n, float* mean, float* var, int ret_log_var);
+/* FakeEnv.step + one step of MBPO._rollout_model (fake_env.py:30-75, mbpo.py:244-270), on the device: actions from `pi`'s stochastic
+ * get_actions (or the given act[n, a]), the ensemble forward, a member per row uniform over elites_host[n_elites] by Philox (or
+ * model_idx[n]), next_obs = obs + mu[1:] + sqrt(var) z, rew = mu[0] + sqrt(var) z (z: eps[n, out_dim] or Philox; none when
+ * deterministic), terminals by ilsx_is_terminal(term_kind), the n rows into model_rb (nullable) followed by terminate_episode, and
+ * the next observations of the non-terminal rows compacted in order into obs_next.  act_out [n, a] / model_idx_out [n] nullable.
+ * *n_survivors is the one value read back. */
+/* (tests only) the largest |value| over the padded entries of the internal blocks (W, Wt, b of every layer and member, and Adam's
+ * m / v): 0 while the padding is intact. */
+int ilsx_bnn_debug_padding(const ilsx_bnn* bnn, double* max_abs);
+int ilsx_mbpo_model_step(ilsx_bnn* bnn, ilsx_net* pi, ilsx_replay* model_rb, int term_kind, const float* obs, const float* act, int n,
+                         const int32_t* elites_host, int n_elites, int deterministic, const float* eps, const int32_t* model_idx,
+                         float* act_out, int32_t* model_idx_out, float* obs_next, int* n_survivors);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1363,11 +1363,118 @@ def gen_her():
     save("g22_her_buffer", **rec)
 
 
+def gen_mbpo():
+    """G27: MBPO — the reference's BNN (networks.py:149-279: init rule, FixedNormalizer, factored forward), BNNTrainer
+    (bnn_trainer.py: compute_loss with and without the variance term, one epoch of train_step = three Adam steps with per-layer
+    weight decay and a short last batch, holdout MSE, elite order, BNN Loss), FakeEnv.step on Hopper with np.random.normal injected and
+    the members given, and MBPO's rollout-length schedule / get_batch split (mbpo.py:170-205).  Small widths (H = 40, padded to 48
+    inside libilsx) keep the file small; every draw comes from this group's own seeds."""
+    import importlib.util
+    import types
+    from types import SimpleNamespace
+    sys.modules.setdefault("envpool", types.ModuleType("envpool"))   # imported by rlkit.envs (mbpo.py's import chain), never used here
+    envs = sys.modules.get("rlkit.envs")
+    if envs is not None and not list(getattr(envs, "__path__", [])):   # the her group's stand-in package: let its submodules load from disk
+        envs.__path__ = [os.path.join(H.REF, "rlkit", "envs")]
+    from rlkit.torch.algorithms.mbpo import mbpo as rmbpo
+    from rlkit.torch.algorithms.mbpo.bnn_trainer import BNNTrainer
+    from rlkit.torch.algorithms.mbpo.fake_env import FakeEnv
+    from rlkit.torch.common.networks import BNN
+    spec = importlib.util.spec_from_file_location("ref_terminals_g27", os.path.join(H.REF, "rlkit", "envs", "terminals.py"))
+    ref_terminals = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref_terminals)
+    E, o, a, Hd, nh, N, B = 3, 11, 3, 40, 4, 150, 48
+    torch.manual_seed(2727)
+    rng = np.random.default_rng(2727)
+    bnn = BNN(hidden_sizes=[Hd] * nh, output_size=o + 1, input_size=o + a, num_nets=E)
+    out = {"p0_" + str(i): n(p) for i, (_, p) in enumerate(bnn.named_parameters())}
+    # dataset (rows of a replay buffer) and the trainer of the shipped specs' keys, reward_scale 2 so the target scaling shows
+    obs = rng.normal(0, 1, (N, o)).astype(np.float32)
+    act = rng.uniform(-1, 1, (N, a)).astype(np.float32)
+    rew = rng.normal(0, 1, (N, 1)).astype(np.float32)
+    nobs = (obs + 0.2 * rng.normal(0, 1, (N, o))).astype(np.float32)
+    out.update(obs=obs, act=act, rew=rew, nobs=nobs)
+    tr = BNNTrainer(bnn, lr=1e-3, num_elites=2, reward_scale=2.0, batch_size=B, max_epochs=1, holdout_ratio=0.2, max_holdout=5000, log_freq=1)
+    # forward and compute_loss on the parameters as initialised, with a normaliser set from the data (bnn_trainer.py:113-118)
+    x = torch.cat((t(obs), t(act)), -1)
+    tg = torch.cat((2.0 * t(rew), t(nobs) - t(obs)), -1)
+    bnn.normalizer.set_mean(n(torch.mean(x, 0, keepdim=True)))
+    sd = torch.std(x, 0, keepdim=True)
+    sd[sd < 1e-12] = 1.0
+    bnn.normalizer.set_std(n(sd))
+    out.update(fwd_norm_mean=np.asarray(bnn.normalizer.mean, np.float32), fwd_norm_std=np.asarray(bnn.normalizer.std, np.float32))
+    xq = rng.normal(0, 1, (29, o + a)).astype(np.float32)
+    with torch.no_grad():
+        m_, v_ = bnn.predict(t(xq), factored=True)
+        _, lv_ = bnn(t(xq), ret_log_var=True)
+        idx = rng.integers(0, N, (E, 40))
+        gi, gt_ = torch.stack([x[i] for i in idx]), torch.stack([tg[i] for i in idx])
+        l1 = tr.compute_loss(gi, gt_, add_var_loss=True)
+        l0 = tr.compute_loss(gi, gt_, add_var_loss=False)
+    out.update(fwd_x=xq, fwd_mean=n(m_), fwd_var=n(v_), fwd_logvar=n(lv_), loss_idx=idx.astype(np.int32), loss_var=n(l1), loss_novar=n(l0))
+    # one epoch of train_step: permutation / bootstrap / shuffle draws from np.random seeded here; 120 training rows in batches of 48, 48, 24
+    seed = 2728
+    np.random.seed(seed)
+    perm = np.random.permutation(N)
+    idxs = np.random.randint(N - 30, size=[E, N - 30])
+    np.random.seed(seed)
+    tr.train_step({"observations": t(obs), "actions": t(act), "rewards": t(rew), "next_observations": t(nobs), "terminals": t(np.zeros((N, 1), np.float32))})
+    ho = perm[:30]
+    with torch.no_grad():
+        hx = torch.tile(x[ho][None], [E, 1, 1])
+        ht = torch.tile(torch.cat((2.0 * t(rew), t(nobs) - t(obs)), -1)[ho][None], [E, 1, 1])
+        ho_mse = n(tr.compute_loss(hx, ht, add_var_loss=False))
+    out.update(train_seed=np.int64(seed), train_perm=perm.astype(np.int64), train_idxs=idxs.astype(np.int64),
+               train_norm_mean=np.asarray(bnn.normalizer.mean, np.float32), train_norm_std=np.asarray(bnn.normalizer.std, np.float32),
+               train_holdout_mse=ho_mse, train_elites=np.asarray(tr._model_idx, np.int64), train_bnn_loss=np.float32(tr.eval_statistics["BNN Loss"]))
+    out.update({"p3_" + str(i): n(p) for i, (_, p) in enumerate(bnn.named_parameters())})
+    # FakeEnv.step on Hopper observations straddling the height bound, with the noise and the members given
+    ns = 64
+    fo = np.zeros((ns, o), np.float32)
+    fo[:, 0] = rng.uniform(0.6, 1.6, ns)
+    fo[:, 1:] = rng.normal(0, 0.05, (ns, o - 1))
+    fa = rng.uniform(-1, 1, (ns, a)).astype(np.float32)
+    z = rng.normal(0, 1, (E, ns, o + 1))
+    midx = rng.integers(0, E, ns)
+    env = FakeEnv(bnn, ref_terminals.HopperTerminalFunc.is_terminal, lambda k: midx[:k])
+    real_normal = np.random.normal
+    np.random.normal = lambda size=None, **kw: z.reshape(size)
+    try:
+        nob, rw, term, _ = env.step(fo, fa)
+    finally:
+        np.random.normal = real_normal
+    out.update(fe_obs=fo, fe_act=fa, fe_noise=z, fe_midx=midx.astype(np.int32), fe_next_obs=np.asarray(nob), fe_rew=np.asarray(rw),
+               fe_term=np.asarray(term))
+    # MBPO._set_rollout_length and get_batch's split (real rows, model rows) on stand-ins for the algorithm and its buffers
+    lens = []
+    for sched in ([20, 150, 1, 15], [20, 150, 1, 1], [0, 2, 1, 3]):
+        for ep in (0, 1, 2, 19, 20, 21, 85, 149, 150, 300):
+            me = SimpleNamespace(rollout_schedule=sched, rollout_length=None)
+            rmbpo.MBPO._set_rollout_length(me, ep)
+            lens.append([*sched, ep, me.rollout_length])
+    split = []
+
+    class _Rb:
+        def __init__(self, size):
+            self._size = size
+
+        def random_batch(self, k):
+            return {"observations": np.zeros((k, 1), np.float32)}
+    for bs, rr, msize in ((256, 0.05, 0), (256, 0.05, 10), (256, 0.1, 5), (100, 0.33, 1), (256, 1.0, 3)):
+        me = SimpleNamespace(real_ratio=rr, batch_size=bs, model_replay_buffer=_Rb(msize), replay_buffer=_Rb(10**6))
+        b = rmbpo.MBPO.get_batch(me)
+        real = int(bs * (rr if msize > 0 else 1.0))
+        assert b["observations"].shape[0] == bs
+        split.append([bs, rr, msize, real, bs - real])
+    out.update(sched=np.asarray(lens, np.float64), split=np.asarray(split, np.float64))
+    save("g27_mbpo", **out)
+
+
 # generation order: a group that reads another group's file comes after it (replay_trajs loads g10_replay.npz, written by replay)
 GROUPS = dict(mlp=gen_mlp, mlp_unequal=gen_mlp_unequal, head=gen_head, sac_alpha=gen_sac_alpha, sac_v=gen_sac_v, td3=gen_td3, ppo=gen_ppo,
               disc=gen_disc, disc_bn=gen_disc_bn, disc_blocks=gen_disc_blocks, disc_branches=gen_disc_branches, replay=gen_replay,
               replay_trajs=gen_replay_trajs, her=gen_her, absorbing=gen_absorbing, bc=gen_bc, rms=gen_rms_actionmap, terminals=gen_terminals,
-              eval_stats=gen_eval_stats, variants=gen_variants, logger_csv=gen_logger_csv, logdir=gen_logdir)
+              eval_stats=gen_eval_stats, variants=gen_variants, logger_csv=gen_logger_csv, logdir=gen_logdir, mbpo=gen_mbpo)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GROUPS)
