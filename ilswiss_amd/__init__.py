@@ -6,8 +6,9 @@ the Python classes below keep the reference's Trainer / ReplayBuffer / policy na
 Importing the classes is cheap; touching a GPU object without the built library raises.
 """
 from .device import Context, DevArray, get_context, set_gpu_mode  # noqa: F401
-from .networks import (FlattenMlp, MakeDeterministic, Mlp,  # noqa: F401
+from .networks import (DiscretePolicy, FlattenMlp, MakeDeterministic, Mlp,  # noqa: F401
                        ReparamTanhMultivariateGaussianPolicy)
 from .replay import EnvReplayBuffer, SimpleReplayBuffer  # noqa: F401
 from .sac import SoftActorCritic, SoftActorCriticGroup, Trainer  # noqa: F401
 from .mbpo import BNN, MBPO, BNNTrainer, FakeEnv  # noqa: F401
+from .discrete_sac import DiscreteSoftActorCritic  # noqa: F401

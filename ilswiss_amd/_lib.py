@@ -92,6 +92,16 @@ class Td3Stats(C.Structure):  # ilsx_td3_stats
                 ("bellman1", C.c_float * 4), ("bellman2", C.c_float * 4), ("policy_action", C.c_float * 4)]
 
 
+class DsacCfg(C.Structure):  # ilsx_dsac_cfg
+    _fields_ = [("discount", C.c_float), ("reward_scale", C.c_float), ("alpha", C.c_float), ("soft_target_tau", C.c_float),
+                ("policy_lr", C.c_float), ("qf_lr", C.c_float), ("beta_1", C.c_float), ("max_batch", C.c_int32)]
+
+
+class DsacStats(C.Structure):  # ilsx_dsac_stats
+    _fields_ = [("qf1_loss", C.c_float), ("qf2_loss", C.c_float), ("policy_loss", C.c_float),
+                ("q1_pred", C.c_float * 4), ("q2_pred", C.c_float * 4)]
+
+
 class SacvCfg(C.Structure):  # ilsx_sacv_cfg
     _fields_ = [("reward_scale", C.c_float), ("discount", C.c_float), ("alpha", C.c_float), ("policy_lr", C.c_float),
                 ("qf_lr", C.c_float), ("vf_lr", C.c_float), ("soft_target_tau", C.c_float),
@@ -307,6 +317,18 @@ PROTOTYPES = {
     "ilsx_bnn_mse": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp]),
     "ilsx_bnn_predict": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int]),
     "ilsx_bnn_debug_padding": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "ilsx_net_set_categorical": (C.c_int, [vp, C.c_int]),
+    "ilsx_policy_log_pis": (C.c_int, [vp, vp, C.c_int, vp]),
+    "ilsx_vecenv_create_classic": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "ilsx_vecenv_action_space": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "ilsx_dsac_create": (C.c_int, [vp, C.POINTER(DsacCfg), vp, vp, vp, C.POINTER(vp)]),
+    "ilsx_dsac_destroy": (C.c_int, [vp]),
+    "ilsx_dsac_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(DsacStats)]),
+    "ilsx_dsac_train_from_replay": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(DsacStats)]),
+    "ilsx_dsac_get_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_dsac_set_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_dsac_get_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
+    "ilsx_dsac_set_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
     "ilsx_mbpo_model_step": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                        C.POINTER(C.c_int)]),
 }

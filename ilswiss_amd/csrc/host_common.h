@@ -145,7 +145,10 @@ struct ilsx_net {
   bool noise_policy = false;
   float noise = 0.f, noise_clip = 0.f, max_act = 1.f;
   bool out_linear = false;   // output activation: identity (Mlp's default) instead of tanh (ilsx_net_set_output_linear)
+  bool categorical = false;  // DiscretePolicy (policies.py:39-101): LogSoftmax head, ilsx_policy_act writes an index (ilsx_net_set_categorical)
 };
+// DiscretePolicy's action draw from raw logits z[rows][n] (dsac.h k_categorical_act; ilsx_ac.hip)
+int launch_categorical_act(ilsx_ctx* ctx, const float* z, int rows, int n, int deterministic, unsigned long long step, float* act, float* logp);
 
 int net_upload_flat(ilsx_ctx* ctx, const NetLayout& L, float* dev_base, const float* src, size_t n, int src_is_device);
 int net_download_flat(ilsx_ctx* ctx, const NetLayout& L, const float* dev_base, float* dst, size_t n, int dst_is_device);

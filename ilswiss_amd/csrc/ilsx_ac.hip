@@ -306,6 +306,7 @@ extern "C" int ilsx_td3_create(ilsx_ctx* ctx, const ilsx_td3_cfg* cfg, ilsx_net*
   if (!ctx || !cfg || !pi || !q1 || !q2 || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_td3_create: NULL argument");
   const ilsx_mlp_cfg &cp = pi->lay.cfg, &c1 = q1->lay.cfg, &c2 = q2->lay.cfg;
   if (cp.n_heads != 1) ILSX_FAIL(ILSX_ERR_ARG, "TD3 policy is a single-head Mlp with tanh output (policies.py:130-188)");
+  if (pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "TD3 trains a continuous policy; this one is categorical (use ilsx_dsac_create)");
   if (c1.n_heads != 1 || c1.out_dim != 1 || memcmp(&c1, &c2, sizeof c1) != 0) ILSX_FAIL(ILSX_ERR_ARG, "qf1/qf2 must be identical single-output FlattenMlp's");
   if (c1.in_dim != cp.in_dim + cp.out_dim) ILSX_FAIL(ILSX_ERR_ARG, "qf input %d != obs %d + act %d", c1.in_dim, cp.in_dim, cp.out_dim);
   if (cfg->max_batch < 1 || cfg->max_batch > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "max_batch=%d out of range", cfg->max_batch);
@@ -871,4 +872,195 @@ extern "C" int ilsx_bc_set_opt(ilsx_bc* b, const float* m_host, const float* v_h
   if (!b) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
   ilsx_opt_meta m2; if (meta) m2 = *meta;
   return ac_opt(&b->g, 0, true, const_cast<float*>(m_host), const_cast<float*>(v_host), n, meta ? &m2 : nullptr);
+}
+
+// ================================================================================================ discrete SAC
+// rlkit/torch/algorithms/discrete_sac/discrete_sac.py:60-181 on the trunk kernels above plus the two loss kernels of dsac.h:
+//   fwd{pi(s) saved, pi(s'), TQ1(s'), TQ2(s')} ; fwd{Q1(s), Q2(s) saved} ; critic loss{target, dL/dQ_i[a]} ; bwd{Q1,Q2: given} ;
+//   dW+Adam+Polyak{Q1,Q2} ; fwd{Q1(s), Q2(s) updated} ; policy loss{dL/dz} ; bwd{pi: given} ; dW+Adam{pi} ; tick
+// pi(s) and pi(s') share the first launch because the policy does not change before its own update; the targets' soft update rides in the
+// critics' Adam epilogue because the critics do not change after it (the reference updates the targets after the policy step, :145).
+#include "dsac.h"
+
+int launch_categorical_act(ilsx_ctx* ctx, const float* z, int rows, int n, int deterministic, unsigned long long step, float* act, float* logp) {
+  if (rows <= 0) return ILSX_OK;
+  hipLaunchKernelGGL(k_categorical_act, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, z, rows, n, deterministic, ctx->seed,
+                     0x41435400u /* 'ACT' */, step, act, logp);
+  HIPCHK(hipGetLastError());
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_policy_log_pis(ilsx_net* pi, const float* obs, int n_rows, float* log_pis) {
+  if (!pi || !obs || !log_pis || n_rows < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_log_pis: bad argument");
+  if (!pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_log_pis: not a categorical policy (ilsx_net_set_categorical)");
+  if (n_rows == 0) return ILSX_OK;
+  ILSX_TRY(ilsx_mlp_forward(pi, obs, n_rows, log_pis));   // raw head, then log_softmax in place on the same stream
+  hipLaunchKernelGGL(k_categorical_log_softmax, dim3((n_rows + 255) / 256), dim3(256), 0, pi->ctx->stream, log_pis, n_rows, pi->lay.cfg.out_dim);
+  HIPCHK(hipGetLastError());
+  return ILSX_OK;
+}
+
+enum { DS_Q1 = 0, DS_Q2 = 1, DS_PI = 2 };
+struct ilsx_dsac {
+  AcAgent g;
+  ilsx_dsac_cfg cfg;
+  int n = 0;   // actions
+  float *zpi = nullptr, *zpn = nullptr, *q1 = nullptr, *q2 = nullptr, *tq1 = nullptr, *tq2 = nullptr, *q1n = nullptr, *q2n = nullptr;   // [cs][B][n]
+  float *gq1 = nullptr, *gq2 = nullptr, *gpi = nullptr;   // loss gradients [B][n]
+  float *y = nullptr, *qa1 = nullptr, *qa2 = nullptr, *ploss = nullptr;   // per-row statistics [B]
+  HeadSlabs slab(const float* p) const { return HeadSlabs{p, g.cs, g.max_batch}; }
+};
+
+extern "C" int ilsx_dsac_create(ilsx_ctx* ctx, const ilsx_dsac_cfg* cfg, ilsx_net* pi, ilsx_net* q1, ilsx_net* q2, ilsx_dsac** out) {
+  if (!ctx || !cfg || !pi || !q1 || !q2 || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dsac_create: NULL argument");
+  const ilsx_mlp_cfg &cp = pi->lay.cfg, &c1 = q1->lay.cfg, &c2 = q2->lay.cfg;
+  if (!pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "discrete SAC needs a categorical policy (ilsx_net_set_categorical)");
+  if (q1->categorical || q2->categorical) ILSX_FAIL(ILSX_ERR_ARG, "qf1 / qf2 must be plain FlattenMlp's, not policies");
+  if (c1.n_heads != 1 || memcmp(&c1, &c2, sizeof c1) != 0) ILSX_FAIL(ILSX_ERR_ARG, "qf1/qf2 must be identical single-head FlattenMlp's");
+  if (c1.in_dim != cp.in_dim || c1.out_dim != cp.out_dim)
+    ILSX_FAIL(ILSX_ERR_ARG, "qf maps obs %d -> %d actions, policy obs %d -> %d", c1.in_dim, c1.out_dim, cp.in_dim, cp.out_dim);
+  if (cfg->max_batch < 1 || cfg->max_batch > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "max_batch=%d out of range", cfg->max_batch);
+  HIPCHK(hipSetDevice(ctx->device));
+  ilsx_dsac* d = new ilsx_dsac();
+  d->cfg = *cfg;
+  d->n = cp.out_dim;
+  ilsx_net* nets[3] = {q1, q2, pi};
+  const int opt_of[3] = {0, 0, 1};
+  AcAgent* g = &d->g;
+  g->lr[0] = cfg->qf_lr; g->lr[1] = cfg->policy_lr; g->beta_1 = cfg->beta_1;   // discrete_sac.py:50-58
+  int rc = ac_init(g, ctx, nets, 3, opt_of, cfg->max_batch, cp.in_dim, 1);
+  const size_t B = (size_t)cfg->max_batch, n = (size_t)d->n, CS = (size_t)g->cs;
+  float** heads[] = {&d->zpi, &d->zpn, &d->q1, &d->q2, &d->tq1, &d->tq2, &d->q1n, &d->q2n};
+  for (float** b : heads) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B * n);
+  float** grads[] = {&d->gq1, &d->gq2, &d->gpi};
+  for (float** b : grads) if (rc == ILSX_OK) rc = ac_alloc(g, b, B * n);
+  float** rows[] = {&d->y, &d->qa1, &d->qa2, &d->ploss};
+  for (float** b : rows) if (rc == ILSX_OK) rc = ac_alloc(g, b, B);
+  if (rc == ILSX_OK) rc = ac_tick(g, 0, 0);
+  if (rc != ILSX_OK) { delete d; return rc; }
+  *out = d;
+  return ILSX_OK;
+}
+extern "C" int ilsx_dsac_destroy(ilsx_dsac* d) {
+  if (!d) return ILSX_OK;
+  ac_release(&d->g);
+  delete d;
+  return ILSX_OK;
+}
+
+static int dsac_step(ilsx_dsac* d, ilsx_dsac_stats* stats) {
+  AcAgent* g = &d->g;
+  const ilsx_dsac_cfg& c = d->cfg;
+  hipStream_t st = g->ctx->stream;
+  const int KP = g->L[DS_Q1].KP;
+  {  // pi(s) (saved: the policy's backward) ; pi(s') ; target critics at s'
+    FwdArgs A = ac_fwd_args(g, 4);
+    ac_fwd(g, A.t[0], DS_PI, false, g->s, g->o, nullptr, 0, true); ac_out(g, A.t[0], d->zpi);
+    ac_fwd(g, A.t[1], DS_PI, false, g->s2, g->o, nullptr, 0, false); ac_out(g, A.t[1], d->zpn);
+    ac_fwd(g, A.t[2], DS_Q1, true, g->s2, g->o, nullptr, 0, false); ac_out(g, A.t[2], d->tq1);
+    ac_fwd(g, A.t[3], DS_Q2, true, g->s2, g->o, nullptr, 0, false); ac_out(g, A.t[3], d->tq2);
+    ILSX_TRY(ac_launch_fwd(g, A, KP));
+  }
+  {  // critics at s (saved)
+    FwdArgs A = ac_fwd_args(g, 2);
+    ac_fwd(g, A.t[0], DS_Q1, false, g->s, g->o, nullptr, 0, true); ac_out(g, A.t[0], d->q1);
+    ac_fwd(g, A.t[1], DS_Q2, false, g->s, g->o, nullptr, 0, true); ac_out(g, A.t[1], d->q2);
+    ILSX_TRY(ac_launch_fwd(g, A, KP));
+  }
+  {
+    DsacCriticArgs A;
+    memset(&A, 0, sizeof A);
+    A.zn = d->slab(d->zpn); A.tq1 = d->slab(d->tq1); A.tq2 = d->slab(d->tq2); A.q1 = d->slab(d->q1); A.q2 = d->slab(d->q2);
+    A.act = g->ac; A.rew = g->r; A.done = g->d; A.g1 = d->gq1; A.g2 = d->gq2; A.y = d->y; A.qa1 = d->qa1; A.qa2 = d->qa2;
+    A.B = g->B; A.n = d->n; A.alpha = c.alpha; A.gamma = c.discount; A.reward_scale = c.reward_scale; A.inv_B = 1.0f / (float)g->B;
+    hipLaunchKernelGGL(k_dsac_critic_grad, dim3((g->B + 255) / 256), dim3(256), 0, st, A);
+    HIPCHK(hipGetLastError());
+  }
+  {
+    BwdArgs A = ac_bwd_args(g, 2, 0.f, 0.f);
+    for (int i = 0; i < 2; ++i) {
+      ac_bwd(g, A.t[i], i, true);
+      A.t[i].loss = LOSS_GIVEN; A.t[i].given = i == 0 ? d->gq1 : d->gq2;
+    }
+    ILSX_TRY(ac_launch_bwd(g, A));
+  }
+  ILSX_TRY(ac_dw_adam(g, DS_Q1, 2, true, c.soft_target_tau));   // Adam on both critics, then target <- (1 - tau) target + tau critic
+  {  // updated critics at s, detached (discrete_sac.py:134-139)
+    FwdArgs A = ac_fwd_args(g, 2);
+    ac_fwd(g, A.t[0], DS_Q1, false, g->s, g->o, nullptr, 0, false); ac_out(g, A.t[0], d->q1n);
+    ac_fwd(g, A.t[1], DS_Q2, false, g->s, g->o, nullptr, 0, false); ac_out(g, A.t[1], d->q2n);
+    ILSX_TRY(ac_launch_fwd(g, A, KP));
+  }
+  {
+    DsacPolicyArgs A;
+    memset(&A, 0, sizeof A);
+    A.z = d->slab(d->zpi); A.q1 = d->slab(d->q1n); A.q2 = d->slab(d->q2n); A.gz = d->gpi; A.ploss = d->ploss;
+    A.B = g->B; A.n = d->n; A.alpha = c.alpha; A.inv_B = 1.0f / (float)g->B;
+    hipLaunchKernelGGL(k_dsac_policy_grad, dim3((g->B + 255) / 256), dim3(256), 0, st, A);
+    HIPCHK(hipGetLastError());
+  }
+  {
+    BwdArgs A = ac_bwd_args(g, 1, 0.f, 0.f);
+    ac_bwd(g, A.t[0], DS_PI, true);
+    A.t[0].loss = LOSS_GIVEN; A.t[0].given = d->gpi;
+    ILSX_TRY(ac_launch_bwd(g, A));
+  }
+  ILSX_TRY(ac_dw_adam(g, DS_PI, 1, false, 0.f));
+  ILSX_TRY(ac_tick(g, 3, 1));
+  if (stats) {  // discrete_sac.py:149-175
+    const size_t B = (size_t)g->B;
+    std::vector<float> y, q1, q2, pl;
+    ILSX_TRY(ac_fetch(g, d->y, B, y)); ILSX_TRY(ac_fetch(g, d->qa1, B, q1)); ILSX_TRY(ac_fetch(g, d->qa2, B, q2));
+    ILSX_TRY(ac_fetch(g, d->ploss, B, pl));
+    HIPCHK(hipStreamSynchronize(st));
+    stats->qf1_loss = 0.5f * mean_sq_diff(q1, y);
+    stats->qf2_loss = 0.5f * mean_sq_diff(q2, y);
+    double s = 0;
+    for (float v : pl) s += v;
+    stats->policy_loss = (float)(s / (double)B);
+    msmm(q1.data(), B, stats->q1_pred); msmm(q2.data(), B, stats->q2_pred);
+  }
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_dsac_train_step(ilsx_dsac* d, const float* obs, const float* act, const float* rew, const float* done, const float* nobs,
+                                    int B, ilsx_dsac_stats* stats) {
+  if (!d) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dsac_train_step: NULL handle");
+  ILSX_TRY(ac_stage(&d->g, obs, act, rew, done, nobs, B, nullptr));
+  std::vector<float> a;   // actions.long() as a gather index (discrete_sac.py:71,84-85): refuse what torch.gather would
+  ILSX_TRY(ac_fetch(&d->g, d->g.ac, (size_t)B, a));
+  HIPCHK(hipStreamSynchronize(d->g.ctx->stream));
+  for (int i = 0; i < B; ++i)
+    if (!(a[i] >= 0.0f && a[i] < (float)d->n && a[i] == std::floor(a[i])))
+      ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dsac_train_step: action %g of row %d is not an index in [0, %d)", (double)a[i], i, d->n);
+  return dsac_step(d, stats);
+}
+extern "C" int ilsx_dsac_train_from_replay(ilsx_dsac* d, ilsx_replay* rb, int n_steps, int B, ilsx_dsac_stats* stats) {
+  if (!d || n_steps < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dsac_train_from_replay: bad argument");
+  HIPCHK(hipSetDevice(d->g.ctx->device));
+  for (int i = 0; i < n_steps; ++i) {
+    ILSX_TRY(ac_sample(&d->g, rb, B));
+    ILSX_TRY(dsac_step(d, i == 0 ? stats : nullptr));
+  }
+  return ILSX_OK;
+}
+// which: 0 qf1, 1 qf2, 2 policy, 3 target_qf1, 4 target_qf2
+extern "C" int ilsx_dsac_get_params(ilsx_dsac* d, int which, float* dst_host, size_t n) {
+  if (!d || which < 0 || which > 4) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dsac_get_params: bad handle or block %d", which);
+  return ac_params(&d->g, which, false, dst_host, n);
+}
+extern "C" int ilsx_dsac_set_params(ilsx_dsac* d, int which, const float* src_host, size_t n) {
+  if (!d || which < 0 || which > 4) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dsac_set_params: bad handle or block %d", which);
+  return ac_params(&d->g, which, true, const_cast<float*>(src_host), n);
+}
+extern "C" int ilsx_dsac_get_opt(ilsx_dsac* d, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta) {
+  if (!d) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  ILSX_TRY(ac_opt(&d->g, which, false, m_host, v_host, n, meta));
+  if (meta) meta->n_train_steps = 0;
+  return ILSX_OK;
+}
+extern "C" int ilsx_dsac_set_opt(ilsx_dsac* d, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta) {
+  if (!d) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  ilsx_opt_meta m2; if (meta) m2 = *meta;
+  return ac_opt(&d->g, which, true, const_cast<float*>(m_host), const_cast<float*>(v_host), n, meta ? &m2 : nullptr);
 }

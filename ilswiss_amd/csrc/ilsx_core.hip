@@ -987,6 +987,20 @@ extern "C" int ilsx_mlp_forward(ilsx_net* n, const float* x, int rows, float* y)
 extern "C" int ilsx_policy_act(ilsx_net* pi, const float* obs, int nrows, int deterministic, const float* eps,
                                float* act, float* logp) {
   if (!pi || !obs || !act || nrows < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: bad argument");
+  if (pi->categorical) {   // DiscretePolicy: raw logits through the trunk, then the categorical head's own launch
+    if (eps) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: a categorical policy takes no explicit noise");
+    HIPCHK(hipSetDevice(pi->ctx->device));
+    const int n = pi->lay.cfg.out_dim;
+    if (nrows == 0) return ILSX_OK;
+    if (pi->ws_rows < nrows) {
+      if (pi->ws_out) ILSX_TRY(ctx_free(pi->ctx, pi->ws_out));
+      pi->ws_out = nullptr; pi->ws_rows = 0;
+      ILSX_TRY(ctx_alloc(pi->ctx, (size_t)nrows * n * sizeof(float), (void**)&pi->ws_out));
+      pi->ws_rows = nrows;
+    }
+    ILSX_TRY(ilsx_mlp_forward(pi, obs, nrows, pi->ws_out));
+    return launch_categorical_act(pi->ctx, pi->ws_out, nrows, n, deterministic, ++pi->ctx->act_calls, act, logp);
+  }
   if (pi->lay.cfg.n_heads != 2 && !pi->noise_policy)
     ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: network has %d heads (need mean|log_std, or a noise policy)", pi->lay.cfg.n_heads);
   HIPCHK(hipSetDevice(pi->ctx->device));
@@ -1014,7 +1028,19 @@ extern "C" int ilsx_policy_act(ilsx_net* pi, const float* obs, int nrows, int de
 extern "C" int ilsx_net_set_noise_policy(ilsx_net* pi, float policy_noise, float policy_noise_clip, float max_act) {
   if (!pi) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_net_set_noise_policy: NULL network");
   if (pi->lay.cfg.n_heads != 1) ILSX_FAIL(ILSX_ERR_ARG, "a noise policy is a single-head Mlp (policies.py:130-188)");
+  if (pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "a categorical policy cannot be a noise policy");
   pi->noise_policy = true; pi->noise = policy_noise; pi->noise_clip = policy_noise_clip; pi->max_act = max_act;
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_net_set_categorical(ilsx_net* pi, int on) {
+  if (!pi) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_net_set_categorical: NULL network");
+  if (on) {
+    if (pi->lay.cfg.n_heads != 1 || pi->noise_policy) ILSX_FAIL(ILSX_ERR_ARG, "a categorical policy is a single-head Mlp (policies.py:39-101)");
+    if (pi->lay.cfg.out_dim < 2 || pi->lay.cfg.out_dim > ILSX_MAX_NO)
+      ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "a categorical policy has 2..%d actions, got %d", ILSX_MAX_NO, pi->lay.cfg.out_dim);
+  }
+  pi->categorical = on != 0;
   return ILSX_OK;
 }
 

@@ -63,7 +63,8 @@ struct ilsx_vecenv {
   // with one copy instead of K (each a serialised 8 us on the stream)
   int* grp_flush_dev = nullptr; int* grp_flush_host = nullptr; int grp_flush_n = 0;
   // 3-D engine (Ant / Humanoid, env3d.h): model, its device copy, and the per-env working set [E3Off::TOTAL][n_env]
-  int engine = 0, nq = 0, nv = 0;
+  int engine = 0, nq = 0, nv = 0;   // engine: 0 planar, 1 3-D, 2 classic control (classic_env.h)
+  int classic = -1, discrete_n = 0;  // engine 2: ILSX_CLASSIC_* task and the size of its Discrete action space (0 = Box actions)
   bool wave3 = true;   // wave-per-env kernels (env3d_wave.h); ILSX_ENV3D_LANE=1 selects the lane-per-env form (env3d.h) for A/B runs
   Spatial3Dev* hm3 = nullptr; Spatial3Dev* dm3 = nullptr; double* scr3 = nullptr;
   const float* policy_obs() const { return norm_obs ? obs_n : obs_cur; }
@@ -480,6 +481,7 @@ __device__ __forceinline__ void env_reset_state(const PlanarModelDev& m, uint64_
 }
 
 #include "env2d_group.h"
+#include "classic_env.h"
 #ifdef ILSX_EG_PROFILE
 extern "C" int ilsx_debug_eg_prof(unsigned long long* out16, int reset) {   // measurement build only
   if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_eg_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
@@ -856,6 +858,12 @@ static int launch_envg_step_t(ilsx_vecenv* e, const EnvStepArgs& A) {
 }
 static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
   if (A.n_ids <= 0) return ILSX_OK;
+  if (e->engine == 2) {
+    ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
+    ILSX_LAUNCH(ps, k_cartpole_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
+    HIPCHK(hipGetLastError());
+    return ILSX_OK;
+  }
   if (e->engine == 1) {
     ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
     if (e->wave3 && e->nv == 23)        // Humanoid
@@ -881,6 +889,12 @@ static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
 static int launch_env_reset(ilsx_vecenv* e, const int* ids_dev, int n_ids, float* obs) {
   if (n_ids <= 0) return ILSX_OK;
   const unsigned long long step = ++e->step_ctr;
+  if (e->engine == 2) {
+    hipLaunchKernelGGL(k_cartpole_reset, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, obs,
+                       e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
+    HIPCHK(hipGetLastError());
+    return ILSX_OK;
+  }
   if (e->engine == 1 && e->wave3) {
     hipLaunchKernelGGL(k_env3dw_reset, dim3(n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, (const Spatial3Dev*)e->dm3, e->qpos, e->qvel,
                        e->n_env, ids_dev, obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
@@ -1032,6 +1046,45 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
   }
   ILSX_TRY(launch_env_reset(e, nullptr, n_env, nullptr));
   *out = e;
+  return ILSX_OK;
+}
+// Classic control (classic_env.h): CartPole, one lane per env, the same handle and protocol entry points as the other engines.
+extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out) {
+  if (!ctx || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_classic: bad argument");
+  if (kind != ILSX_CLASSIC_CARTPOLE) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_classic: unknown kind %d", kind);
+  HIPCHK(hipSetDevice(ctx->device));
+  ilsx_vecenv* e = new ilsx_vecenv();
+  e->ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++; e->engine = 2;
+  e->classic = kind; e->discrete_n = 2;
+  e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1;
+  const size_t N = (size_t)n_env;
+  int rc = ctx_alloc(ctx, N * e->nq * 8, (void**)&e->qpos);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->nv * 8, (void**)&e->qvel);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->obs_cur);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->a * 4, (void**)&e->act);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->nobs);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->rew);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N, (void**)&e->done);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ep_len);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->obs_n);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, sizeof(ObsRms), (void**)&e->rms);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 8, (void**)&e->ep_ret);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, 4 * 8, (void**)&e->stats);
+  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ids);
+  if (rc != ILSX_OK) { delete e; return rc; }
+  {
+    ObsRms h;   // RunningMeanStd(): mean 0, var 1, count 0 (normalizer.py:133-136)
+    for (int i = 0; i < ENV_MAX_OBS; ++i) { h.mean[i] = 0.0; h.var[i] = 1.0; h.count[i] = 0.0; }
+    HIPCHK(hipMemcpyAsync(e->rms, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  ILSX_TRY(launch_env_reset(e, nullptr, n_env, nullptr));
+  *out = e;
+  return ILSX_OK;
+}
+extern "C" int ilsx_vecenv_action_space(const ilsx_vecenv* e, int* discrete_n) {
+  if (!e || !discrete_n) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_action_space: NULL argument");
+  *discrete_n = e->discrete_n;
   return ILSX_OK;
 }
 extern "C" int ilsx_vecenv_set_path_mode(ilsx_vecenv* e, int on) {
@@ -1198,6 +1251,7 @@ extern "C" int ilsx_is_terminal(ilsx_ctx* ctx, int kind, const float* next_obs, 
 // The envs are reset so that the observations they currently show follow the new map.
 extern "C" int ilsx_vecenv_set_obs_affine(ilsx_vecenv* e, const double* shift_host, const double* scale_host) {
   if (!e || !shift_host || !scale_host) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_set_obs_affine: NULL argument");
+  if (e->engine == 2) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_set_obs_affine: not available for classic-control envs");
   HIPCHK(hipSetDevice(e->ctx->device));
   for (int i = 0; i < e->o; ++i) {
     if (!(scale_host[i] != 0.0)) ILSX_FAIL(ILSX_ERR_ARG, "observation scale %d is zero", i);
@@ -1291,9 +1345,19 @@ static int rollout_paths_finish(ilsx_vecenv* e, bool synced = false, const int* 
     if (flags[i]) { envs.push_back(i); lens.push_back(flags[i] & ((1 << 30) - 1)); term.push_back((flags[i] >> 30) & 1); }
   return replay_insert_paths(rb, e->stage, e->stage_len, envs.data(), lens.data(), term.data(), (int)envs.size());
 }
+// A policy acts in the env's kind of action space: a categorical policy writes indices (Discrete envs), every other policy writes
+// continuous actions (Box envs).  Crossed, either the stepper reads an index as a force or an index lands in a continuous column.
+static int env_policy_kind_check(const ilsx_vecenv* e, const ilsx_net* pi, const char* who) {
+  if (pi && pi->categorical != (e->discrete_n > 0))
+    ILSX_FAIL(ILSX_ERR_ARG, "%s: a %s policy on an env with a %s action space", who, pi->categorical ? "categorical" : "continuous",
+              e->discrete_n > 0 ? "Discrete" : "Box");
+  return ILSX_OK;
+}
 static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, int label_deterministic, ilsx_replay* rb,
                              int max_path_length, int random_actions, int deterministic, int no_terminal, bool defer_paths = false) {
   if (!e || (!pi && !random_actions)) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_rollout_step: need a policy or random_actions");
+  ILSX_TRY(env_policy_kind_check(e, pi, "ilsx_rollout_step"));
+  ILSX_TRY(env_policy_kind_check(e, label_pi, "ilsx_rollout_step_relabel"));
   if (e->paths_pending) ILSX_FAIL(ILSX_ERR_STATE, "ilsx_rollout_step: the previous step was begun with ilsx_rollout_step_begin and never ended (ilsx_rollout_step_end)");
   ilsx_ctx* ctx = e->ctx;
   HIPCHK(hipSetDevice(ctx->device));
@@ -1306,7 +1370,11 @@ static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, i
     ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_rollout_step: norm_obs=1 with a replay ring is not supported (the fused insert records raw "
               "observations); use the on-policy rollout (ilsx_ppo_rollout) or turn norm_obs off");
   const unsigned long long step = ++e->step_ctr;
-  if (random_actions) {
+  if (random_actions && e->discrete_n > 0) {   // Discrete(n).sample()
+    hipLaunchKernelGGL(k_random_discrete_actions, dim3((e->n_env + 255) / 256), dim3(256), 0, ctx->stream, e->act, e->n_env, e->discrete_n,
+                       e->seed, e->rng_stream ^ 0x5A5A5A5Au, step);
+    HIPCHK(hipGetLastError());
+  } else if (random_actions) {
     const int tot = e->n_env * e->a;
     hipLaunchKernelGGL(k_random_actions, dim3((tot + 255) / 256), dim3(256), 0, ctx->stream, e->act, e->n_env, e->seed,
                        e->rng_stream ^ 0x5A5A5A5Au, step, e->a);
@@ -1369,7 +1437,7 @@ static bool rollout_runs_groupable(ilsx_vecenv* const* envs, ilsx_net* const* pi
         e->o != e0->o || e->a != e0->a || e->ctx->device != e0->ctx->device)
       return false;
     if (memcmp(&p->lay.cfg, &p0->lay.cfg, sizeof p->lay.cfg) || p->noise_policy != p0->noise_policy || p->out_linear != p0->out_linear ||
-        (p->lay.cfg.n_heads != 2 && !p->noise_policy))
+        (p->lay.cfg.n_heads != 2 && !p->noise_policy) || p->categorical)   // the grouped forward has no categorical head
       return false;
   }
   return true;
@@ -1533,6 +1601,7 @@ __global__ void k_onpolicy_record_post(const float* __restrict__ rew, const int*
 extern "C" int ilsx_ppo_rollout(ilsx_ppo* ppo, ilsx_vecenv* e, int T, int max_path_length, float* obs, float* act, float* rew,
                                 uint8_t* ends, float* last_values) {
   if (!ppo || !e || !obs || !act || !rew || !ends || T < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_ppo_rollout: bad argument");
+  if (e->discrete_n > 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_ppo_rollout: PPO's Gaussian policy on an env with a Discrete action space");
   ilsx_ctx* ctx = e->ctx;
   HIPCHK(hipSetDevice(ctx->device));
   const int n = e->n_env, w = e->o + e->a;
@@ -1612,6 +1681,8 @@ __global__ void k_eval_accum(const float* __restrict__ rew, const unsigned char*
 extern "C" int ilsx_eval_rollout(ilsx_vecenv* e, ilsx_net* pi, ilsx_ppo* ppo, int max_path_length, int deterministic, int reset_stats,
                                  double* stats_host) {
   if (!e || (!pi && !ppo) || max_path_length < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_eval_rollout: bad argument");
+  ILSX_TRY(env_policy_kind_check(e, pi, "ilsx_eval_rollout"));
+  if (!pi && e->discrete_n > 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_eval_rollout: PPO's Gaussian policy on an env with a Discrete action space");
   ilsx_ctx* ctx = e->ctx;
   HIPCHK(hipSetDevice(ctx->device));
   const int n = e->n_env;

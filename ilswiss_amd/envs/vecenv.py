@@ -24,6 +24,26 @@ class Box:  # minimal gym.spaces.Box stand-in (gym is not installed here)
         return np.random.uniform(self.low, self.high).astype(np.float32)
 
 
+class Discrete:  # minimal gym.spaces.Discrete stand-in: n actions {0, ..., n-1}; one action column (env_replay_buffer.py:40 get_dim == 1)
+    def __init__(self, n):
+        self.n = int(n)
+        self.shape, self.dtype = (), np.int64
+
+    def sample(self):
+        return int(np.random.randint(self.n))
+
+    def contains(self, x):
+        return float(x) == int(x) and 0 <= int(x) < self.n
+
+    def __repr__(self):
+        return f"Discrete({self.n})"
+
+
+# classic-control tasks of the engine in csrc/classic_env.h (include/ilsx.h ILSX_CLASSIC_*): env_name -> kind.  `cartpole` is gym 0.22's
+# CartPoleEnv, what rlkit/envs/envs_dict.py:2 maps the name to.
+CLASSIC = {"cartpole": 0}
+
+
 def model_struct(m):
     s = _lib.PlanarModel()
     s.task, s.n_body, s.n_geom, s.frame_skip, s.pgs_iters = m["task"], m["n_body"], m["n_geom"], m["frame_skip"], m["pgs_iters"]
@@ -149,13 +169,22 @@ class HipVectorEnv:
     def __init__(self, env_name, env_num, seed=0, ctx=None, model=None, norm_obs=False, obs_rms=None, update_obs_rms=True,
                  obs_shift=None, obs_scale=None):
         self.ctx = ctx or get_context()
-        self.model = model or (MODELS3D[env_name]() if env_name in MODELS3D else MODELS[env_name]())
+        self.env_name = env_name
         self.env_num = int(env_num)
         self.h = C.c_void_p()
-        if "n_link" in self.model:      # 3-D engine (Ant / Humanoid)
+        if env_name in CLASSIC:         # classic-control engine (CartPole)
+            if model is not None:
+                raise ValueError(f"{env_name}: a classic-control task has no model description")
+            if obs_shift is not None:
+                raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for classic-control tasks")
+            self.model = None
+            _lib.check(self.ctx.lib.ilsx_vecenv_create_classic(self.ctx.h, CLASSIC[env_name], self.env_num, C.c_uint64(seed), C.byref(self.h)))
+        else:
+            self.model = model or (MODELS3D[env_name]() if env_name in MODELS3D else MODELS[env_name]())
+        if self.model is not None and "n_link" in self.model:      # 3-D engine (Ant / Humanoid)
             ms = spatial_struct(self.model)
             _lib.check(self.ctx.lib.ilsx_vecenv_create_spatial(self.ctx.h, C.byref(ms), self.env_num, C.c_uint64(seed), C.byref(self.h)))
-        else:
+        elif self.model is not None:
             ms = model_struct(self.model)
             _lib.check(self.ctx.lib.ilsx_vecenv_create(self.ctx.h, C.byref(ms), self.env_num, C.c_uint64(seed), C.byref(self.h)))
         o, a, n, ne = C.c_int(), C.c_int(), C.c_int(), C.c_int()
@@ -164,7 +193,10 @@ class HipVectorEnv:
         _lib.check(self.ctx.lib.ilsx_vecenv_state_dims(self.h, C.byref(o), C.byref(a)))
         self.nq, self.nv = o.value, a.value
         ob = Box(-np.inf * np.ones(self.obs_dim), np.inf * np.ones(self.obs_dim))
-        ac = Box(-np.ones(self.act_dim), np.ones(self.act_dim))
+        dn = C.c_int()
+        _lib.check(self.ctx.lib.ilsx_vecenv_action_space(self.h, C.byref(dn)))
+        self.discrete_n = dn.value      # 0: Box actions
+        ac = Discrete(dn.value) if dn.value else Box(-np.ones(self.act_dim), np.ones(self.act_dim))
         self.observation_space, self.action_space = [ob] * self.env_num, [ac] * self.env_num  # vecenvs.py:118-140
         self.single_observation_space, self.single_action_space = ob, ac
         self.obs_shift, self.obs_scale = obs_shift, obs_scale
@@ -281,6 +313,11 @@ class HipVectorEnv:
         if self.h:
             self.ctx.lib.ilsx_vecenv_destroy(self.h)
             self.h = None
+
+
+def get_env(env_specs, ctx=None):
+    """rlkit/envs/__init__.py get_env: one env of env_specs["env_name"] (here a one-env HipVectorEnv)."""
+    return HipVectorEnv(env_specs["env_name"], 1, seed=env_specs.get("eval_env_seed", env_specs.get("seed", 0)), ctx=ctx)
 
 
 def get_envs(env_specs, env_wrapper=None, wrapper_kwargs=None, ctx=None, norm_obs=False, obs_rms=None, update_obs_rms=True,

@@ -182,6 +182,57 @@ class ReparamTanhMultivariateGaussianPolicy(Mlp):
         return out
 
 
+class DiscretePolicy(Mlp):
+    """policies.py:39-101: Mlp with a LogSoftmax over the last linear layer.  Actions are indices (Gumbel-max when stochastic, the first
+    maximal log-probability when deterministic), returned as an [n, 1] float column — the replay buffer's 1-wide action column
+    (env_replay_buffer.py:40)."""
+
+    def __init__(self, hidden_sizes, obs_dim, action_dim, init_w=1e-3, **kwargs):
+        super().__init__(hidden_sizes, input_size=obs_dim, output_size=action_dim, init_w=init_w, **kwargs)
+        self.obs_dim, self.action_dim = int(obs_dim), int(action_dim)
+        _lib.check(self.ctx.lib.ilsx_net_set_categorical(self.h, 1))
+
+    def copy(self, ctx=None):
+        c = super().copy(ctx)
+        _lib.check(c.ctx.lib.ilsx_net_set_categorical(c.h, 1))
+        return c
+
+    def get_actions_dev(self, obs_ptr, n, deterministic=False, logp=None):
+        act = self.ctx.empty((n, 1))
+        _lib.check(self.ctx.lib.ilsx_policy_act(self.h, obs_ptr, n, int(bool(deterministic)), None, act.ptr,
+                                                logp.ptr if logp is not None else None))
+        return act
+
+    def get_actions(self, obs_np, deterministic=False):   # policies.py:58-60
+        obs_np = np.ascontiguousarray(obs_np, np.float32)
+        keep, p = as_dev(self.ctx, obs_np)
+        return self.get_actions_dev(p, obs_np.shape[0], deterministic).numpy()
+
+    def get_action(self, obs_np, deterministic=False):    # policies.py:54-56
+        return self.get_actions(np.asarray(obs_np)[None], deterministic=deterministic)[0], {}
+
+    def forward(self, obs, deterministic=False, return_log_prob=False):   # policies.py:62-97: (idx [n, 1], log_prob [n, 1] or None)
+        obs = np.ascontiguousarray(obs, np.float32)
+        n = obs.shape[0]
+        keep, p = as_dev(self.ctx, obs)
+        logp = self.ctx.empty((n,)) if not deterministic else None
+        idx = self.get_actions_dev(p, n, deterministic, logp).numpy().astype(np.int64)
+        return idx, (logp.numpy().reshape(n, 1) if logp is not None else None)
+
+    __call__ = forward
+
+    def get_log_pis(self, obs):   # policies.py:99-100: log_softmax of the last linear layer, [n, action_dim] (ilsx_policy_log_pis)
+        obs = np.ascontiguousarray(obs, np.float32)
+        n = obs.shape[0]
+        keep, p = as_dev(self.ctx, obs)
+        out = self.ctx.empty((n, self.action_dim))
+        _lib.check(self.ctx.lib.ilsx_policy_log_pis(self.h, p, n, out.ptr))
+        return out.numpy()
+
+    def set_num_steps_total(self, t):
+        pass
+
+
 class MakeDeterministic:
     """policies.py:19-36."""
 

@@ -50,6 +50,7 @@ typedef struct ilsx_ppo ilsx_ppo;
 typedef struct ilsx_td3 ilsx_td3;
 typedef struct ilsx_sacv ilsx_sacv;
 typedef struct ilsx_bc ilsx_bc;
+typedef struct ilsx_dsac ilsx_dsac;
 
 enum { ILSX_ACT_RELU = 0, ILSX_ACT_TANH = 1 };
 
@@ -157,6 +158,14 @@ int ilsx_net_set_noise_policy(ilsx_net* pi, float policy_noise, float policy_noi
 /* Output activation of a noise policy: 0 = tanh (what td3_exp_script.py:75 passes), 1 = identity (Mlp's default, networks.py:31:
  * action = max_act * last_fc(h) + clipped noise).  Set it before ilsx_td3_create adopts the network. */
 int ilsx_net_set_output_linear(ilsx_net* pi, int linear);
+/* Marks a single-head Mlp with n = out_dim outputs (2 <= n <= 64) as DiscretePolicy (policies.py:39-101): LogSoftmax over the last linear
+ * layer.  ilsx_policy_act then writes the action INDEX as a float to act[n_rows][1] — stochastic: Gumbel-max argmax(z_j - log(-log u_j)), u
+ * from Philox on the 'ACT' stream; deterministic: the first maximal log-probability — and logp (nullable) = log pi(a|s).  eps must be NULL.
+ * on = 0 clears the mark.  Set it before a trainer adopts the network; continuous trainers refuse a categorical policy. */
+int ilsx_net_set_categorical(ilsx_net* pi, int on);
+/* DiscretePolicy.get_log_pis (policies.py:99-100) of a categorical policy: obs[n_rows,o] -> log_pis[n_rows,n] = log_softmax of the last
+ * linear layer (max-shifted; device pointers). */
+int ilsx_policy_log_pis(ilsx_net* pi, const float* obs, int n_rows, float* log_pis);
 
 /* ---------------------------------------------------------------- replay buffer
  * Replaces rlkit/data_management/simple_replay_buffer.py:17-442 + env_replay_buffer.py:7-49.
@@ -403,6 +412,30 @@ int ilsx_td3_train_from_replay(ilsx_td3* td3, ilsx_replay* rb, int n_steps, int 
 int ilsx_td3_get_params(ilsx_td3* td3, int which, float* dst_host, size_t n);
 int ilsx_td3_set_params(ilsx_td3* td3, int which, const float* src_host, size_t n);
 
+/* ---------------------------------------------------------------- discrete SAC
+ * Replaces rlkit/torch/algorithms/discrete_sac/discrete_sac.py:23-58 (ctor), :62-181 (train_step), :196-198 (soft updates).  pi: a
+ * categorical policy (ilsx_net_set_categorical) of n outputs; qf1 / qf2: identical FlattenMlp's obs -> n.  Batches carry the action INDEX
+ * as a float in a 1-wide action column.  Fixed alpha (the reference has no automatic tuning); Adam betas (beta_1, 0.999) for all three
+ * optimisers.  Statistics are those of the first batch of a call (discrete_sac.py:149-151). */
+typedef struct {
+  float discount, reward_scale, alpha, soft_target_tau, policy_lr, qf_lr, beta_1;
+  int32_t max_batch;
+} ilsx_dsac_cfg;
+typedef struct {
+  float qf1_loss, qf2_loss, policy_loss;
+  float q1_pred[4], q2_pred[4];   /* {Mean, Std, Max, Min} of Q_i(s)[a] */
+} ilsx_dsac_stats;
+int ilsx_dsac_create(ilsx_ctx* ctx, const ilsx_dsac_cfg* cfg, ilsx_net* pi, ilsx_net* qf1, ilsx_net* qf2, ilsx_dsac** out);
+int ilsx_dsac_destroy(ilsx_dsac* d);
+/* device batch rows: obs[B,o], act[B,1] (indices), rew[B], done[B], nobs[B,o]; an index outside [0, n) or not integral = ILSX_ERR_ARG
+ * (the check reads the action column back to the host).  stats nullable (host). */
+int ilsx_dsac_train_step(ilsx_dsac* d, const float* obs, const float* act, const float* rew, const float* done, const float* nobs, int B,
+                         ilsx_dsac_stats* stats);
+int ilsx_dsac_train_from_replay(ilsx_dsac* d, ilsx_replay* rb, int n_steps, int B, ilsx_dsac_stats* stats);
+/* which: 0 qf1, 1 qf2, 2 policy, 3 target_qf1, 4 target_qf2; HOST flat arrays */
+int ilsx_dsac_get_params(ilsx_dsac* d, int which, float* dst_host, size_t n);
+int ilsx_dsac_set_params(ilsx_dsac* d, int which, const float* src_host, size_t n);
+
 /* ---------------------------------------------------------------- SAC with a state-value function
  * Replaces rlkit/torch/algorithms/sac/sac.py:23-68 (ctor), :70-179 (train_step), :242-243 (soft update of V).
  * cfg fields == the YAML `sac_params` keys (exp_specs/sac/sac_hopper.yaml:36-47 with run_scripts/sac_exp_script.py). */
@@ -437,6 +470,8 @@ int ilsx_sacv_set_params(ilsx_sacv* sac, int which, const float* src_host, size_
 typedef struct { int64_t t; uint64_t rng_step; int64_t n_train_steps; } ilsx_opt_meta;
 int ilsx_td3_get_opt(ilsx_td3* td3, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);    /* 0 qf1, 1 qf2, 2 policy */
 int ilsx_td3_set_opt(ilsx_td3* td3, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
+int ilsx_dsac_get_opt(ilsx_dsac* d, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);     /* 0 qf1, 1 qf2, 2 policy */
+int ilsx_dsac_set_opt(ilsx_dsac* d, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
 int ilsx_sacv_get_opt(ilsx_sacv* sac, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);  /* 0 qf1, 1 qf2, 2 vf, 3 policy */
 int ilsx_sacv_set_opt(ilsx_sacv* sac, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
 int ilsx_bc_get_opt(ilsx_bc* bc, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);
@@ -570,6 +605,16 @@ typedef struct {
   double init_qpos[ILSX_ENV3_MAX_LINK + 6];
 } ilsx_spatial_model;
 int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
+/* Classic control — gym 0.22's CartPoleEnv (gym/envs/classic_control/cartpole.py; rlkit/envs/envs_dict.py:2): closed-form Euler
+ * dynamics, float64 in gym's order and constants, one lane per env.  State rows: qpos = (x, theta), qvel = (x_dot, theta_dot) (nq = nv = 2);
+ * observation = float32 (x, x_dot, theta, theta_dot); reward 1 on every step, the terminal one included; done = |x| > 2.4 or |theta| > 12 deg;
+ * reset: every component U[-0.05, 0.05) from the env's Philox stream.  Actions are a Discrete(2) index held as a float in a 1-wide action
+ * column (act_dim 1; env_replay_buffer.py:40); random actions are uniform indices.  Reset / step / rollout / evaluation entry points are the
+ * ordinary ones; ilsx_vecenv_set_obs_affine is not available. */
+enum { ILSX_CLASSIC_CARTPOLE = 0 };
+int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out);
+/* discrete_n = n of a Discrete(n) action space, 0 for Box actions */
+int ilsx_vecenv_action_space(const ilsx_vecenv* env, int* discrete_n);
 /* Path mode of the fused rollout (ilsx_rollout_step with a replay ring): 0 (default) = every transition enters the ring when it
  * happens; 1 = the reference's order (rlkit/core/base_algorithm.py:509-519, simple_replay_buffer.py:78-132): an episode's samples are
  * staged in HBM and enter the ring contiguously when the episode ends (ended envs in ascending order), the trajectory is registered in

@@ -1470,11 +1470,71 @@ def gen_mbpo():
     save("g27_mbpo", **out)
 
 
+def dsac_init(seed, o, Hw, na):
+    """G28's initial parameters (regenerated by the tests from the seed: the fixture stays under the size limit)."""
+    rng = np.random.default_rng(seed)
+    pi0 = omlp.init_mlp(rng, o, [Hw, Hw], na, init_w=1e-3)
+    pi0[-(Hw * na + na):] *= 100.0          # head weights up so that the softmax is not uniform
+    return rng, pi0, omlp.init_mlp(rng, o, [Hw, Hw], na), omlp.init_mlp(rng, o, [Hw, Hw], na)
+
+
+def gen_discrete_sac():
+    """G28: DiscreteSoftActorCritic.train_step (discrete_sac/discrete_sac.py:60-181) with the reference's own DiscretePolicy and FlattenMlp,
+    three chained steps per case (H, B, n) in {(128, 128, 2), (256, 37, 5)}: per-step losses and Q predictions, the first step's gradients,
+    the final parameters of all five networks, DiscretePolicy.get_log_pis and the deterministic actions of the initial policy.  Initial
+    parameters come from dsac_init(seed); parameter / gradient vectors of the H = 256 case are kept at `idx` only (a fixed random subset)."""
+    from rlkit.torch.algorithms.discrete_sac.discrete_sac import DiscreteSoftActorCritic
+    from rlkit.torch.common.networks import FlattenMlp
+    from rlkit.torch.common.policies import DiscretePolicy
+    o, steps = 4, 3
+    kw = dict(reward_scale=1.0, discount=0.95, alpha=0.05, policy_lr=1e-4, qf_lr=1e-3, vf_lr=1e-3, soft_target_tau=0.005, beta_1=0.9)
+    rec = dict(dims=np.array([o, steps]), kw_vals=np.array([kw[k] for k in sorted(kw)], np.float64), kw_keys=np.array(sorted(kw)))
+    for c, (Hw, B, na, seed) in enumerate(((128, 128, 2, 2828), (256, 37, 5, 2829))):
+        Hh = [Hw, Hw]
+        rng, pi0, q10, q20 = dsac_init(seed, o, Hw, na)
+        pol = DiscretePolicy(hidden_sizes=Hh, obs_dim=o, action_dim=na)
+        qf1 = FlattenMlp(hidden_sizes=Hh, input_size=o, output_size=na)
+        qf2 = FlattenMlp(hidden_sizes=Hh, input_size=o, output_size=na)
+        set_flat(pol, pi0), set_flat(qf1, q10), set_flat(qf2, q20)
+        tr = DiscreteSoftActorCritic(policy=pol, qf1=qf1, qf2=qf2, **kw)
+        grads = {}
+        _hook_grads(grads, tr.qf1_optimizer, "q1", qf1), _hook_grads(grads, tr.qf2_optimizer, "q2", qf2)
+        _hook_grads(grads, tr.policy_optimizer, "pi", pol)
+        pre = f"c{c}_"
+        idx = np.arange(pi0.size) if Hw == 128 else np.sort(rng.choice(pi0.size, 4096, replace=False))
+        rec.update({pre + "shape": np.array([Hw, B, na, seed]), pre + "idx": idx.astype(np.int64)})
+        lp_obs = rng.normal(0, 1, (64, o)).astype(np.float32)
+        with torch.no_grad():
+            rec[pre + "lp_obs"] = lp_obs
+            rec[pre + "log_pis"] = n(pol.get_log_pis(t(lp_obs)))
+            rec[pre + "det_act"] = n(pol(t(lp_obs), deterministic=True)[0]).astype(np.int64)
+        for s in range(steps):
+            batch = dict(observations=rng.normal(0, 1, (B, o)).astype(np.float32),
+                         actions=rng.integers(0, na, (B, 1)).astype(np.float32),
+                         rewards=rng.normal(0, 1, (B, 1)).astype(np.float32),
+                         terminals=(rng.random((B, 1)) < 0.1).astype(np.float32),
+                         next_observations=rng.normal(0, 1, (B, o)).astype(np.float32))
+            tr.eval_statistics = None
+            tr.train_step({k: t(v) for k, v in batch.items()})
+            st = tr.eval_statistics
+            rec.update({f"{pre}s{s}_{k}": v for k, v in batch.items()})
+            rec.update({f"{pre}s{s}_qf1_loss": np.float32(st["QF1 Loss"]), f"{pre}s{s}_qf2_loss": np.float32(st["QF2 Loss"]),
+                        f"{pre}s{s}_policy_loss": np.float32(st["Policy Loss"]),
+                        f"{pre}s{s}_q1_pred": np.array([st["Q1 Predictions " + k] for k in ("Mean", "Std", "Max", "Min")], np.float32),
+                        f"{pre}s{s}_q2_pred": np.array([st["Q2 Predictions " + k] for k in ("Mean", "Std", "Max", "Min")], np.float32)})
+            if s == 0:
+                rec.update({pre + "grad_q1": grads["q1"][idx], pre + "grad_q2": grads["q2"][idx], pre + "grad_pi": grads["pi"][idx]})
+        rec.update({pre + "pi": get_flat(pol)[idx], pre + "q1": get_flat(qf1)[idx], pre + "q2": get_flat(qf2)[idx],
+                    pre + "tq1": get_flat(tr.target_qf1)[idx], pre + "tq2": get_flat(tr.target_qf2)[idx]})
+    save("g28_discrete_sac", **rec)
+
+
 # generation order: a group that reads another group's file comes after it (replay_trajs loads g10_replay.npz, written by replay)
 GROUPS = dict(mlp=gen_mlp, mlp_unequal=gen_mlp_unequal, head=gen_head, sac_alpha=gen_sac_alpha, sac_v=gen_sac_v, td3=gen_td3, ppo=gen_ppo,
               disc=gen_disc, disc_bn=gen_disc_bn, disc_blocks=gen_disc_blocks, disc_branches=gen_disc_branches, replay=gen_replay,
               replay_trajs=gen_replay_trajs, her=gen_her, absorbing=gen_absorbing, bc=gen_bc, rms=gen_rms_actionmap, terminals=gen_terminals,
-              eval_stats=gen_eval_stats, variants=gen_variants, logger_csv=gen_logger_csv, logdir=gen_logdir, mbpo=gen_mbpo)
+              eval_stats=gen_eval_stats, variants=gen_variants, logger_csv=gen_logger_csv, logdir=gen_logdir, mbpo=gen_mbpo,
+              discrete_sac=gen_discrete_sac)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GROUPS)
