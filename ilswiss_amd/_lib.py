@@ -119,6 +119,11 @@ class BcCfg(C.Structure):  # ilsx_bc_cfg
     _fields_ = [("mode", C.c_int32), ("lr", C.c_float), ("momentum", C.c_float), ("max_batch", C.c_int32)]
 
 
+class GcslCfg(C.Structure):  # ilsx_gcsl_cfg
+    _fields_ = [("mode", C.c_int32), ("policy_lr", C.c_float), ("max_batch", C.c_int32), ("d_obs", C.c_int32), ("d_goal", C.c_int32),
+                ("horizon", C.c_int32)]
+
+
 class PpoCfg(C.Structure):  # ilsx_ppo_cfg
     _fields_ = [("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32),
                 ("reward_scale", C.c_float), ("discount", C.c_float), ("clip_eps", C.c_float),
@@ -331,6 +336,21 @@ PROTOTYPES = {
     "ilsx_dsac_set_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
     "ilsx_mbpo_model_step": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                        C.POINTER(C.c_int)]),
+    "ilsx_her_horizon_gather": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "ilsx_bncat_create": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "ilsx_bncat_destroy": (C.c_int, [vp]),
+    "ilsx_bncat_num_params": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "ilsx_bncat_get": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_bncat_set": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_bncat_get_meta": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
+    "ilsx_bncat_set_meta": (C.c_int, [vp, C.c_int64, C.c_uint64]),
+    "ilsx_bncat_input": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
+    "ilsx_bncat_train_step": (C.c_int, [vp, C.c_int, C.c_float, vp]),
+    "ilsx_bncat_act": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+    "ilsx_gcsl_create": (C.c_int, [vp, C.POINTER(GcslCfg), vp, vp, C.c_int, C.POINTER(vp)]),
+    "ilsx_gcsl_destroy": (C.c_int, [vp]),
+    "ilsx_gcsl_train_from_replay": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
+    "ilsx_gcsl_train_step": (C.c_int, [vp, vp, vp, C.c_int, vp]),
 }
 
 _lib = None

@@ -752,6 +752,45 @@ int ilsx_mbpo_model_step(ilsx_bnn* bnn, ilsx_net* pi, ilsx_replay* model_rb, int
                          const int32_t* elites_host, int n_elites, int deterministic, const float* eps, const int32_t* model_idx,
                          float* act_out, int32_t* model_idx_out, float* obs_next, int* n_survivors);
 
+/* ---------------------------------------------------------------- GCSL (rlkit/torch/algorithms/gcsl/)
+ * HindsightHorizonReplayBuffer.random_batch (relabel_horizon_replay_buffer.py:163-270, her_ratio 1) as one gather from the ring: for the
+ * host-drawn device int64 idx / idx_relabel [B], X[B, d_obs + d_goal + T] = observation | next achieved goal of the relabel record |
+ * horizon row (j >= idx_relabel - idx on raw ring indices: a wrapped trajectory gives an all-ones row, as in the reference).  mode 0:
+ * act[B, act_dim] floats; mode 1: label[B] = (int32) action[0] (truncated like .long()).  Rows with an index outside the ring: zeros, label -1. */
+int ilsx_her_horizon_gather(ilsx_replay* rb, const int64_t* idx, const int64_t* idx_relabel, int B, int d_obs, int d_goal, int T, int mode,
+                            float* X, float* act, int32_t* label);
+/* The BatchNorm categorical policy (CatagorialConditionPolicy(batch_norm=True): networks.py:118-145, policies.py:759-840): n_blocks (1..3)
+ * Linear -> BatchNorm1d(eps 1e-5, momentum 0.1) -> ReLU blocks of width `hidden`, then last_fc to n_classes (<= 64) logits.  Flat
+ * parameters in torch's parameters() order (per block W | b | gamma | beta, then last_fc W | b); running statistics [n_blocks][hidden]. */
+typedef struct ilsx_bncat ilsx_bncat;
+enum { ILSX_BNCAT_PARAMS = 0, ILSX_BNCAT_RUNNING_MEAN = 1, ILSX_BNCAT_RUNNING_VAR = 2, ILSX_BNCAT_ADAM_M = 3, ILSX_BNCAT_ADAM_V = 4 };
+int ilsx_bncat_create(ilsx_ctx* ctx, int in_dim, int hidden, int n_blocks, int n_classes, int max_rows, ilsx_bncat** out);
+int ilsx_bncat_destroy(ilsx_bncat* b);
+int ilsx_bncat_num_params(const ilsx_bncat* b, int* n);
+int ilsx_bncat_get(ilsx_bncat* b, int which, float* dst_host, size_t n);          /* which: ILSX_BNCAT_*; n must match */
+int ilsx_bncat_set(ilsx_bncat* b, int which, const float* src_host, size_t n);
+int ilsx_bncat_get_meta(const ilsx_bncat* b, int64_t* t, uint64_t* draws);      /* Adam step count, stochastic act calls so far */
+int ilsx_bncat_set_meta(ilsx_bncat* b, int64_t t, uint64_t draws);
+int ilsx_bncat_input(ilsx_bncat* b, float** X, int32_t** label);               /* the device input buffer the train step reads */
+/* gcsl.py:87-103 in CLASS mode on the input buffer: train-mode forward, CrossEntropyLoss, one running-statistics update, Adam(lr) over
+ * every parameter.  stats2_host (nullable, syncs): {CE Loss, Accuracy}. */
+int ilsx_bncat_train_step(ilsx_bncat* b, int B, float lr, float* stats2_host);
+/* eval mode: act[rows] (device, float index) = first argmax of the softmax (deterministic) or a Philox Gumbel-max draw from it;
+ * probs (device [rows][n_classes], nullable). */
+int ilsx_bncat_act(ilsx_bncat* b, const float* x, int rows, int deterministic, float* act, float* probs);
+/* GCSL.train_step (gcsl.py:58-103): CLASS mode on an ilsx_bncat; MSE mode on an ilsx_bc in ILSX_BC_MSE mode whose noise is held at
+ * zero (its action is then tanh(mean): the reference's max_act * tanh(last_fc) for max_act 1; the log-std head gets no gradient). */
+typedef struct ilsx_gcsl ilsx_gcsl;
+enum { ILSX_GCSL_MSE = 1, ILSX_GCSL_CLASS = 2 };
+typedef struct { int32_t mode; float policy_lr; int32_t max_batch, d_obs, d_goal, horizon; } ilsx_gcsl_cfg;
+int ilsx_gcsl_create(ilsx_ctx* ctx, const ilsx_gcsl_cfg* cfg, ilsx_bncat* cat, ilsx_bc* bc, int act_dim, ilsx_gcsl** out);
+int ilsx_gcsl_destroy(ilsx_gcsl* g);
+/* gather (ilsx_her_horizon_gather) straight into the trainer's input, then one step; stats2_host (nullable, syncs): CLASS {CE Loss,
+ * Accuracy}, MSE {MSE, 0} */
+int ilsx_gcsl_train_from_replay(ilsx_gcsl* g, ilsx_replay* rb, const int64_t* idx, const int64_t* idx_relabel, int B, float* stats2_host);
+/* one step on device X[B, d_obs + d_goal + horizon] and targets (CLASS: int32 [B]; MSE: float [B, act_dim]) */
+int ilsx_gcsl_train_step(ilsx_gcsl* g, const float* X, const void* target, int B, float* stats2_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1529,12 +1529,168 @@ def gen_discrete_sac():
     save("g28_discrete_sac", **rec)
 
 
+def gen_gcsl():
+    """G29: GCSL (gcsl/gcsl.py, relabel_horizon_replay_buffer.py) with the reference's own trainer, buffer, policies and DiscretEnv.
+    buf_*: HindsightHorizonReplayBuffer.random_batch on point-reach-shaped paths in a 40-slot ring (the last path wraps it): the indices it
+    drew (captured at _get_batch_using_indices), its horizons, goals and actions.  c{0,1}_*: CLASS mode with CatagorialConditionPolicy(
+    batch_norm=True) at (H 300, B 128, n 25, input 56) and (H 64, B 37): per-step CE loss and accuracy, final parameters (the large case at a
+    fixed random subset `idx`, plus every gamma / beta), running statistics and eval-mode probabilities on a probe batch.  m0_*: MSE mode with
+    MlpGaussianAndEpsilonConditionPolicy(batch_norm=True, output_activation=tanh) at (H 256, B 128).  base_actions: DiscretEnv(granularity 5)
+    over point-reach's 2-D action box.  Initial parameters and batches come from tests/gcsl_restatement.py's seeded draws."""
+    import importlib.util
+    import types
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gcsl_restatement as GR
+    if "rlkit.envs" not in sys.modules:        # as gen_her: the buffer needs only goal_env_utils' two default callables
+        pkg = types.ModuleType("rlkit.envs")
+        pkg.__path__ = []
+        sys.modules["rlkit.envs"] = pkg
+        geu = types.ModuleType("rlkit.envs.goal_env_utils")
+        geu.compute_reward = geu.compute_distance = None
+        sys.modules["rlkit.envs.goal_env_utils"] = geu
+    from rlkit.data_management.relabel_horizon_replay_buffer import HindsightHorizonReplayBuffer
+    from rlkit.torch.algorithms.gcsl.gcsl import GCSL
+    from rlkit.torch.common.policies import CatagorialConditionPolicy, MlpGaussianAndEpsilonConditionPolicy
+    spaces = sys.modules["gym.spaces"]
+    Box = spaces.Box
+    o, gd, a, T, cap = 4, 2, 2, 50, 40
+    rec = dict(dims=np.array([o, gd, a, T, cap]))
+    # ---------------------------------------------------------------- DiscretEnv.base_actions (rlkit/envs/wrappers.py:411-446)
+    if "rlkit.envs.wrappers" not in sys.modules:
+        spec = importlib.util.spec_from_file_location("rlkit.envs.wrappers", os.path.join(H.REF, "rlkit", "envs", "wrappers.py"))
+        wr = importlib.util.module_from_spec(spec)
+        sys.modules["rlkit.envs.wrappers"] = wr
+        spec.loader.exec_module(wr)
+    wr = sys.modules["rlkit.envs.wrappers"]
+    had = "__init__" in spaces.Discrete.__dict__
+    if not had:                                # the gym stub's Discrete takes no n
+        spaces.Discrete.__init__ = lambda self, n: setattr(self, "n", n)
+    try:
+        inner = type("PR", (), dict(action_space=Box(-np.ones(a), np.ones(a)), observation_space=None))()
+        denv = wr.DiscretEnv(inner, granularity=5)
+        rec["base_actions"] = np.asarray(denv.base_actions, np.float64)
+        assert denv.action_space.n == 25
+    finally:
+        if not had:
+            del spaces.Discrete.__init__
+    # ---------------------------------------------------------------- buffer
+    class DSpace(spaces.Dict):
+        def __init__(self):
+            self.spaces = dict(observation=Box(-np.ones(o), np.ones(o)), desired_goal=Box(-np.ones(gd), np.ones(gd)),
+                               achieved_goal=Box(-np.ones(gd), np.ones(gd)))
+
+    def compute_reward(ag, dg, info=None):
+        return -(np.linalg.norm(ag - dg, axis=-1) > 0.1).astype(np.float32)
+    env = type("E", (), dict(observation_space=DSpace(), action_space=Box(-np.ones(a), np.ones(a)), compute_reward=staticmethod(compute_reward)))()
+    rng = np.random.default_rng(2929)
+    paths = []
+    for L in (9, 12, 7, 10):               # 38 samples, then 10 more: the last path wraps the 40-slot ring and overwrites the first
+        obs = [dict(observation=rng.normal(0, 1, o), desired_goal=rng.uniform(-1, 1, gd), achieved_goal=rng.uniform(-1, 1, gd)) for _ in range(L + 1)]
+        for ob in obs[1:]:
+            ob["desired_goal"] = obs[0]["desired_goal"]
+        paths.append(dict(obs=obs, act=rng.integers(0, 25, (L, 1)).astype(np.float64), rew=-np.ones(L), term=[False] * L))
+    obs = [dict(observation=rng.normal(0, 1, o), desired_goal=rng.uniform(-1, 1, gd), achieved_goal=rng.uniform(-1, 1, gd)) for _ in range(11)]
+    paths.append(dict(obs=obs, act=rng.integers(0, 25, (10, 1)).astype(np.float64), rew=-np.ones(10), term=[False] * 10))
+    ref = HindsightHorizonReplayBuffer(max_path_length=T, max_replay_buffer_size=cap, env=env, random_seed=29, relabel_type="future")
+    assert ref.her_ratio == 1.0
+    for pth in paths:
+        for i in range(len(pth["act"])):
+            ref.add_sample(pth["obs"][i], pth["act"][i], pth["rew"][i], pth["term"][i], pth["obs"][i + 1])
+        ref.terminate_episode()
+    seen = []
+    orig = ref._get_batch_using_indices
+    ref._get_batch_using_indices = lambda idx, keys=None: (seen.append(np.array(idx, np.int64)), orig(idx, keys=keys))[1]
+    np.random.seed(2930)                   # `future` draws from the GLOBAL numpy stream
+    bt = ref.random_batch(64)
+    idx, idx_rel = seen[0], seen[1]
+    assert ((idx_rel - idx) < 0).any() and ((idx_rel - idx) >= 0).any()   # wrapped rows (all-ones horizons) and ordinary ones
+    rec.update(buf_idx=idx, buf_idx_relabel=idx_rel, buf_horizons=np.asarray(bt["horizons"]), buf_obs=np.asarray(bt["observations"]),
+               buf_desired_goals=np.asarray(bt["desired_goals"]), buf_actions=np.asarray(bt["actions"]),
+               buf_rewards=np.asarray(bt["rewards"]), buf_endpoints=np.array(sorted(ref._traj_endpoints.items())))
+    for pi_, pth in enumerate(paths):
+        rec[f"p{pi_}_obs"] = np.array([x["observation"] for x in pth["obs"]])
+        rec[f"p{pi_}_dg"] = np.array([x["desired_goal"] for x in pth["obs"]])
+        rec[f"p{pi_}_ag"] = np.array([x["achieved_goal"] for x in pth["obs"]])
+        rec[f"p{pi_}_act"] = pth["act"]
+    # ---------------------------------------------------------------- CLASS
+    D, ncls, steps, lr = o + gd + T, 25, 20, 3e-4
+
+    def load(mod, flat, names):
+        named = dict(mod.named_parameters())
+        off = 0
+        with torch.no_grad():
+            for nm in names:
+                p = named[nm]
+                p.copy_(t(flat[off:off + p.numel()]).view_as(p))
+                off += p.numel()
+        assert off == flat.size
+
+    def read(mod, names):
+        named = dict(mod.named_parameters())
+        return np.concatenate([n(named[nm]).ravel() for nm in names]).astype(np.float32)
+    for c, (Hw, B, seed) in enumerate(((300, 128, 2931), (64, 37, 2932))):
+        pol = CatagorialConditionPolicy(hidden_sizes=[Hw, Hw], obs_dim=o, condition_dim=gd + T, action_dim=ncls, batch_norm=True)
+        names = [nm for nm, _ in pol.named_parameters()]
+        assert names == ["fc0.weight", "fc0.bias", "batch_norm0.weight", "batch_norm0.bias", "fc1.weight", "fc1.bias", "batch_norm1.weight",
+                         "batch_norm1.bias", "last_fc.weight", "last_fc.bias"], names
+        p0 = GR.cat_init(seed, D, Hw, 2, ncls)
+        load(pol, p0, names)
+        tr = GCSL(policy=pol, mode="CLASS", use_horizons=True, reward_scale=1.0, discount=0.99, soft_target_tau=0.005, policy_lr=lr)
+        rst = GR.CatRestatement(p0, D, Hw, 2, ncls, lr=lr)
+        ce, acc = [], []
+        for X, y in GR.cat_batches(seed + 100, B, steps, o, gd, T, ncls):
+            tr.eval_statistics = None
+            tr.train_step(dict(observations=t(X[:, :o]), desired_goals=t(X[:, o:o + gd]), horizons=t(X[:, o + gd:]),
+                               actions=t(y.astype(np.float32).reshape(B, 1))))
+            ce.append(float(tr.eval_statistics["CE Loss"])), acc.append(float(tr.eval_statistics["Accuracy"]))
+            l2, a2 = rst.train_step(X, y)
+            assert abs(l2 - ce[-1]) <= 1e-5 * abs(ce[-1]) and a2 == acc[-1], (c, len(ce), l2, ce[-1], a2, acc[-1])
+        final = read(pol, names)
+        assert np.abs(final - rst.flat())[~rst.dead_bias_mask()].max() < 5e-5
+        pr = GR.probe(seed + 200, 64, o, gd, T)
+        pol.eval()
+        with torch.no_grad():
+            _, logits, _ = pol(t(pr), deterministic=True)
+            probs = n(torch.softmax(logits, -1))
+        pol.train()
+        assert np.abs(probs - rst.probs(pr)).max() < 1e-5
+        bns = [pol.batch_norm0, pol.batch_norm1]
+        pre = f"c{c}_"
+        lidx = np.arange(final.size) if Hw == 64 else np.sort(np.random.default_rng(seed).choice(final.size, 8192, replace=False))
+        rec.update({pre + "shape": np.array([Hw, B, ncls, seed, steps]), pre + "idx": lidx.astype(np.int64), pre + "final": final[lidx],
+                    pre + "ce": np.array(ce, np.float32), pre + "acc": np.array(acc, np.float32),
+                    pre + "gamma": np.stack([n(b.weight) for b in bns]), pre + "beta": np.stack([n(b.bias) for b in bns]),
+                    pre + "running_mean": np.stack([n(b.running_mean) for b in bns]), pre + "running_var": np.stack([n(b.running_var) for b in bns]),
+                    pre + "probe_probs": probs.astype(np.float32)})
+    # ---------------------------------------------------------------- MSE
+    Hw, B, seed, msteps = 256, 128, 2933, 10
+    space = type("S", (), {"shape": (a,), "sample": lambda self: np.zeros(a)})()
+    pol = MlpGaussianAndEpsilonConditionPolicy(hidden_sizes=[Hw, Hw], obs_dim=o, condition_dim=gd + T, action_dim=a, action_space=space,
+                                               output_activation=torch.tanh, batch_norm=True)
+    names = ["fc0.weight", "fc0.bias", "fc1.weight", "fc1.bias", "last_fc.weight", "last_fc.bias"]
+    p0 = GR.mse_init(seed, D, Hw, 2, a)
+    load(pol, p0, names)
+    tr = GCSL(policy=pol, mode="MSE", use_horizons=True, reward_scale=1.0, discount=0.99, soft_target_tau=0.005, policy_lr=lr)
+    rst = GR.MseRestatement(p0, D, Hw, 2, a, lr=lr)
+    mse = []
+    for X, act in GR.mse_batches(seed + 100, B, msteps, o, gd, T, a):
+        tr.eval_statistics = None
+        tr.train_step(dict(observations=t(X[:, :o]), desired_goals=t(X[:, o:o + gd]), horizons=t(X[:, o + gd:]), actions=t(act)))
+        mse.append(float(tr.eval_statistics["MSE"]))
+        assert abs(rst.train_step(X, act) - mse[-1]) <= 1e-5 * abs(mse[-1])
+    final = read(pol, names)
+    assert np.abs(final - rst.flat()).max() < 5e-5
+    lidx = np.sort(np.random.default_rng(seed).choice(final.size, 8192, replace=False))
+    rec.update(m0_shape=np.array([Hw, B, a, seed, msteps]), m0_idx=lidx.astype(np.int64), m0_final=final[lidx], m0_mse=np.array(mse, np.float32))
+    save("g29_gcsl", **rec)
+
+
 # generation order: a group that reads another group's file comes after it (replay_trajs loads g10_replay.npz, written by replay)
 GROUPS = dict(mlp=gen_mlp, mlp_unequal=gen_mlp_unequal, head=gen_head, sac_alpha=gen_sac_alpha, sac_v=gen_sac_v, td3=gen_td3, ppo=gen_ppo,
               disc=gen_disc, disc_bn=gen_disc_bn, disc_blocks=gen_disc_blocks, disc_branches=gen_disc_branches, replay=gen_replay,
               replay_trajs=gen_replay_trajs, her=gen_her, absorbing=gen_absorbing, bc=gen_bc, rms=gen_rms_actionmap, terminals=gen_terminals,
               eval_stats=gen_eval_stats, variants=gen_variants, logger_csv=gen_logger_csv, logdir=gen_logdir, mbpo=gen_mbpo,
-              discrete_sac=gen_discrete_sac)
+              discrete_sac=gen_discrete_sac, gcsl=gen_gcsl)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GROUPS)
