@@ -860,7 +860,10 @@ static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
   if (A.n_ids <= 0) return ILSX_OK;
   if (e->engine == 2) {
     ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
-    ILSX_LAUNCH(ps, k_cartpole_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
+    if (e->classic == ILSX_CLASSIC_PENDULUM)
+      ILSX_LAUNCH(ps, k_pendulum_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
+    else
+      ILSX_LAUNCH(ps, k_cartpole_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
     HIPCHK(hipGetLastError());
     return ILSX_OK;
   }
@@ -889,6 +892,12 @@ static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
 static int launch_env_reset(ilsx_vecenv* e, const int* ids_dev, int n_ids, float* obs) {
   if (n_ids <= 0) return ILSX_OK;
   const unsigned long long step = ++e->step_ctr;
+  if (e->engine == 2 && e->classic == ILSX_CLASSIC_PENDULUM) {
+    hipLaunchKernelGGL(k_pendulum_reset, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, ids_dev, n_ids, obs,
+                       e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
+    HIPCHK(hipGetLastError());
+    return ILSX_OK;
+  }
   if (e->engine == 2) {
     hipLaunchKernelGGL(k_cartpole_reset, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, obs,
                        e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
@@ -1048,15 +1057,17 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
   *out = e;
   return ILSX_OK;
 }
-// Classic control (classic_env.h): CartPole, one lane per env, the same handle and protocol entry points as the other engines.
+// Classic control (classic_env.h): CartPole and Pendulum, one lane per env, the same handle and protocol entry points as the other engines.
 extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out) {
   if (!ctx || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_classic: bad argument");
-  if (kind != ILSX_CLASSIC_CARTPOLE) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_classic: unknown kind %d", kind);
+  if (kind != ILSX_CLASSIC_CARTPOLE && kind != ILSX_CLASSIC_PENDULUM)
+    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_classic: unknown kind %d", kind);
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_vecenv* e = new ilsx_vecenv();
   e->ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++; e->engine = 2;
-  e->classic = kind; e->discrete_n = 2;
-  e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1;
+  e->classic = kind;
+  if (kind == ILSX_CLASSIC_PENDULUM) { e->discrete_n = 0; e->n = 1; e->nq = 1; e->nv = 1; e->o = 3; e->a = 1; }   // Box(-1, 1) actions
+  else { e->discrete_n = 2; e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1; }
   const size_t N = (size_t)n_env;
   int rc = ctx_alloc(ctx, N * e->nq * 8, (void**)&e->qpos);
   if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->nv * 8, (void**)&e->qvel);

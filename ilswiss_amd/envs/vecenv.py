@@ -40,8 +40,9 @@ class Discrete:  # minimal gym.spaces.Discrete stand-in: n actions {0, ..., n-1}
 
 
 # classic-control tasks of the engine in csrc/classic_env.h (include/ilsx.h ILSX_CLASSIC_*): env_name -> kind.  `cartpole` is gym 0.22's
-# CartPoleEnv, what rlkit/envs/envs_dict.py:2 maps the name to.
-CLASSIC = {"cartpole": 0}
+# CartPoleEnv, what rlkit/envs/envs_dict.py:2 maps the name to; `pendulum` is gym 0.22's PendulumEnv behind NormalizedBoxEnv (Box(-1, 1)
+# actions of width 1, 3-wide observations).
+CLASSIC = {"cartpole": 0, "pendulum": 1}
 
 
 def model_struct(m):
@@ -172,7 +173,7 @@ class HipVectorEnv:
         self.env_name = env_name
         self.env_num = int(env_num)
         self.h = C.c_void_p()
-        if env_name in CLASSIC:         # classic-control engine (CartPole)
+        if env_name in CLASSIC:         # classic-control engine (CartPole, Pendulum)
             if model is not None:
                 raise ValueError(f"{env_name}: a classic-control task has no model description")
             if obs_shift is not None:

@@ -609,9 +609,15 @@ int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_model* model, i
  * dynamics, float64 in gym's order and constants, one lane per env.  State rows: qpos = (x, theta), qvel = (x_dot, theta_dot) (nq = nv = 2);
  * observation = float32 (x, x_dot, theta, theta_dot); reward 1 on every step, the terminal one included; done = |x| > 2.4 or |theta| > 12 deg;
  * reset: every component U[-0.05, 0.05) from the env's Philox stream.  Actions are a Discrete(2) index held as a float in a 1-wide action
- * column (act_dim 1; env_replay_buffer.py:40); random actions are uniform indices.  Reset / step / rollout / evaluation entry points are the
- * ordinary ones; ilsx_vecenv_set_obs_affine is not available. */
-enum { ILSX_CLASSIC_CARTPOLE = 0 };
+ * column (act_dim 1; env_replay_buffer.py:40); random actions are uniform indices.
+ * ILSX_CLASSIC_PENDULUM — gym 0.22's PendulumEnv behind the reference's NormalizedBoxEnv (rlkit/envs/wrappers.py:342-346): Box(-1, 1)
+ * actions of width 1 (discrete_n 0), torque = clip(-2 + (a + 1) * 0.5 * 4, +-2) in float32; float64 state qpos = (theta), qvel =
+ * (theta_dot) (nq = nv = 1, theta never wrapped); observation = float32 (cos theta, sin theta, theta_dot); reward = -(angle_normalize(theta)^2
+ * + 0.1 theta_dot^2 + 0.001 u^2) of the state before the step; theta_dot' = clip(theta_dot + (15 sin theta + 3 u) * 0.05, +-8), theta' =
+ * theta + theta_dot' * 0.05; never done (max_path_length ends episodes); reset: theta ~ U[-pi, pi), theta_dot ~ U[-1, 1).  The replay
+ * record holds the action as the policy gave it, before the map.
+ * Reset / step / rollout / evaluation entry points are the ordinary ones; ilsx_vecenv_set_obs_affine is not available. */
+enum { ILSX_CLASSIC_CARTPOLE = 0, ILSX_CLASSIC_PENDULUM = 1 };
 int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out);
 /* discrete_n = n of a Discrete(n) action space, 0 for Box actions */
 int ilsx_vecenv_action_space(const ilsx_vecenv* env, int* discrete_n);
