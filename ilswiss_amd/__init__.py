@@ -9,6 +9,7 @@ from .device import Context, DevArray, get_context, set_gpu_mode  # noqa: F401
 from .networks import (DiscretePolicy, FlattenMlp, MakeDeterministic, Mlp,  # noqa: F401
                        ReparamTanhMultivariateGaussianPolicy)
 from .replay import EnvReplayBuffer, SimpleReplayBuffer  # noqa: F401
-from .sac import SoftActorCritic, SoftActorCriticGroup, Trainer  # noqa: F401
+from .sac import SoftActorCritic, SoftActorCriticGroup  # noqa: F401
+from .trainer import DeviceTrainer, Trainer  # noqa: F401
 from .mbpo import BNN, MBPO, BNNTrainer, FakeEnv  # noqa: F401
 from .discrete_sac import DiscreteSoftActorCritic  # noqa: F401

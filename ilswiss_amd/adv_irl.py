@@ -17,7 +17,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .device import as_dev, get_context
+from .device import as_dev, get_context, host_ptr
 
 _MODES = dict(airl=0, gail=1, gail2=2, fairl=3)
 _ACT = dict(relu=0, tanh=1)
@@ -111,13 +111,13 @@ class MLPDisc:
         self._need()
         n = self.num_layer_blocks * self.hid_dim
         rm, rv = np.empty(n, np.float32), np.empty(n, np.float32)
-        _lib.check(self.ctx.lib.ilsx_disc_get_bn_stats(self.h, rm.ctypes.data_as(C.c_void_p), rv.ctypes.data_as(C.c_void_p), n))
+        _lib.check(self.ctx.lib.ilsx_disc_get_bn_stats(self.h, host_ptr(rm), host_ptr(rv), n))
         return rm.reshape(self.num_layer_blocks, self.hid_dim), rv.reshape(self.num_layer_blocks, self.hid_dim)
 
     def set_bn_stats(self, running_mean, running_var):
         self._need()
         rm, rv = np.ascontiguousarray(running_mean, np.float32).ravel(), np.ascontiguousarray(running_var, np.float32).ravel()
-        _lib.check(self.ctx.lib.ilsx_disc_set_bn_stats(self.h, rm.ctypes.data_as(C.c_void_p), rv.ctypes.data_as(C.c_void_p), rm.size))
+        _lib.check(self.ctx.lib.ilsx_disc_set_bn_stats(self.h, host_ptr(rm), host_ptr(rv), rm.size))
 
     def bind(self, obs_dim, second_dim=None, state_only=False, disc_lr=1e-3, disc_momentum=0.0, use_grad_pen=True,
              grad_pen_weight=10.0, max_batch=1024, grad_world=1):
@@ -167,11 +167,11 @@ class MLPDisc:
             self._flat = flat.copy()
             return
         phys = self._pad(flat)
-        _lib.check(self.ctx.lib.ilsx_disc_set_params(self.h, phys.ctypes.data_as(C.c_void_p), phys.size))
+        _lib.check(self.ctx.lib.ilsx_disc_set_params(self.h, host_ptr(phys), phys.size))
 
     def _get(self, fn):
         out = np.empty(self._nphys, np.float32)
-        _lib.check(fn(self.h, out.ctypes.data_as(C.c_void_p), out.size))
+        _lib.check(fn(self.h, host_ptr(out), out.size))
         return self._unpad(out)
 
     def get_flat_params(self):
@@ -299,11 +299,9 @@ class AdvIRLTrainer:
         self.disc.reward_dev(obs.ptr, self._second(self._p).ptr, self.Bp, self.mode, self.rew_clip_min, self.rew_clip_max, rew=rew)
         tr = self.policy_trainer
         want = tr.eval_statistics is None
-        _lib.check(self.ctx.lib.ilsx_sac_train_step(tr.h, obs.ptr, act.ptr, rew.ptr, done.ptr, nobs.ptr, self.Bp, None, None,
-                                                    C.byref(tr._stats) if want else None))
+        tr._call("train_step", obs.ptr, act.ptr, rew.ptr, done.ptr, nobs.ptr, self.Bp, None, None)
         self._last_rew = "host"     # the relabelled rewards of this (the latest) policy batch stay in self._p: get_eval_statistics reads them
         if want:
-            tr._fill_stats()
             r = rew.numpy()[: self.Bp]
             if self.disc_eval_statistics is None:
                 self.disc_eval_statistics = OrderedDict()

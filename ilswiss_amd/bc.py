@@ -1,19 +1,20 @@
 """Behaviour cloning over libilsx: the update of the reference's `BC` algorithm (rlkit/torch/algorithms/bc/bc.py:14-106).
 `BC(mode, policy, expert_replay_buffer, batch_size, lr, momentum, num_updates_per_train_call)` keeps the reference's
 kwargs; `train_from_replay` is `_do_training` (:77-79) with the expert batches drawn on the device."""
-import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
 
 from . import _lib
 from .device import as_dev
-from .sac import Trainer, check_swallowed_kwargs
+from .trainer import DeviceTrainer, check_swallowed_kwargs
 
 _MODES = dict(MLE=0, MSE=1)
 
 
-class BC(Trainer):
+class BC(DeviceTrainer):
+    ABI = "bc"   # Stats: the one float of the base (the batch's log-likelihood or MSE)
+
     def __init__(self, mode, policy, expert_replay_buffer=None, num_updates_per_train_call=1, batch_size=1024, lr=1e-3,
                  momentum=0.0, **kwargs):
         assert mode in _MODES, "Invalid mode!"           # bc.py:26
@@ -23,55 +24,34 @@ class BC(Trainer):
         self.mode, self.policy, self.ctx = mode, policy, policy.ctx
         self.expert_replay_buffer, self.batch_size = expert_replay_buffer, int(batch_size)
         self.num_updates_per_train_call = int(num_updates_per_train_call)
-        cfg = _lib.BcCfg(_MODES[mode], lr, momentum, self.batch_size)
-        self.h = C.c_void_p()
-        _lib.check(self.ctx.lib.ilsx_bc_create(self.ctx.h, C.byref(cfg), policy.h, C.byref(self.h)))
-        self.eval_statistics = None
+        self._create(_lib.BcCfg(_MODES[mode], lr, momentum, self.batch_size), policy.h)
 
-    def _record(self, stat):
-        self.eval_statistics = OrderedDict({"Log-Likelihood" if self.mode == "MLE" else "MSE": stat})
+    def _fill_stats(self):
+        self.eval_statistics = OrderedDict({"Log-Likelihood" if self.mode == "MLE" else "MSE": self._stats.value})
 
     def train_step(self, batch, eps=None):
         """_do_update_step (bc.py:81-106) on an explicit batch with keys observations / actions."""
-        ko, po = as_dev(self.ctx, np.ascontiguousarray(batch["observations"], np.float32))
-        ka, pa = as_dev(self.ctx, np.ascontiguousarray(batch["actions"], np.float32))
-        ke, pe = as_dev(self.ctx, np.ascontiguousarray(eps, np.float32)) if eps is not None else (None, None)
-        want, st = self.eval_statistics is None, C.c_float()
-        _lib.check(self.ctx.lib.ilsx_bc_train_step(self.h, po, pa, int(np.shape(batch["observations"])[0]), pe,
-                                                   C.byref(st) if want else None))
-        if want:
-            self._record(st.value)
-        else:
-            self.ctx.sync()
+        keep = [as_dev(self.ctx, np.ascontiguousarray(x, np.float32)) if x is not None else (None, None)
+                for x in (batch["observations"], batch["actions"], eps)]
+        (_, po), (_, pa), (_, pe) = keep
+        self._call("train_step", po, pa, int(np.shape(batch["observations"])[0]), pe, keep=keep)
 
     def train_from_replay(self, replay_buffer=None, n_updates=None, batch_size=None):
         rb = self.expert_replay_buffer if self.expert_replay_buffer is not None else replay_buffer   # use_expert_buffer=True
-        want, st = self.eval_statistics is None, C.c_float()
-        _lib.check(self.ctx.lib.ilsx_bc_train_from_replay(self.h, rb.h, int(n_updates or self.num_updates_per_train_call),
-                                                          int(batch_size or self.batch_size), C.byref(st) if want else None))
-        if want:
-            self._record(st.value)
-
-    def get_eval_statistics(self):
-        return self.eval_statistics
-
-    def end_epoch(self):
-        self.eval_statistics = None
+        super().train_from_replay(rb, n_updates or self.num_updates_per_train_call, batch_size or self.batch_size)
 
     @property
     def networks(self):
         return [self.policy]
 
     def get_snapshot(self):   # bc.py:108-113 (+ the optimiser's Adam state)
-        from .snapshot import get_opt
         flat = self.policy.get_flat_params()
-        return dict(policy=flat, optimizer=get_opt(self.ctx.lib, "bc", self.h, flat.size))
+        return dict(policy=flat, optimizer=self._get_opt(flat.size))
 
     def load_snapshot(self, snap):
-        from .snapshot import set_opt
         self.policy.set_flat_params(snap["policy"])
         if "optimizer" in snap:
-            set_opt(self.ctx.lib, "bc", self.h, snap["optimizer"])
+            self._set_opt(snap["optimizer"])
 
 
 class DAgger(BC):
@@ -93,14 +73,11 @@ class DAgger(BC):
     def train_from_replay(self, replay_buffer=None, n_updates=None, batch_size=None):
         n = int(n_updates or self.num_updates_per_train_call)
         B = int(batch_size or self.batch_size)
-        if self._first_call:          # `epoch == 0` in the reference
+        if self._first_call:          # `epoch == 0` in the reference; these updates report no statistics
             self._first_call = False
-            _lib.check(self.ctx.lib.ilsx_bc_train_from_replay(self.h, self.expert_replay_buffer.h, self.num_initial_train_steps, B, None))
+            _lib.check(self._fn("train_from_replay")(self.h, self.expert_replay_buffer.h, self.num_initial_train_steps, B, None))
         rb = replay_buffer if replay_buffer is not None else self.replay_buffer
-        want, st = self.eval_statistics is None, C.c_float()
-        _lib.check(self.ctx.lib.ilsx_bc_train_from_replay(self.h, rb.h, n, B, C.byref(st) if want else None))
-        if want:
-            self._record(st.value)
+        DeviceTrainer.train_from_replay(self, rb, n, B)
 
     @property
     def networks(self):

@@ -54,7 +54,7 @@ class Context:
         arr = np.ascontiguousarray(arr, dtype=dtype)
         d = DevArray(self, arr.shape, dtype)
         if arr.size:
-            _lib.check(self.lib.ilsx_memcpy_h2d(self.h, d.ptr, arr.ctypes.data_as(C.c_void_p), arr.nbytes))
+            _lib.check(self.lib.ilsx_memcpy_h2d(self.h, d.ptr, host_ptr(arr), arr.nbytes))
         return d
 
     def close(self):
@@ -82,13 +82,13 @@ class DevArray:
     def numpy(self):
         out = np.empty(self.shape, self.dtype)
         if out.size:
-            _lib.check(self.ctx.lib.ilsx_memcpy_d2h(self.ctx.h, out.ctypes.data_as(C.c_void_p), self._p, out.nbytes))
+            _lib.check(self.ctx.lib.ilsx_memcpy_d2h(self.ctx.h, host_ptr(out), self._p, out.nbytes))
         return out
 
     def copy_from(self, arr):
         arr = np.ascontiguousarray(arr, dtype=self.dtype)
         assert arr.shape == self.shape, (arr.shape, self.shape)
-        _lib.check(self.ctx.lib.ilsx_memcpy_h2d(self.ctx.h, self._p, arr.ctypes.data_as(C.c_void_p), arr.nbytes))
+        _lib.check(self.ctx.lib.ilsx_memcpy_h2d(self.ctx.h, self._p, host_ptr(arr), arr.nbytes))
 
     @property
     def __cuda_array_interface__(self):
@@ -141,6 +141,11 @@ def get_context():
     return _default_ctx
 
 
+def host_ptr(arr):
+    """void pointer to the data of a contiguous numpy array, which the caller keeps alive across the library call"""
+    return arr.ctypes.data_as(C.c_void_p)
+
+
 def as_dev(ctx, x, dtype=np.float32):
     """numpy / torch(cpu or cuda) / DevArray -> (keepalive, ctypes pointer)."""
     if isinstance(x, DevArray):
@@ -157,3 +162,17 @@ def as_dev(ctx, x, dtype=np.float32):
         x = x.detach().cpu().numpy()
     d = ctx.from_numpy(np.asarray(x), dtype)
     return d, d.ptr
+
+
+def batch_ptrs(ctx, batch, keep):
+    """A transition batch (numpy / torch / DevArray values; rewards and terminals [B] or [B, 1]) as the library's five device pointers
+    observations, actions, rewards, terminals, next_observations -> (B, pointers, dev).  `dev(x)` stages one more array; every staged
+    copy is appended to `keep`, which must outlive the asynchronous call that reads the pointers."""
+    def dev(x):
+        k, p = as_dev(ctx, x)
+        keep.append(k)
+        return p
+    B = int(batch["observations"].shape[0])
+    flat = lambda v: v.reshape(B) if hasattr(v, "reshape") else v  # noqa: E731
+    return B, [dev(batch["observations"]), dev(batch["actions"]), dev(flat(batch["rewards"])),
+               dev(flat(batch["terminals"])), dev(batch["next_observations"])], dev

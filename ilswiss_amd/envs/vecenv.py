@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from ..device import as_dev, get_context
+from ..device import as_dev, get_context, host_ptr
 from .models import MODELS
 from .models3d import MODELS3D
 
@@ -153,7 +153,7 @@ class DeviceObsRms:
     def _get(self):
         e = self.env
         m, v, c = np.empty(e.obs_dim), np.empty(e.obs_dim), C.c_double()
-        _lib.check(e.ctx.lib.ilsx_vecenv_get_obs_rms(e.h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), C.byref(c)))
+        _lib.check(e.ctx.lib.ilsx_vecenv_get_obs_rms(e.h, host_ptr(m), host_ptr(v), C.byref(c)))
         return m, v, c.value
 
     mean = property(lambda self: self._get()[0])
@@ -163,7 +163,7 @@ class DeviceObsRms:
     def set(self, mean, var, count):
         e = self.env
         m, v = np.ascontiguousarray(mean, np.float64), np.ascontiguousarray(var, np.float64)
-        _lib.check(e.ctx.lib.ilsx_vecenv_set_obs_rms(e.h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), float(count)))
+        _lib.check(e.ctx.lib.ilsx_vecenv_set_obs_rms(e.h, host_ptr(m), host_ptr(v), float(count)))
 
 
 class HipVectorEnv:
@@ -204,7 +204,7 @@ class HipVectorEnv:
         if obs_shift is not None:   # ScaledEnv / MinmaxEnv folded into the stepper
             sh, sc = np.ascontiguousarray(obs_shift, np.float64), np.ascontiguousarray(obs_scale, np.float64)
             assert sh.shape == (self.obs_dim,) and sc.shape == (self.obs_dim,)
-            _lib.check(self.ctx.lib.ilsx_vecenv_set_obs_affine(self.h, sh.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p)))
+            _lib.check(self.ctx.lib.ilsx_vecenv_set_obs_affine(self.h, host_ptr(sh), host_ptr(sc)))
         # vecenvs.py:104-113
         self.norm_obs, self.update_obs_rms = bool(norm_obs), bool(update_obs_rms) and bool(norm_obs)
         self.obs_rms = DeviceObsRms(self) if norm_obs else None
@@ -257,7 +257,7 @@ class HipVectorEnv:
     def reset(self, id=None):
         ids, n = self._ids(id)
         obs = self.ctx.empty((n, self.obs_dim))
-        _lib.check(self.ctx.lib.ilsx_vecenv_reset(self.h, ids.ctypes.data_as(C.c_void_p) if ids is not None else None, n, obs.ptr))
+        _lib.check(self.ctx.lib.ilsx_vecenv_reset(self.h, host_ptr(ids) if ids is not None else None, n, obs.ptr))
         return obs.numpy().astype(np.float64)
 
     def step(self, action, id=None):
@@ -265,7 +265,7 @@ class HipVectorEnv:
         action = np.ascontiguousarray(action, np.float32).reshape(n, self.act_dim)  # sync mode: len(action) == len(id)
         k, pa = as_dev(self.ctx, action)
         obs, rew, done = self.ctx.empty((n, self.obs_dim)), self.ctx.empty((n,)), self.ctx.empty((n,), np.uint8)
-        _lib.check(self.ctx.lib.ilsx_vecenv_step(self.h, pa, ids.ctypes.data_as(C.c_void_p) if ids is not None else None, n,
+        _lib.check(self.ctx.lib.ilsx_vecenv_step(self.h, pa, host_ptr(ids) if ids is not None else None, n,
                                                  obs.ptr, rew.ptr, done.ptr))
         env_ids = ids if ids is not None else np.arange(n)
         infos = [{"env_id": int(i)} for i in env_ids]  # vecenvs.py:217-219
@@ -274,13 +274,13 @@ class HipVectorEnv:
     # ---- simulator state (tests, snapshots)
     def get_state(self):
         q = np.empty((self.env_num, self.nq)); v = np.empty((self.env_num, self.nv))
-        _lib.check(self.ctx.lib.ilsx_vecenv_get_state(self.h, q.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)))
+        _lib.check(self.ctx.lib.ilsx_vecenv_get_state(self.h, host_ptr(q), host_ptr(v)))
         return q, v
 
     def set_state(self, qpos, qvel):
         q, v = np.ascontiguousarray(qpos, np.float64), np.ascontiguousarray(qvel, np.float64)
         assert q.shape == (self.env_num, self.nq) and v.shape == (self.env_num, self.nv)
-        _lib.check(self.ctx.lib.ilsx_vecenv_set_state(self.h, q.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)))
+        _lib.check(self.ctx.lib.ilsx_vecenv_set_state(self.h, host_ptr(q), host_ptr(v)))
 
     # ---- fused device loop (BaseAlgorithm's sampling iteration, base_algorithm.py:183-277)
     def rollout_step(self, policy=None, replay=None, max_path_length=1000, random_actions=False, deterministic=False,

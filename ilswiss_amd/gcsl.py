@@ -17,10 +17,10 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .device import as_dev, get_context
+from .device import as_dev, get_context, host_ptr
 from .her import HER, DeviceHindsightReplayBuffer, HindsightReplayBuffer
 from .networks import ReparamTanhMultivariateGaussianPolicy
-from .sac import Trainer, check_swallowed_kwargs
+from .trainer import DeviceTrainer, check_swallowed_kwargs
 
 
 def horizon_row(T, t):
@@ -161,12 +161,12 @@ class CatagorialConditionPolicy:
 
     def _get(self, which, n):
         out = np.empty(n, np.float32)
-        _lib.check(self.ctx.lib.ilsx_bncat_get(self.h, which, out.ctypes.data_as(C.c_void_p), out.size))
+        _lib.check(self.ctx.lib.ilsx_bncat_get(self.h, which, host_ptr(out), out.size))
         return out
 
     def _set(self, which, v):
         v = np.ascontiguousarray(v, np.float32).ravel()
-        _lib.check(self.ctx.lib.ilsx_bncat_set(self.h, which, v.ctypes.data_as(C.c_void_p), v.size))
+        _lib.check(self.ctx.lib.ilsx_bncat_set(self.h, which, host_ptr(v), v.size))
 
     def get_flat_params(self):
         return self._get(0, self.num_params)
@@ -299,9 +299,10 @@ class MlpGaussianAndEpsilonConditionPolicy(ReparamTanhMultivariateGaussianPolicy
 _MODES = dict(MSE=1, CLASS=2)
 
 
-class GCSL(Trainer):
+class GCSL(DeviceTrainer):
     """gcsl.py:11-118.  `reward_scale`, `discount` (and `soft_target_tau` of the specs) are accepted and unused, as in the reference.
     Statistics: CLASS {"CE Loss", "Accuracy"}, MSE {"MSE"}, from the first batch after end_epoch."""
+    ABI, Stats = "gcsl", C.c_float * 2
 
     def __init__(self, policy, mode="MSE", reward_scale=1.0, discount=0.99, policy_lr=1e-3, optimizer_class=None, use_horizons=False,
                  goal_dim=None, max_batch=256, **kwargs):
@@ -330,25 +331,20 @@ class GCSL(Trainer):
         elif policy.max_rows < self.max_batch:
             raise ValueError(f"GCSL: policy max_rows {policy.max_rows} < max_batch {self.max_batch}")
         cfg = _lib.GcslCfg(_MODES[mode], self.policy_lr, self.max_batch, self.d_obs, self.d_goal, self.horizon)
-        self.h = C.c_void_p()
-        _lib.check(self.ctx.lib.ilsx_gcsl_create(self.ctx.h, C.byref(cfg), policy.h if mode == "CLASS" else None, bc_h,
-                                                 int(policy.action_dim), C.byref(self.h)))
-        self.eval_statistics = None
+        self._create(cfg, policy.h if mode == "CLASS" else None, bc_h, int(policy.action_dim))
         self._n_train_steps_total = 0
 
-    def _record(self, st):
+    def _fill_stats(self):
+        st = self._stats
         if self.mode == "CLASS":
             self.eval_statistics = OrderedDict([("CE Loss", float(st[0])), ("Accuracy", float(st[1]))])
         else:
             self.eval_statistics = OrderedDict([("MSE", float(st[0]))])
 
     def train_step(self, batch):
-        want = self.eval_statistics is None
-        st = np.zeros(2, np.float32)
-        sp = st.ctypes.data_as(C.c_void_p) if want else None
         if "_gcsl_indices" in batch:          # DeviceHindsightHorizonReplayBuffer: gathered on the device into the trainer's input
             di, dr, B = batch["_gcsl_indices"]
-            _lib.check(self.ctx.lib.ilsx_gcsl_train_from_replay(self.h, batch["_ring"].h, di.ptr, dr.ptr, B, sp))
+            self._call("train_from_replay", batch["_ring"].h, di.ptr, dr.ptr, B)
         else:
             parts = [np.asarray(batch["observations"], np.float32), np.asarray(batch["desired_goals"], np.float32)]
             if self.horizon:
@@ -359,16 +355,8 @@ class GCSL(Trainer):
                    else np.ascontiguousarray(a, np.float32))
             kx, px = as_dev(self.ctx, X)
             kt, pt = as_dev(self.ctx, tgt, tgt.dtype)
-            _lib.check(self.ctx.lib.ilsx_gcsl_train_step(self.h, px, pt, X.shape[0], sp))
-        if want:
-            self._record(st)
+            self._call("train_step", px, pt, X.shape[0], keep=(kx, kt))
         self._n_train_steps_total += 1
-
-    def get_eval_statistics(self):
-        return self.eval_statistics
-
-    def end_epoch(self):
-        self.eval_statistics = None
 
     @property
     def networks(self):
@@ -379,17 +367,15 @@ class GCSL(Trainer):
         vector (log-std head included) with its Adam state, the layout ilsx_bc_get_opt speaks."""
         if self.mode == "CLASS":
             return dict(policy=self.policy.get_snapshot())
-        from .snapshot import get_opt
         flat = self.policy.get_device_flat_params()
-        return dict(policy=dict(params=flat, optimizer=get_opt(self.ctx.lib, "bc", self._bc.h, flat.size)))
+        return dict(policy=dict(params=flat, optimizer=self._bc._get_opt(flat.size)))
 
     def load_snapshot(self, snap):
         if self.mode == "CLASS":
             self.policy.load_snapshot(snap["policy"])
         else:
-            from .snapshot import set_opt
             self.policy.set_device_flat_params(snap["policy"]["params"])
-            set_opt(self.ctx.lib, "bc", self._bc.h, snap["policy"]["optimizer"])
+            self._bc._set_opt(snap["policy"]["optimizer"])
 
     def __del__(self):
         h = getattr(self, "h", None)

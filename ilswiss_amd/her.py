@@ -13,6 +13,7 @@ import random
 
 import numpy as np
 
+from .device import host_ptr
 from .sac import SoftActorCritic
 from .td3 import TD3 as _TD3, MlpGaussianNoisePolicy
 
@@ -249,12 +250,10 @@ class DeviceHindsightReplayBuffer(HindsightReplayBuffer):
 
     def add_sample(self, observation, action, reward, terminal, next_observation, **kwargs):
         assert isinstance(observation, dict), "Observation should be dict!"
-        C = self._C
         obs, nobs = self._row(observation), self._row(next_observation)
         act = np.asarray(action, np.float32).reshape(1, self._action_dim)
         rew, done = np.asarray([reward], np.float32), np.asarray([1 if terminal else 0], np.uint8)
-        p = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
-        self._lib.check(self.ctx.lib.ilsx_replay_add(self.h, p(obs), p(act), p(rew), p(done), p(nobs), 1, None, 0))
+        self._lib.check(self.ctx.lib.ilsx_replay_add(self.h, *[host_ptr(x) for x in (obs, act, rew, done, nobs)], 1, None, 0))
         t = self._top                               # host cursors exactly as the parent's (the ring's own cursor moves in step)
         if terminal:
             nxt = (t + 1) % self._max_replay_buffer_size

@@ -15,9 +15,9 @@ import numpy as np
 
 from . import _lib
 from .algorithm import DeviceRLAlgorithm
-from .device import get_context
+from .device import get_context, host_ptr
 from .replay import EnvReplayBuffer, SimpleReplayBuffer
-from .sac import check_swallowed_kwargs
+from .trainer import check_swallowed_kwargs
 
 MAX_LOG_VAR, MIN_LOG_VAR = 0.5, -10.0
 
@@ -40,7 +40,7 @@ class FixedNormalizer:
     def _get(self):
         n = self._bnn.input_size
         m, s = np.empty(n, np.float32), np.empty(n, np.float32)
-        _lib.check(self._bnn.ctx.lib.ilsx_bnn_get_normalizer(self._bnn.h, m.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._bnn.ctx.lib.ilsx_bnn_get_normalizer(self._bnn.h, host_ptr(m), host_ptr(s)))
         return m, s
 
     @property
@@ -54,7 +54,7 @@ class FixedNormalizer:
     def _set(self, mean, std):
         m = np.ascontiguousarray(mean, np.float32).reshape(-1)
         s = np.ascontiguousarray(std, np.float32).reshape(-1)
-        _lib.check(self._bnn.ctx.lib.ilsx_bnn_set_normalizer(self._bnn.h, m.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._bnn.ctx.lib.ilsx_bnn_set_normalizer(self._bnn.h, host_ptr(m), host_ptr(s)))
 
     def set_mean(self, mean):
         self._set(np.asarray(mean, np.float32) + np.zeros(self._bnn.input_size, np.float32), self.std)
@@ -131,12 +131,12 @@ class BNN:
 
     def get_flat_params(self):
         p = np.empty(self.num_params(), np.float32)
-        _lib.check(self.ctx.lib.ilsx_bnn_get_params(self.h, p.ctypes.data_as(C.c_void_p), p.size))
+        _lib.check(self.ctx.lib.ilsx_bnn_get_params(self.h, host_ptr(p), p.size))
         return p
 
     def set_flat_params(self, p):
         p = np.ascontiguousarray(p, np.float32).reshape(-1)
-        _lib.check(self.ctx.lib.ilsx_bnn_set_params(self.h, p.ctypes.data_as(C.c_void_p), p.size))
+        _lib.check(self.ctx.lib.ilsx_bnn_set_params(self.h, host_ptr(p), p.size))
 
     def get_params(self):
         flat, out, f = self.get_flat_params(), [], 0
@@ -152,13 +152,13 @@ class BNN:
     def get_opt(self):
         n = self.num_params()
         m, v, meta = np.empty(n, np.float32), np.empty(n, np.float32), _lib.OptMeta()
-        _lib.check(self.ctx.lib.ilsx_bnn_get_opt(self.h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), n, C.byref(meta)))
+        _lib.check(self.ctx.lib.ilsx_bnn_get_opt(self.h, host_ptr(m), host_ptr(v), n, C.byref(meta)))
         return m, v, dict(t=meta.t, rng_step=meta.rng_step)
 
     def set_opt(self, m, v, meta):
         m, v = np.ascontiguousarray(m, np.float32), np.ascontiguousarray(v, np.float32)
         om = _lib.OptMeta(int(meta["t"]), int(meta["rng_step"]), int(meta["t"]))
-        _lib.check(self.ctx.lib.ilsx_bnn_set_opt(self.h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), m.size, C.byref(om)))
+        _lib.check(self.ctx.lib.ilsx_bnn_set_opt(self.h, host_ptr(m), host_ptr(v), m.size, C.byref(om)))
 
     def forward(self, inputs, ret_log_var=False):
         """inputs [n, in] (numpy) -> (mean [E, n, D], log-var or var [E, n, D])"""
@@ -223,13 +223,13 @@ class BNNTrainer:
         if n == 0:   # torch.mean over no rows (an empty holdout): NaN, as compute_loss gives in the reference
             return np.full(self.bnn.num_nets, np.nan, np.float32)
         out = np.empty(self.bnn.num_nets, np.float32)
-        _lib.check(self.ctx.lib.ilsx_bnn_mse(self.bnn.h, rb.h, table.ptr, int(stride), int(n), int(add_var), out.ctypes.data_as(C.c_void_p)))
+        _lib.check(self.ctx.lib.ilsx_bnn_mse(self.bnn.h, rb.h, table.ptr, int(stride), int(n), int(add_var), host_ptr(out)))
         return out
 
     def _train_batch(self, rb, table, col, stride, B, want_loss=False):
         out = np.empty(self.bnn.num_nets, np.float32) if want_loss else None
         _lib.check(self.ctx.lib.ilsx_bnn_train_batch(self.bnn.h, rb.h, _off(table.ptr, 4 * col), int(stride), int(B),
-                                                      out.ctypes.data_as(C.c_void_p) if want_loss else None))
+                                                      host_ptr(out) if want_loss else None))
         return out
 
     def train_step(self, batch):
@@ -477,7 +477,7 @@ class MBPO(DeviceRLAlgorithm):
         for i in range(self.rollout_length):
             ns = C.c_int()
             _lib.check(lib.ilsx_mbpo_model_step(self.model.bnn.h, self.algo.policy.h, self.model_replay_buffer.h, self.term_kind, cur.ptr,
-                                                None, rows, elites.ctypes.data_as(C.c_void_p), len(elites), int(deterministic), None, None,
+                                                None, rows, host_ptr(elites), len(elites), int(deterministic), None, None,
                                                 None, None, nxt.ptr, C.byref(ns)))
             steps.append(rows)
             if ns.value == 0:
@@ -509,10 +509,7 @@ class MBPO(DeviceRLAlgorithm):
                 if cnt > 0:
                     ptrs = [_off(x.ptr, 4 * lo * (x.shape[1] if len(x.shape) > 1 else 1)) for x in st]
                     _lib.check(lib.ilsx_replay_sample(rb.h, cnt, None, *ptrs, None))
-            want = self.algo.eval_statistics is None
-            _lib.check(lib.ilsx_sac_train_step(self.algo.h, *[x.ptr for x in st], B, None, None, C.byref(self.algo._stats) if want else None))
-            if want:
-                self.algo._fill_stats()
+            self.algo._call("train_step", *[x.ptr for x in st], B, None, None)
 
     # ---- mbpo.py:70-162
     def train(self, start_epoch=0):

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import DevArray, as_dev, get_context
+from .device import DevArray, as_dev, get_context, host_ptr
 
 _ACT = {"relu": 0, "tanh": 1}
 _WIDTHS = (64, 128, 256)   # hidden widths the kernels are instantiated for
@@ -75,12 +75,12 @@ class Mlp:
     # -- parameters
     def get_flat_params(self):
         out = np.empty(self.num_params, np.float32)
-        _lib.check(self.ctx.lib.ilsx_net_get_params(self.h, out.ctypes.data_as(C.c_void_p), out.size, 0))
+        _lib.check(self.ctx.lib.ilsx_net_get_params(self.h, host_ptr(out), out.size, 0))
         return out
 
     def set_flat_params(self, flat):
         flat = np.ascontiguousarray(flat, np.float32)
-        _lib.check(self.ctx.lib.ilsx_net_set_params(self.h, flat.ctypes.data_as(C.c_void_p), flat.size, 0))
+        _lib.check(self.ctx.lib.ilsx_net_set_params(self.h, host_ptr(flat), flat.size, 0))
 
     def copy(self, ctx=None):  # PyTorchModule.copy (rlkit/torch/core.py:32-35); ctx: the copy lives in another context of the same device
         c = type(self).__new__(type(self))

@@ -10,9 +10,9 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .device import as_dev
+from .device import as_dev, host_ptr
 from .networks import Mlp
-from .sac import Trainer, check_swallowed_kwargs
+from .trainer import Trainer, check_swallowed_kwargs
 
 
 class ReparamMultivariateGaussianPolicy(Mlp):
@@ -90,11 +90,11 @@ class PPO(Trainer):
         for which, flat in ((0, pi_flat), (1, vf_flat)):
             if flat is not None:
                 flat = np.ascontiguousarray(flat, np.float32)
-                _lib.check(self.ctx.lib.ilsx_ppo_set_params(self.h, which, flat.ctypes.data_as(C.c_void_p), flat.size))
+                _lib.check(self.ctx.lib.ilsx_ppo_set_params(self.h, which, host_ptr(flat), flat.size))
 
     def get_flat_params(self, which):
         out = np.empty(self._num(which), np.float32)
-        _lib.check(self.ctx.lib.ilsx_ppo_get_params(self.h, which, out.ctypes.data_as(C.c_void_p), out.size))
+        _lib.check(self.ctx.lib.ilsx_ppo_get_params(self.h, which, host_ptr(out), out.size))
         return out
 
     # ---- data plumbing
@@ -115,7 +115,7 @@ class PPO(Trainer):
         keep, (po, pa, pr), offs = self._upload(trajs)
         N = int(offs[-1])
         outs = [self.ctx.empty((N,)) for _ in range(4)]
-        _lib.check(self.ctx.lib.ilsx_ppo_gae(self.h, po, pa, pr, offs.ctypes.data_as(C.c_void_p), len(offs) - 1, None,
+        _lib.check(self.ctx.lib.ilsx_ppo_gae(self.h, po, pa, pr, host_ptr(offs), len(offs) - 1, None,
                                              *[x.ptr for x in outs]))
         return tuple(x.numpy().reshape(N, 1) for x in outs)
 
@@ -127,8 +127,8 @@ class PPO(Trainer):
         if perms is not None:
             perms = np.ascontiguousarray(perms, np.int32)
             assert perms.shape == (self.update_epoch, int(offs[-1]))
-            pp = perms.ctypes.data_as(C.c_void_p)
-        _lib.check(self.ctx.lib.ilsx_ppo_train(self.h, po, pa, pr, offs.ctypes.data_as(C.c_void_p), len(offs) - 1, None, pp))
+            pp = host_ptr(perms)
+        _lib.check(self.ctx.lib.ilsx_ppo_train(self.h, po, pa, pr, host_ptr(offs), len(offs) - 1, None, pp))
         if self.eval_statistics is None:
             self.eval_statistics = OrderedDict()
 
@@ -157,7 +157,7 @@ class PPO(Trainer):
             seg_of_last = np.searchsorted(offs, (open_env + 1) * T, side="left") - 1
             b[seg_of_last] = lastv.numpy()[open_env]
         boot = ctx.from_numpy(b)
-        _lib.check(ctx.lib.ilsx_ppo_train(self.h, obs.ptr, act.ptr, rew.ptr, offs.ctypes.data_as(C.c_void_p), offs.size - 1,
+        _lib.check(ctx.lib.ilsx_ppo_train(self.h, obs.ptr, act.ptr, rew.ptr, host_ptr(offs), offs.size - 1,
                                           boot.ptr, None))
         if self.eval_statistics is None:
             self.eval_statistics = OrderedDict([("PPO Segments", float(offs.size - 1)), ("PPO Samples", float(N))])

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import as_dev, get_context
+from .device import as_dev, get_context, host_ptr
 
 
 class SimpleReplayBuffer:
@@ -63,10 +63,8 @@ class SimpleReplayBuffer:
         ee = None
         if ep_end is not None:
             ee = np.ascontiguousarray(ep_end).astype(np.uint8)
-        vp = C.c_void_p
         _lib.check(self.ctx.lib.ilsx_replay_add(
-            self.h, obs.ctypes.data_as(vp), act.ctypes.data_as(vp), rew.ctypes.data_as(vp), term.ctypes.data_as(vp),
-            next_obs.ctypes.data_as(vp), n, ee.ctypes.data_as(vp) if ee is not None else None, 0))
+            self.h, host_ptr(obs), host_ptr(act), host_ptr(rew), host_ptr(term), host_ptr(next_obs), n, host_ptr(ee) if ee is not None else None, 0))
 
     def add_sample(self, observation, action, reward, terminal, next_observation, timeout=False, **kwargs):
         self.add_rows(np.asarray(observation)[None], np.asarray(action)[None], [reward], [terminal],
@@ -102,7 +100,7 @@ class SimpleReplayBuffer:
         top = self._top
         self.add_rows(np.asarray(obs), np.asarray(act), np.asarray(rew), np.zeros(m, np.uint8), np.asarray(nobs), ep_end)
         flags = np.ascontiguousarray(ab, np.float32)
-        _lib.check(self.ctx.lib.ilsx_replay_set_absorbing(self.h, top, m, flags.ctypes.data_as(C.c_void_p)))
+        _lib.check(self.ctx.lib.ilsx_replay_set_absorbing(self.h, top, m, host_ptr(flags)))
         self._trajs += 1
 
     def get_traj_num(self):

@@ -3,60 +3,22 @@ rlkit/torch/algorithms/sac/sac_alpha.py:13-284 interface (Trainer ABC: rlkit/cor
 Constructor kwargs are the YAML `sac_params` keys (exp_specs/sac/sac_hopper.yaml:36-47); unknown keys
 are swallowed like the reference's **kwargs (sac_alpha.py:39).
 """
-import abc
 import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
 
 from . import _lib
-from .device import RawView, as_dev, get_context
+from .device import RawView, batch_ptrs, host_ptr
+from .trainer import DeviceTrainer, Trainer, check_swallowed_kwargs, create_stats_ordered_dict  # noqa: F401  (importable from here as before)
 
 
-def check_swallowed_kwargs(kwargs, who):
-    """The reference's trainers take **kwargs and ignore what they do not know; two of the keys they DO read select something libilsx
-    does not have — another optimiser than Adam (`optimizer_class`, e.g. sac_alpha.py:35) or another critic criterion than MSE
-    (`qf_criterion`, td3.py:36): those fail loudly, everything else is swallowed as in the reference."""
-    oc = kwargs.get("optimizer_class")
-    if oc is not None and getattr(oc, "__name__", oc) != "Adam":
-        raise NotImplementedError(f"{who}(optimizer_class={getattr(oc, '__name__', oc)}): libilsx implements torch.optim.Adam")
-    qc = kwargs.get("qf_criterion")
-    if qc is not None:   # an nn.MSELoss instance, the class itself, or its name; anything else (L1Loss, "huber", ...) is refused, not trained as MSE
-        name = qc if isinstance(qc, str) else (getattr(qc, "__name__", None) or type(qc).__name__)
-        if name.lower() not in ("mseloss", "mse"):
-            raise NotImplementedError(f"{who}(qf_criterion={qc!r}): libilsx implements the MSE criterion")
-
-
-class Trainer(metaclass=abc.ABCMeta):  # rlkit/core/trainer.py:4-28
-    @abc.abstractmethod
-    def train_step(self, batch):
-        pass
-
-    def get_eval_statistics(self):
-        return None
-
-    def get_snapshot(self):
-        return {}
-
-    def end_epoch(self):
-        pass
-
-    @property
-    @abc.abstractmethod
-    def networks(self):
-        pass
-
-
-def create_stats_ordered_dict(name, data):  # rlkit/core/eval_util.py:create_stats_ordered_dict (Mean/Std/Max/Min)
-    data = np.asarray(data, dtype=np.float64)
-    if data.size == 1:
-        return OrderedDict({name: float(data.ravel()[0])})
-    return OrderedDict([(name + " Mean", np.mean(data)), (name + " Std", np.std(data)),
-                        (name + " Max", np.max(data)), (name + " Min", np.min(data))])
-
-
-class SoftActorCritic(Trainer):
+class SoftActorCritic(DeviceTrainer):
+    ABI, Stats = "sac", _lib.SacStats
     WHICH = dict(policy=0, qf1=1, qf2=2, target_qf1=3, target_qf2=4)
+    SNAPSHOT_KEYS = tuple(WHICH)
+    OPT = (("policy", 0), ("qf1", 1), ("qf2", 2))
+    PARAMS_TAIL = (0,)   # dst_is_device / src_is_device: host arrays
 
     def __init__(self, policy, qf1, qf2, reward_scale=1.0, discount=0.99, policy_lr=1e-3, qf_lr=1e-3,
                  alpha_lr=3e-4, soft_target_tau=1e-2, alpha=0.2, train_alpha=True,
@@ -75,42 +37,16 @@ class SoftActorCritic(Trainer):
                           int(grad_world))
         self.target_entropy = target_entropy if target_entropy is not None else -policy.action_dim / 2.0
         self.max_batch, self.grad_world = int(max_batch), int(grad_world)
-        self.h = C.c_void_p()
-        _lib.check(self.ctx.lib.ilsx_sac_create(self.ctx.h, C.byref(cfg), policy.h, qf1.h, qf2.h, C.byref(self.h)))
-        self.eval_statistics = None
-        self._stats = _lib.SacStats()
+        self._create(cfg, policy.h, qf1.h, qf2.h)
 
     # ---- Trainer API
     def train_step(self, batch, eps_next=None, eps_cur=None):
         """batch: dict with observations, actions, rewards, terminals, next_observations (numpy, torch or
         DevArray, fp32 [B,.]).  eps_*: explicit N(0,1) [B,a] draws (parity mode), else Philox."""
-        ctx, keep = self.ctx, []
-
-        def dev(x):
-            k, p = as_dev(ctx, x)
-            keep.append(k)
-            return p
-        obs = batch["observations"]
-        B = int(obs.shape[0])
-        flat = lambda v: v.reshape(B) if hasattr(v, "reshape") else v  # noqa: E731
-        p = [dev(obs), dev(batch["actions"]), dev(flat(batch["rewards"])), dev(flat(batch["terminals"])),
-             dev(batch["next_observations"])]
-        e1 = dev(eps_next) if eps_next is not None else None
-        e2 = dev(eps_cur) if eps_cur is not None else None
-        want = self.eval_statistics is None
-        _lib.check(ctx.lib.ilsx_sac_train_step(self.h, *p, B, e1, e2, C.byref(self._stats) if want else None))
-        if want:
-            self._fill_stats()
-        if not want:
-            ctx.sync()  # `keep` buffers must outlive the asynchronous step
-
-    def train_from_replay(self, replay_buffer, n_steps, batch_size):
-        """TorchRLAlgorithm._do_training (torch_rl_algorithm.py:28-34) with on-device sampling."""
-        want = self.eval_statistics is None
-        _lib.check(self.ctx.lib.ilsx_sac_train_from_replay(self.h, replay_buffer.h, int(n_steps), int(batch_size),
-                                                           C.byref(self._stats) if want else None))
-        if want:
-            self._fill_stats()
+        keep = []
+        B, p, dev = batch_ptrs(self.ctx, batch, keep)
+        self._call("train_step", *p, B, dev(eps_next) if eps_next is not None else None, dev(eps_cur) if eps_cur is not None else None,
+                   keep=keep)
 
     def phase_state(self):
         """How the merged phase kernels of this agent's train windows are doing (include/ilsx.h ilsx_sac_phase_state): a shared GPU can
@@ -138,39 +74,15 @@ class SoftActorCritic(Trainer):
         block("Policy log std", s.policy_log_std_mean, 4)
         self.eval_statistics = st
 
-    def get_eval_statistics(self):
-        return self.eval_statistics
-
-    def end_epoch(self):
-        self.eval_statistics = None
-
     @property
     def networks(self):
         return [self.policy, self.qf1, self.qf2]
 
-    def to(self, device=None):
-        return self
-
     # ---- parameter / optimiser access (snapshots, parity tests)
-    def _n(self, which):
-        return self.policy.num_params if which == 0 else self.qf1.num_params
-
-    def get_params(self, name):
-        w = self.WHICH[name]
-        out = np.empty(self._n(w), np.float32)
-        _lib.check(self.ctx.lib.ilsx_sac_get_params(self.h, w, out.ctypes.data_as(C.c_void_p), out.size, 0))
-        return out
-
-    def set_params(self, name, flat):
-        w = self.WHICH[name]
-        flat = np.ascontiguousarray(flat, np.float32)
-        _lib.check(self.ctx.lib.ilsx_sac_set_params(self.h, w, flat.ctypes.data_as(C.c_void_p), flat.size, 0))
+    get_params, set_params = DeviceTrainer.get_flat_params, DeviceTrainer.set_flat_params   # the names this trainer has always had
 
     def get_grads(self, name):
-        w = self.WHICH[name]
-        out = np.empty(self._n(w), np.float32)
-        _lib.check(self.ctx.lib.ilsx_sac_get_grads(self.h, w, out.ctypes.data_as(C.c_void_p), out.size, 0))
-        return out
+        return self._read("get_grads", name)
 
     @property
     def log_alpha(self):
@@ -194,14 +106,14 @@ class SoftActorCritic(Trainer):
         _lib.check(self.ctx.lib.ilsx_sac_grads_ptr(self.h, segment, C.byref(p), C.byref(n)))
         return RawView(p.value, n.value)
 
+    # overrides the base's pair: this on-disk dict has no rng_step / n_train_steps per net, so it goes through ilsx_sac_get_adam / alpha_opt
     def get_snapshot(self):  # sac_alpha.py:249-261, as plain arrays
-        snap = {k: self.get_params(k) for k in self.WHICH}
+        snap = {k: self.get_params(k) for k in self.SNAPSHOT_KEYS}
         snap["log_alpha"] = self.log_alpha
-        for k, w in (("policy", 0), ("qf1", 1), ("qf2", 2)):
-            m, v = np.empty(self._n(w), np.float32), np.empty(self._n(w), np.float32)
+        for k, w in self.OPT:
+            m, v = np.empty(snap[k].size, np.float32), np.empty(snap[k].size, np.float32)
             t = C.c_int64()
-            _lib.check(self.ctx.lib.ilsx_sac_get_adam(self.h, w, m.ctypes.data_as(C.c_void_p),
-                                                      v.ctypes.data_as(C.c_void_p), m.size, C.byref(t)))
+            _lib.check(self.ctx.lib.ilsx_sac_get_adam(self.h, w, host_ptr(m), host_ptr(v), m.size, C.byref(t)))
             snap[k + "_optimizer"] = dict(exp_avg=m, exp_avg_sq=v, step=t.value)
         m, v, t, r = C.c_double(), C.c_double(), C.c_int64(), C.c_uint64()
         _lib.check(self.ctx.lib.ilsx_sac_get_alpha_opt(self.h, C.byref(m), C.byref(v), C.byref(t), C.byref(r)))
@@ -209,14 +121,13 @@ class SoftActorCritic(Trainer):
         return snap
 
     def load_snapshot(self, snap):  # sac_alpha.py:263-273
-        for k in self.WHICH:
+        for k in self.SNAPSHOT_KEYS:
             self.set_params(k, snap[k])
         self.log_alpha = snap["log_alpha"]
-        for k, w in (("policy", 0), ("qf1", 1), ("qf2", 2)):
+        for k, w in self.OPT:
             o = snap[k + "_optimizer"]
             m, v = np.ascontiguousarray(o["exp_avg"], np.float32), np.ascontiguousarray(o["exp_avg_sq"], np.float32)
-            _lib.check(self.ctx.lib.ilsx_sac_set_adam(self.h, w, m.ctypes.data_as(C.c_void_p),
-                                                      v.ctypes.data_as(C.c_void_p), m.size, int(o["step"])))
+            _lib.check(self.ctx.lib.ilsx_sac_set_adam(self.h, w, host_ptr(m), host_ptr(v), m.size, int(o["step"])))
         o = snap["alpha_optimizer"]
         _lib.check(self.ctx.lib.ilsx_sac_set_alpha_opt(self.h, o["exp_avg"], o["exp_avg_sq"], int(o["step"]),
                                                        int(o["rng_step"])))
@@ -251,19 +162,11 @@ class SoftActorCritic(Trainer):
 
     # ---- split-run phases (multi-GPU)
     def set_batch(self, batch, eps_next=None, eps_cur=None):
-        ctx, keep = self.ctx, []
-
-        def dev(x):
-            k, p = as_dev(ctx, x)
-            keep.append(k)
-            return p
-        B = int(batch["observations"].shape[0])
-        flat = lambda v: v.reshape(B)  # noqa: E731
-        _lib.check(ctx.lib.ilsx_sac_set_batch(
-            self.h, dev(batch["observations"]), dev(batch["actions"]), dev(flat(batch["rewards"])),
-            dev(flat(batch["terminals"])), dev(batch["next_observations"]), B,
-            dev(eps_next) if eps_next is not None else None, dev(eps_cur) if eps_cur is not None else None))
-        ctx.sync()
+        keep = []
+        B, p, dev = batch_ptrs(self.ctx, batch, keep)
+        _lib.check(self.ctx.lib.ilsx_sac_set_batch(self.h, *p, B, dev(eps_next) if eps_next is not None else None,
+                                                   dev(eps_cur) if eps_cur is not None else None))
+        self.ctx.sync()   # `keep` must outlive the asynchronous copies
 
     def critic_backward(self):
         _lib.check(self.ctx.lib.ilsx_sac_critic_backward(self.h))

@@ -12,13 +12,14 @@ import pickle
 import numpy as np
 
 from . import _lib
+from .device import host_ptr
 
 
 def get_opt(lib, name, h, n, which=None):
     """Adam state of one parameter block through ilsx_<name>_get_opt -> dict(exp_avg, exp_avg_sq, step, rng_step, n_train_steps)."""
     m, v, meta = np.empty(n, np.float32), np.empty(n, np.float32), _lib.OptMeta()
     fn = getattr(lib, f"ilsx_{name}_get_opt")
-    args = ([h] if which is None else [h, int(which)]) + [m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), n, C.byref(meta)]
+    args = ([h] if which is None else [h, int(which)]) + [host_ptr(m), host_ptr(v), n, C.byref(meta)]
     _lib.check(fn(*args))
     return dict(exp_avg=m, exp_avg_sq=v, step=int(meta.t), rng_step=int(meta.rng_step), n_train_steps=int(meta.n_train_steps))
 
@@ -28,7 +29,7 @@ def set_opt(lib, name, h, state, which=None):
     v = np.ascontiguousarray(state["exp_avg_sq"], np.float32)
     meta = _lib.OptMeta(int(state["step"]), int(state.get("rng_step", 0)), int(state.get("n_train_steps", 0)))
     fn = getattr(lib, f"ilsx_{name}_set_opt")
-    args = ([h] if which is None else [h, int(which)]) + [m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), m.size, C.byref(meta)]
+    args = ([h] if which is None else [h, int(which)]) + [host_ptr(m), host_ptr(v), m.size, C.byref(meta)]
     _lib.check(fn(*args))
 
 
@@ -74,7 +75,7 @@ def restore_replay(rb, dump):
         ab = dump.get("absorbing")
         if ab is not None and len(ab) and np.any(ab[sl]):     # the wrap_absorbing flags travel with the rows (simple_replay_buffer.py:66-67)
             flags = np.ascontiguousarray(ab[sl], np.float32)
-            _lib.check(rb.ctx.lib.ilsx_replay_set_absorbing(rb.h, int(slot0), int(flags.shape[0]), flags.ctypes.data_as(C.c_void_p)))
+            _lib.check(rb.ctx.lib.ilsx_replay_set_absorbing(rb.h, int(slot0), int(flags.shape[0]), host_ptr(flags)))
 
 
 def load_from_file(algorithm, load_replay_buffer=False, load_model=True, load_path=None):
