@@ -60,6 +60,17 @@ class PlanarModel(C.Structure):  # ilsx_planar_model
 _ML3, _MC3, _MB3 = 20, 32, 16
 
 
+_MC = 3    # ILSX_CARTCHAIN_MAX_DOF
+
+
+class CartChainModel(C.Structure):  # ilsx_cartchain_model
+    _fields_ = [("n_pole", C.c_int32), ("frame_skip", C.c_int32), ("pgs_iters", C.c_int32), ("limited", C.c_int32 * _MC),
+                ("mass", C.c_double * _MC), ("inertia", C.c_double * _MC), ("com", (C.c_double * 2) * _MC), ("anchor", (C.c_double * 2) * _MC),
+                ("armature", C.c_double * _MC), ("damping", C.c_double * _MC), ("range", (C.c_double * 2) * _MC),
+                ("tip", C.c_double * 2), ("gear", C.c_double), ("ctrl_range", C.c_double * 2), ("jsign", C.c_double),
+                ("timestep", C.c_double), ("gravity", C.c_double), ("limit_solref", C.c_double * 2), ("limit_solimp", C.c_double * 3)]
+
+
 class SpatialModel(C.Structure):  # ilsx_spatial_model
     _fields_ = [("task", C.c_int32), ("n_link", C.c_int32), ("n_act", C.c_int32), ("n_contact", C.c_int32),
                 ("n_body", C.c_int32), ("frame_skip", C.c_int32), ("pgs_iters", C.c_int32), ("max_rows", C.c_int32),
@@ -325,6 +336,7 @@ PROTOTYPES = {
     "ilsx_net_set_categorical": (C.c_int, [vp, C.c_int]),
     "ilsx_policy_log_pis": (C.c_int, [vp, vp, C.c_int, vp]),
     "ilsx_vecenv_create_classic": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "ilsx_vecenv_create_cartchain": (C.c_int, [vp, C.POINTER(CartChainModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
     "ilsx_vecenv_action_space": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "ilsx_dsac_create": (C.c_int, [vp, C.POINTER(DsacCfg), vp, vp, vp, C.POINTER(vp)]),
     "ilsx_dsac_destroy": (C.c_int, [vp]),

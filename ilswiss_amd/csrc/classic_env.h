@@ -11,9 +11,12 @@
 // (rlkit/envs/wrappers.py:342-346), which every training script wraps Box envs in and which is folded into the stepper here as it is for
 // the MuJoCo tasks.  Box(-1, 1) actions of width 1; qpos = (theta), qvel = (theta_dot), float64; theta is never wrapped in the state.
 // Never done (the reference builds PendulumEnv directly, with no TimeLimit): max_path_length ends episodes.
+//
+// InvertedPendulum / InvertedDoublePendulum: gym 0.22's task rules (envs_dict.py `invertedpendulum` / `inverteddoublependulum`) on this
+// repository's own cart-and-poles dynamics (k_cartchain_step at the end of this file).
 #pragma once
 
-enum { CLASSIC_CARTPOLE = 0, CLASSIC_PENDULUM = 1 };
+enum { CLASSIC_CARTPOLE = 0, CLASSIC_PENDULUM = 1, CLASSIC_INVERTED_PENDULUM = 2, CLASSIC_INVERTED_DOUBLE_PENDULUM = 3 };
 
 struct CartPoleC {
   static constexpr double gravity = 9.8, masscart = 1.0, masspole = 0.1, length = 0.5, force_mag = 10.0, tau = 0.02;
@@ -230,4 +233,331 @@ __global__ __launch_bounds__(256) void k_pendulum_reset(double* qpos, double* qv
   }
   ep_len[env] = 0; ep_ret[env] = 0.0;
   qpos[env] = th; qvel[env] = thd;
+}
+
+// ------------------------------------------------------------------------------------------------ cart + chain of poles
+// InvertedPendulum (NP = 1) and InvertedDoublePendulum (NP = 2): gym 0.22's task rules on this repository's own rigid-body dynamics, in
+// the form of oracle/planar_env.py for another tree — DoF 0 slides the cart along x, DoF k >= 1 is the hinge of pole k:
+//   M(q) qdd + c(q, qd) = tau + J^T f,  M = sum_b m_b Jc_b^T Jc_b + I_b Jphi_b^T Jphi_b + diag(armature),
+//   tau = gear * ctrl (slide only) - damping * qd,  gravity (0, -g),
+// one unilateral soft row per violated joint limit (planar_env.py's impedance / aref / R rule, projected Gauss-Seidel), classic RK4 with
+// the constraint solve inside every stage, frame_skip substeps.  M is 2x2 or 3x3: it, its Cholesky factor and the two possible rows
+// (DoF 0 and DoF 1) live in registers, every index is a compile-time constant.  The constants come by value as a kernel argument.
+struct CartChainDev {
+  int frame_skip, pgs_iters, limited[2];
+  double mass[3], inertia[3], com[3][2], anchor[3][2], armature[3], damping[3], range[2][2], tip[2];
+  double gear, jsign, timestep, gravity, solimp[3], lim_b, lim_k;   // lim_b = 2 / (dmax tc), lim_k = 1 / (dmax^2 tc^2 dr^2)
+  float ctrl_lo, ctrl_hi;
+};
+
+// NormalizedBoxEnv.step on float32 arrays: lb + (a + 1.0) * 0.5 * (ub - lb), one rounding per operation, then np.clip (a NaN stays a NaN)
+__device__ __forceinline__ float cartchain_ctrl(float a, float lb, float ub) {
+  const float s = lb + ((a + 1.0f) * 0.5f) * (ub - lb);
+  return s < lb ? lb : (s > ub ? ub : s);
+}
+
+// x = M^-1 b from the lower Cholesky factor L of M (forward, then backward substitution)
+template <int N>
+__device__ __forceinline__ void cartchain_chol_solve(const double (&L)[N][N], const double (&b)[N], double (&x)[N]) {
+  double y[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double s = b[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+    y[i] = s / L[i][i];
+  }
+#pragma unroll
+  for (int i = N - 1; i >= 0; --i) {
+    double s = y[i];
+#pragma unroll
+    for (int k = i + 1; k < N; ++k) s -= L[k][i] * x[k];
+    x[i] = s / L[i][i];
+  }
+}
+
+// qacc = f(q, v, tau0) with the limit rows solved; qfrc = J^T f, the constraint force in joint space
+template <int NP>
+__device__ void cartchain_dynamics(const CartChainDev& m, const double (&q)[NP + 1], const double (&v)[NP + 1], double tau0,
+                                   double (&qacc)[NP + 1], double (&qfrc)[NP + 1]) {
+  constexpr int N = NP + 1;
+  const double js = m.jsign;
+  // ---- kinematics: (jx, jz)[b] = COM Jacobian of pole b + 1 (column j = jsign * perp(lever about hinge j)), jp[b] its angular Jacobian,
+  // (fx, fz)[b] = m_b (g - acceleration of the COM at qdd = 0)
+  double jx[NP][N], jz[NP][N], jp[NP][N], fx[NP], fz[NP];
+  {
+    double s1, c1;
+    const double w1 = js * v[1];
+    sincos(js * q[1], &s1, &c1);
+    const double d1x = c1 * m.com[1][0] - s1 * m.com[1][1], d1z = s1 * m.com[1][0] + c1 * m.com[1][1];
+    jx[0][0] = 1.0; jz[0][0] = 0.0; jp[0][0] = 0.0;
+    jx[0][1] = -js * d1z; jz[0][1] = js * d1x; jp[0][1] = js;
+    if constexpr (NP == 2) { jx[0][2] = 0.0; jz[0][2] = 0.0; jp[0][2] = 0.0; }
+    // acceleration of the COM at qdd = 0 is -w^2 * lever; force m (g - acc)
+    fx[0] = m.mass[1] * (0.0 - (-(w1 * w1) * d1x));
+    fz[0] = m.mass[1] * (-m.gravity - (-(w1 * w1) * d1z));
+    if constexpr (NP == 2) {
+      double s2, c2;
+      const double w2 = w1 + js * v[2];
+      sincos(js * q[1] + js * q[2], &s2, &c2);
+      const double ex = c1 * m.anchor[2][0] - s1 * m.anchor[2][1], ez = s1 * m.anchor[2][0] + c1 * m.anchor[2][1];
+      const double d2x = c2 * m.com[2][0] - s2 * m.com[2][1], d2z = s2 * m.com[2][0] + c2 * m.com[2][1];
+      jx[1][0] = 1.0; jz[1][0] = 0.0; jp[1][0] = 0.0;
+      jx[1][1] = -js * (ez + d2z); jz[1][1] = js * (ex + d2x); jp[1][1] = js;
+      jx[1][2] = -js * d2z; jz[1][2] = js * d2x; jp[1][2] = js;
+      const double ax = -(w1 * w1) * ex - (w2 * w2) * d2x, az = -(w1 * w1) * ez - (w2 * w2) * d2z;
+      fx[1] = m.mass[2] * (0.0 - ax);
+      fz[1] = m.mass[2] * (-m.gravity - az);
+    }
+  }
+  // ---- mass matrix (lower triangle) and right-hand side
+  double M[N][N], rhs[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    rhs[i] = 0.0;
+#pragma unroll
+    for (int k = 0; k <= i; ++k) M[i][k] = 0.0;
+  }
+  M[0][0] = m.mass[0];
+#pragma unroll
+  for (int b = 0; b < NP; ++b) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      rhs[i] += jx[b][i] * fx[b] + jz[b][i] * fz[b];
+#pragma unroll
+      for (int k = 0; k <= i; ++k) M[i][k] += m.mass[b + 1] * (jx[b][i] * jx[b][k] + jz[b][i] * jz[b][k]) + m.inertia[b + 1] * jp[b][i] * jp[b][k];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) { M[i][i] += m.armature[i]; rhs[i] -= m.damping[i] * v[i]; }
+  rhs[0] += tau0;
+  // ---- Cholesky M = L L^T, in place
+  double L[N][N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int k = 0; k <= i; ++k) {
+      double s = M[i][k];
+#pragma unroll
+      for (int j = 0; j < k; ++j) s -= L[i][j] * L[k][j];
+      L[i][k] = (i == k) ? sqrt(s) : s / L[k][k];
+    }
+#pragma unroll
+    for (int k = i + 1; k < N; ++k) L[i][k] = 0.0;
+  }
+  double qacc0[N];
+  cartchain_chol_solve<N>(L, rhs, qacc0);
+  // ---- limit rows: DoF 0, then DoF 1 (J = sg * e_j, r = distance to the limit, negative when violated)
+  bool on[2];
+  double sg[2], r[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    on[j] = false; sg[j] = 0.0; r[j] = 0.0;
+    if (m.limited[j]) {
+      if (q[j] - m.range[j][0] < 0.0) { on[j] = true; sg[j] = 1.0; r[j] = q[j] - m.range[j][0]; }
+      else if (m.range[j][1] - q[j] < 0.0) { on[j] = true; sg[j] = -1.0; r[j] = m.range[j][1] - q[j]; }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) { qacc[i] = qacc0[i]; qfrc[i] = 0.0; }
+  if (!on[0] && !on[1]) return;
+  double u[2][N], e[N];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) e[i] = (i == j) ? 1.0 : 0.0;
+    cartchain_chol_solve<N>(L, e, u[j]);
+  }
+  const double a01 = (sg[0] * sg[1]) * u[0][1];
+  double den[2], rc[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const double ajj = u[j][j];
+    const double d = impedance_d(fabs(r[j]), m.solimp);
+    const double aref = -m.lim_b * (sg[j] * v[j]) - m.lim_k * d * r[j];
+    den[j] = ajj + (1.0 - d) / d * ajj;
+    rc[j] = aref - sg[j] * qacc0[j];
+  }
+  double f0 = 0.0, f1 = 0.0;
+#pragma unroll 1
+  for (int it = 0; it < m.pgs_iters; ++it) {
+    if (on[0]) f0 = fmax((rc[0] - a01 * f1) / den[0], 0.0);
+    if (on[1]) f1 = fmax((rc[1] - a01 * f0) / den[1], 0.0);
+  }
+  const double g0 = sg[0] * f0, g1 = sg[1] * f1;
+#pragma unroll
+  for (int i = 0; i < N; ++i) qacc[i] = qacc0[i] + (u[0][i] * g0 + u[1][i] * g1);
+  qfrc[0] = g0; qfrc[1] = g1;
+}
+
+// classic RK4 on (q, qd), env_substep's form: ONE dynamics call site in a 4-trip loop, sums in the order q + h/6 (k1 + 2 k2 + 2 k3 + k4).
+// qfrc is left holding the constraint force of the last stage.
+template <int NP>
+__device__ __forceinline__ void cartchain_substep(const CartChainDev& m, double (&q)[NP + 1], double (&v)[NP + 1], double tau0,
+                                                  double (&qfrc)[NP + 1]) {
+  constexpr int N = NP + 1;
+  const double h = m.timestep;
+  double qs[N], vs[N], qsum[N], vsum[N], a[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { qs[i] = q[i]; vs[i] = v[i]; qsum[i] = 0.0; vsum[i] = 0.0; }
+#pragma unroll 1
+  for (int stage = 0; stage < 4; ++stage) {
+    cartchain_dynamics<NP>(m, qs, vs, tau0, a, qfrc);
+    const double w = (stage == 1 || stage == 2) ? 2.0 : 1.0;
+    const double ch = (stage == 2) ? h : 0.5 * h;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      qsum[i] = stage == 0 ? vs[i] : qsum[i] + w * vs[i];
+      vsum[i] = stage == 0 ? a[i] : vsum[i] + w * a[i];
+      const double vn = v[i] + ch * a[i];
+      qs[i] = q[i] + ch * vs[i];
+      vs[i] = vn;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const double qn = q[i] + h / 6.0 * qsum[i];
+    const double vn = v[i] + h / 6.0 * vsum[i];
+    q[i] = qn; v[i] = vn;
+  }
+}
+
+template <int NP> struct CartChainDims { static constexpr int N = NP + 1, O = NP == 1 ? 4 : 11; };
+
+__device__ __forceinline__ float cartchain_clip10(double x) { return (float)(x < -10.0 ? -10.0 : (x > 10.0 ? 10.0 : x)); }   // np.clip: NaN stays
+
+// _get_obs(): InvertedPendulum (qpos | qvel); InvertedDoublePendulum (x, sin th, cos th, clip(qvel, +-10), clip(qfrc_constraint, +-10))
+template <int NP>
+__device__ __forceinline__ void cartchain_write_obs(const double (&q)[NP + 1], const double (&v)[NP + 1], const double (&qfrc)[NP + 1], float* dst) {
+  if constexpr (NP == 1) {
+    dst[0] = (float)q[0]; dst[1] = (float)q[1]; dst[2] = (float)v[0]; dst[3] = (float)v[1];
+  } else {
+    dst[0] = (float)q[0];
+    dst[1] = (float)sin(q[1]); dst[2] = (float)sin(q[2]);
+    dst[3] = (float)cos(q[1]); dst[4] = (float)cos(q[2]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { dst[5 + i] = cartchain_clip10(v[i]); dst[8 + i] = cartchain_clip10(qfrc[i]); }
+  }
+}
+
+// reset_model(): InvertedPendulum init + U(+-0.01) on qpos and qvel (counters 0..3 of the env's Philox stream); InvertedDoublePendulum
+// qpos = init + U(+-0.1) (counters 0..2), qvel = 0.1 * randn by env_reset_state's Box-Muller draw (counters 3 + 2 i, 4 + 2 i)
+template <int NP>
+__device__ __forceinline__ void cartchain_reset_state(uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, double (&q)[NP + 1],
+                                                      double (&v)[NP + 1]) {
+  constexpr int N = NP + 1;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    if constexpr (NP == 1) {
+      q[i] = -0.01 + 0.02 * env_uniform(seed, stream, step, env, i);
+      v[i] = -0.01 + 0.02 * env_uniform(seed, stream, step, env, N + i);
+    } else {
+      q[i] = -0.1 + 0.2 * env_uniform(seed, stream, step, env, i);
+      const double u1 = env_uniform(seed, stream, step, env, N + 2 * i), u2 = env_uniform(seed, stream, step, env, N + 2 * i + 1);
+      v[i] = 0.1 * (sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+    }
+  }
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void k_cartchain_step(const EnvStepArgs A, const CartChainDev m) {
+  constexpr int N = CartChainDims<NP>::N, O = CartChainDims<NP>::O;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= A.n_ids) return;
+  const int env = A.ids ? A.ids[t] : t;
+  if (A.frozen && A.frozen[env]) return;
+  const size_t ne = (size_t)A.n_env;
+  double q[N], v[N], qfrc[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { q[i] = A.qpos[i * ne + env]; v[i] = A.qvel[i * ne + env]; qfrc[i] = 0.0; }
+  float obs_before[O];
+  if (A.replay) {
+    cartchain_write_obs<NP>(q, v, qfrc, obs_before);
+    // the constraint force belongs to the step that produced the state: the columns the env showed for it (0 after a reset)
+    if constexpr (NP == 2)
+      if (A.obs_cur)
+        for (int i = 0; i < 3; ++i) obs_before[8 + i] = A.obs_cur[(size_t)env * O + 8 + i];
+  }
+  const float av = A.act[t];
+  const double tau0 = m.gear * (double)cartchain_ctrl(av, m.ctrl_lo, m.ctrl_hi);
+#pragma unroll 1
+  for (int s = 0; s < m.frame_skip; ++s) cartchain_substep<NP>(m, q, v, tau0, qfrc);
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < N; ++i) finite = finite && isfinite(q[i]) && isfinite(v[i]);
+  bool done;
+  double reward;
+  if constexpr (NP == 1) {
+    reward = 1.0;
+    done = !finite || fabs(q[1]) > 0.2;
+  } else {
+    // tip site of pole 2: cart + hinge 2 (pole 1's frame) + site (pole 2's frame)
+    const double p1 = m.jsign * q[1], p2 = m.jsign * q[1] + m.jsign * q[2];
+    const double s1 = sin(p1), c1 = cos(p1), s2 = sin(p2), c2 = cos(p2);
+    const double xt = q[0] + (c1 * m.anchor[2][0] - s1 * m.anchor[2][1]) + (c2 * m.tip[0] - s2 * m.tip[1]);
+    const double yt = (s1 * m.anchor[2][0] + c1 * m.anchor[2][1]) + (s2 * m.tip[0] + c2 * m.tip[1]);
+    const double dist_penalty = 0.01 * (xt * xt) + (yt - 2.0) * (yt - 2.0);
+    const double vel_penalty = 1e-3 * (v[1] * v[1]) + 5e-3 * (v[2] * v[2]);
+    reward = 10.0 - dist_penalty - vel_penalty;
+    done = yt <= 1.0;
+  }
+  float ob[O];
+  cartchain_write_obs<NP>(q, v, qfrc, ob);
+  if (A.obs) for (int i = 0; i < O; ++i) A.obs[(size_t)t * O + i] = ob[i];
+  if (A.rew) A.rew[t] = (float)reward;
+  if (A.done) A.done[t] = done ? 1 : 0;
+  if (A.replay) {   // fused replay insert (k_env_step's record layout with a 1-wide action column); the unmapped action
+    long long slot = A.top + env;
+    if (slot >= A.cap) slot -= A.cap;
+    float* rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
+    for (int i = 0; i < O; ++i) rec[i] = obs_before[i];
+    rec[O] = A.rec_act ? A.rec_act[t] : av;
+    rec[O + 1] = (float)reward;
+    rec[O + 2] = (done && !A.no_terminal) ? 1.0f : 0.0f;
+    for (int i = 0; i < O; ++i) rec[O + 3 + i] = ob[i];
+    rec[2 * O + 3] = 0.0f; rec[2 * O + 4] = 0.0f;   // absorbing = [0, 0]
+  }
+  if (A.auto_reset) {
+    const int len = A.ep_len[env] + 1;
+    const double ret = A.ep_ret[env] + reward;
+    const bool end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // as k_env_step
+    if (end) {
+      atomicAdd(&A.stats[0], 1.0);
+      atomicAdd(&A.stats[1], ret);
+      cartchain_reset_state<NP>(A.seed, A.stream, A.step, (uint32_t)env, q, v);
+#pragma unroll
+      for (int i = 0; i < N; ++i) qfrc[i] = 0.0;
+      cartchain_write_obs<NP>(q, v, qfrc, ob);
+    }
+    A.ep_len[env] = end ? 0 : len;
+    A.ep_ret[env] = end ? 0.0 : ret;
+    if (A.flush_len) A.flush_len[env] = end ? (len | ((done && !A.no_terminal) ? (1 << 30) : 0)) : 0;
+  }
+  if (A.obs_cur) for (int i = 0; i < O; ++i) A.obs_cur[(size_t)env * O + i] = ob[i];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { A.qpos[i * ne + env] = q[i]; A.qvel[i * ne + env] = v[i]; }
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void k_cartchain_reset(double* qpos, double* qvel, int n_env, const int* ids, int n_ids, float* obs,
+                                                         float* obs_cur, int* ep_len, double* ep_ret, uint64_t seed, uint32_t stream,
+                                                         unsigned long long step) {
+  constexpr int N = CartChainDims<NP>::N, O = CartChainDims<NP>::O;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_ids) return;
+  const int env = ids ? ids[t] : t;
+  double q[N], v[N], qfrc[N];
+  cartchain_reset_state<NP>(seed, stream, step, (uint32_t)env, q, v);
+#pragma unroll
+  for (int i = 0; i < N; ++i) qfrc[i] = 0.0;
+  float ob[O];
+  cartchain_write_obs<NP>(q, v, qfrc, ob);
+  for (int i = 0; i < O; ++i) {
+    if (obs) obs[(size_t)t * O + i] = ob[i];
+    if (obs_cur) obs_cur[(size_t)env * O + i] = ob[i];
+  }
+  ep_len[env] = 0; ep_ret[env] = 0.0;
+  const size_t ne = (size_t)n_env;
+#pragma unroll
+  for (int i = 0; i < N; ++i) { qpos[i * ne + env] = q[i]; qvel[i * ne + env] = v[i]; }
 }

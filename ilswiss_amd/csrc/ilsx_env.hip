@@ -65,6 +65,7 @@ struct ilsx_vecenv {
   // 3-D engine (Ant / Humanoid, env3d.h): model, its device copy, and the per-env working set [E3Off::TOTAL][n_env]
   int engine = 0, nq = 0, nv = 0;   // engine: 0 planar, 1 3-D, 2 classic control (classic_env.h)
   int classic = -1, discrete_n = 0;  // engine 2: ILSX_CLASSIC_* task and the size of its Discrete action space (0 = Box actions)
+  struct CartChainDev* cc = nullptr; // engine 2, InvertedPendulum / InvertedDoublePendulum: the constants k_cartchain_step takes by value
   bool wave3 = true;   // wave-per-env kernels (env3d_wave.h); ILSX_ENV3D_LANE=1 selects the lane-per-env form (env3d.h) for A/B runs
   Spatial3Dev* hm3 = nullptr; Spatial3Dev* dm3 = nullptr; double* scr3 = nullptr;
   const float* policy_obs() const { return norm_obs ? obs_n : obs_cur; }
@@ -862,6 +863,10 @@ static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
     ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
     if (e->classic == ILSX_CLASSIC_PENDULUM)
       ILSX_LAUNCH(ps, k_pendulum_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
+    else if (e->classic == ILSX_CLASSIC_INVERTED_PENDULUM)
+      ILSX_LAUNCH(ps, k_cartchain_step<1>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->cc);
+    else if (e->classic == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM)
+      ILSX_LAUNCH(ps, k_cartchain_step<2>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->cc);
     else
       ILSX_LAUNCH(ps, k_cartpole_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
     HIPCHK(hipGetLastError());
@@ -895,6 +900,16 @@ static int launch_env_reset(ilsx_vecenv* e, const int* ids_dev, int n_ids, float
   if (e->engine == 2 && e->classic == ILSX_CLASSIC_PENDULUM) {
     hipLaunchKernelGGL(k_pendulum_reset, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, ids_dev, n_ids, obs,
                        e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
+    HIPCHK(hipGetLastError());
+    return ILSX_OK;
+  }
+  if (e->engine == 2 && (e->classic == ILSX_CLASSIC_INVERTED_PENDULUM || e->classic == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM)) {
+    if (e->classic == ILSX_CLASSIC_INVERTED_PENDULUM)
+      hipLaunchKernelGGL(k_cartchain_reset<1>, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids,
+                         obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
+    else
+      hipLaunchKernelGGL(k_cartchain_reset<2>, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids,
+                         obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
     HIPCHK(hipGetLastError());
     return ILSX_OK;
   }
@@ -1057,17 +1072,22 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
   *out = e;
   return ILSX_OK;
 }
-// Classic control (classic_env.h): CartPole and Pendulum, one lane per env, the same handle and protocol entry points as the other engines.
-extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out) {
-  if (!ctx || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_classic: bad argument");
-  if (kind != ILSX_CLASSIC_CARTPOLE && kind != ILSX_CLASSIC_PENDULUM)
-    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_classic: unknown kind %d", kind);
+// Classic control (classic_env.h): CartPole, Pendulum and the cart-and-poles tasks, one lane per env, the same handle and protocol entry
+// points as the other engines.  cc != null: InvertedPendulum / InvertedDoublePendulum with these constants.
+static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n_env, uint64_t seed, ilsx_vecenv** out) {
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_vecenv* e = new ilsx_vecenv();
+  struct Guard {   // every early return below gives back what was allocated so far (the handle, its buffers, the constants)
+    ilsx_vecenv* e;
+    ~Guard() { if (e) ilsx_vecenv_destroy(e); }
+  } guard{e};
   e->ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++; e->engine = 2;
   e->classic = kind;
   if (kind == ILSX_CLASSIC_PENDULUM) { e->discrete_n = 0; e->n = 1; e->nq = 1; e->nv = 1; e->o = 3; e->a = 1; }   // Box(-1, 1) actions
+  else if (kind == ILSX_CLASSIC_INVERTED_PENDULUM) { e->discrete_n = 0; e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1; }
+  else if (kind == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM) { e->discrete_n = 0; e->n = 3; e->nq = 3; e->nv = 3; e->o = 11; e->a = 1; }
   else { e->discrete_n = 2; e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1; }
+  if (cc) e->cc = new CartChainDev(*cc);
   const size_t N = (size_t)n_env;
   int rc = ctx_alloc(ctx, N * e->nq * 8, (void**)&e->qpos);
   if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->nv * 8, (void**)&e->qvel);
@@ -1082,7 +1102,7 @@ extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, ui
   if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 8, (void**)&e->ep_ret);
   if (rc == ILSX_OK) rc = ctx_alloc(ctx, 4 * 8, (void**)&e->stats);
   if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ids);
-  if (rc != ILSX_OK) { delete e; return rc; }
+  if (rc != ILSX_OK) return rc;
   {
     ObsRms h;   // RunningMeanStd(): mean 0, var 1, count 0 (normalizer.py:133-136)
     for (int i = 0; i < ENV_MAX_OBS; ++i) { h.mean[i] = 0.0; h.var[i] = 1.0; h.count[i] = 0.0; }
@@ -1090,8 +1110,91 @@ extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, ui
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   ILSX_TRY(launch_env_reset(e, nullptr, n_env, nullptr));
+  guard.e = nullptr;
   *out = e;
   return ILSX_OK;
+}
+
+// MuJoCo's capsule rule as ilswiss_amd/envs/models.py states it (capsule_mass_inertia): m = rho pi r^2 (L + r), inertia about the COM
+static void cartchain_capsule(double L, double r, double* mass, double* inertia) {
+  const double rho = 1000.0, pi = 3.141592653589793;
+  const double m_c = rho * pi * r * r * L, m_s = rho * pi * (r * r * r);
+  *mass = m_c + m_s;
+  *inertia = m_c * (L * L / 12.0 + r * r / 4.0) + m_s * (2.0 * r * r / 5.0 + L * L / 4.0 + 3.0 * L * r / 8.0);
+}
+
+// The built-in constants: the values of ilswiss_amd/envs/models_cartchain.py (gym 0.22's inverted_pendulum.xml / inverted_double_pendulum.xml
+// as authored there, UNVERIFIED against MuJoCo)
+static void cartchain_defaults(int n_pole, ilsx_cartchain_model* m) {
+  memset(m, 0, sizeof *m);
+  const double pi = 3.141592653589793;
+  m->n_pole = n_pole; m->pgs_iters = 30; m->gravity = 9.81; m->jsign = -1.0;
+  m->limit_solref[0] = 0.02; m->limit_solref[1] = 1.0;
+  m->limit_solimp[0] = 0.9; m->limit_solimp[1] = 0.95; m->limit_solimp[2] = 0.001;
+  cartchain_capsule(0.2, 0.1, &m->mass[0], &m->inertia[0]);   // cart: capsule of radius 0.1, half-length 0.1 along x, COM at its origin
+  m->limited[0] = 1; m->range[0][0] = -1.0; m->range[0][1] = 1.0;
+  if (n_pole == 1) {
+    m->timestep = 0.02; m->frame_skip = 2; m->gear = 100.0; m->ctrl_range[0] = -3.0; m->ctrl_range[1] = 3.0;
+    cartchain_capsule(hypot(0.001, 0.6), 0.049, &m->mass[1], &m->inertia[1]);
+    m->com[1][0] = 0.5 * 0.001; m->com[1][1] = 0.5 * 0.6;
+    m->tip[0] = 0.001; m->tip[1] = 0.6;
+    m->damping[0] = m->damping[1] = 1.0;
+    m->limited[1] = 1; m->range[1][0] = -90.0 * (pi / 180.0); m->range[1][1] = 90.0 * (pi / 180.0);
+  } else {
+    m->timestep = 0.01; m->frame_skip = 5; m->gear = 500.0; m->ctrl_range[0] = -1.0; m->ctrl_range[1] = 1.0;
+    for (int k = 1; k <= 2; ++k) {
+      cartchain_capsule(0.6, 0.045, &m->mass[k], &m->inertia[k]);
+      m->com[k][0] = 0.0; m->com[k][1] = 0.5 * 0.6;
+    }
+    m->anchor[2][0] = 0.0; m->anchor[2][1] = 0.6;
+    m->tip[0] = 0.0; m->tip[1] = 0.6;
+    m->damping[0] = m->damping[1] = m->damping[2] = 0.05;
+  }
+}
+
+extern "C" int ilsx_vecenv_create_cartchain(ilsx_ctx* ctx, const ilsx_cartchain_model* pm, int n_env, uint64_t seed, ilsx_vecenv** out) {
+  if (!ctx || !pm || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_cartchain: bad argument");
+  if (pm->n_pole != 1 && pm->n_pole != 2) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "n_pole=%d: kernels exist for 1 and 2 poles", pm->n_pole);
+  const int n = pm->n_pole + 1;
+  if (pm->frame_skip < 1 || pm->pgs_iters < 1 || !(pm->timestep > 0.0)) ILSX_FAIL(ILSX_ERR_ARG, "cartchain: frame_skip, pgs_iters and timestep must be positive");
+  if (pm->n_pole == 2 && pm->limited[2]) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "cartchain: the kernel solves limit rows on DoF 0 and DoF 1 only");
+  if (!(pm->ctrl_range[0] < pm->ctrl_range[1])) ILSX_FAIL(ILSX_ERR_ARG, "cartchain: empty ctrl_range");
+  if (!(pm->limit_solref[0] > 0.0) || !(pm->limit_solref[1] > 0.0) || !(pm->limit_solimp[0] > 0.0) || !(pm->limit_solimp[1] > 0.0))
+    ILSX_FAIL(ILSX_ERR_ARG, "cartchain: limit_solref and the impedances of limit_solimp must be positive");
+  CartChainDev d;
+  memset(&d, 0, sizeof d);
+  d.frame_skip = pm->frame_skip; d.pgs_iters = pm->pgs_iters;
+  for (int i = 0; i < n; ++i) {
+    if (!(pm->mass[i] > 0.0) || pm->inertia[i] < 0.0 || pm->armature[i] < 0.0) ILSX_FAIL(ILSX_ERR_ARG, "cartchain: body %d needs mass > 0, inertia >= 0, armature >= 0", i);
+    d.mass[i] = pm->mass[i]; d.inertia[i] = pm->inertia[i]; d.armature[i] = pm->armature[i]; d.damping[i] = pm->damping[i];
+    for (int k = 0; k < 2; ++k) { d.com[i][k] = pm->com[i][k]; d.anchor[i][k] = pm->anchor[i][k]; }
+    if (i < 2) {
+      d.limited[i] = pm->limited[i] != 0;
+      d.range[i][0] = pm->range[i][0]; d.range[i][1] = pm->range[i][1];
+      if (d.limited[i] && !(d.range[i][0] < d.range[i][1])) ILSX_FAIL(ILSX_ERR_ARG, "cartchain: DoF %d is limited to an empty range", i);
+    }
+  }
+  if (pm->anchor[1][0] != 0.0 || pm->anchor[1][1] != 0.0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "cartchain: hinge 1 sits at the cart's origin");
+  d.tip[0] = pm->tip[0]; d.tip[1] = pm->tip[1];
+  d.gear = pm->gear; d.jsign = pm->jsign; d.timestep = pm->timestep; d.gravity = pm->gravity;
+  for (int k = 0; k < 3; ++k) d.solimp[k] = pm->limit_solimp[k];
+  const double tc = pm->limit_solref[0], dr = pm->limit_solref[1], dmax = pm->limit_solimp[1];
+  d.lim_b = 2.0 / (dmax * tc);
+  d.lim_k = 1.0 / (dmax * dmax * tc * tc * dr * dr);
+  d.ctrl_lo = (float)pm->ctrl_range[0]; d.ctrl_hi = (float)pm->ctrl_range[1];
+  return create_classic(ctx, pm->n_pole == 1 ? ILSX_CLASSIC_INVERTED_PENDULUM : ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM, &d, n_env, seed, out);
+}
+
+extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out) {
+  if (!ctx || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_classic: bad argument");
+  if (kind == ILSX_CLASSIC_INVERTED_PENDULUM || kind == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM) {
+    ilsx_cartchain_model m;
+    cartchain_defaults(kind == ILSX_CLASSIC_INVERTED_PENDULUM ? 1 : 2, &m);
+    return ilsx_vecenv_create_cartchain(ctx, &m, n_env, seed, out);
+  }
+  if (kind != ILSX_CLASSIC_CARTPOLE && kind != ILSX_CLASSIC_PENDULUM)
+    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_classic: unknown kind %d", kind);
+  return create_classic(ctx, kind, nullptr, n_env, seed, out);
 }
 extern "C" int ilsx_vecenv_action_space(const ilsx_vecenv* e, int* discrete_n) {
   if (!e || !discrete_n) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_action_space: NULL argument");
@@ -1118,6 +1221,7 @@ extern "C" int ilsx_vecenv_destroy(ilsx_vecenv* e) {
   if (e->grp_flush_host) hipHostFree(e->grp_flush_host);
   if (e->grp_flush_dev) ctx_free(e->ctx, e->grp_flush_dev);
   delete e->hm3;
+  delete e->cc;
   delete e;
   return ILSX_OK;
 }

@@ -13,6 +13,7 @@ from .. import _lib
 from ..device import as_dev, get_context, host_ptr
 from .models import MODELS
 from .models3d import MODELS3D
+from .models_cartchain import MODELS_CARTCHAIN
 
 
 class Box:  # minimal gym.spaces.Box stand-in (gym is not installed here)
@@ -43,6 +44,11 @@ class Discrete:  # minimal gym.spaces.Discrete stand-in: n actions {0, ..., n-1}
 # CartPoleEnv, what rlkit/envs/envs_dict.py:2 maps the name to; `pendulum` is gym 0.22's PendulumEnv behind NormalizedBoxEnv (Box(-1, 1)
 # actions of width 1, 3-wide observations).
 CLASSIC = {"cartpole": 0, "pendulum": 1}
+# the cart-and-poles tasks of the same engine (k_cartchain_step; ILSX_CLASSIC_INVERTED_PENDULUM / _INVERTED_DOUBLE_PENDULUM), under the
+# envs_dict spellings.  Unlike the two above they carry a model description (models_cartchain.py), which HipVectorEnv always passes to
+# the library (ilsx_vecenv_create_cartchain), so they are listed apart; CLASSIC_KINDS holds every name of the engine.
+CARTCHAIN = {"invertedpendulum": 2, "inverteddoublependulum": 3}
+CLASSIC_KINDS = {**CLASSIC, **CARTCHAIN}
 
 
 def model_struct(m):
@@ -71,6 +77,23 @@ def model_struct(m):
     for i, v in enumerate(m["init_qpos"]):
         s.init_qpos[i] = v
     s.reset_noise_vel_std, s.qvel_clip, s.max_rows = m.get("reset_noise_vel_std", 0.0), m.get("qvel_clip", 10.0), m.get("max_rows", 0)
+    return s
+
+
+def cartchain_struct(m):
+    """models_cartchain dict -> ilsx_cartchain_model (include/ilsx.h)."""
+    s = _lib.CartChainModel()
+    s.n_pole, s.frame_skip, s.pgs_iters = m["n_pole"], m["frame_skip"], m["pgs_iters"]
+    for i in range(m["n_pole"] + 1):
+        s.limited[i], s.mass[i], s.inertia[i] = m["limited"][i], m["mass"][i], m["inertia"][i]
+        s.armature[i], s.damping[i] = m["armature"][i], m["damping"][i]
+        for k in (0, 1):
+            s.com[i][k], s.anchor[i][k], s.range[i][k] = m["com"][i][k], m["anchor"][i][k], m["range"][i][k]
+    for k in (0, 1):
+        s.tip[k], s.ctrl_range[k], s.limit_solref[k] = m["tip"][k], m["ctrl_range"][k], m["limit_solref"][k]
+    for k in (0, 1, 2):
+        s.limit_solimp[k] = m["limit_solimp"][k]
+    s.gear, s.jsign, s.timestep, s.gravity = m["gear"], m["jsign"], m["timestep"], m["gravity"]
     return s
 
 
@@ -173,7 +196,16 @@ class HipVectorEnv:
         self.env_name = env_name
         self.env_num = int(env_num)
         self.h = C.c_void_p()
-        if env_name in CLASSIC:         # classic-control engine (CartPole, Pendulum)
+        if env_name in CARTCHAIN:       # classic-control engine, cart and poles: the constants always come from the model description
+            if obs_shift is not None:
+                raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for classic-control tasks")
+            self.cartchain_model = model or MODELS_CARTCHAIN[env_name]()
+            if self.cartchain_model["n_pole"] != CARTCHAIN[env_name] - 1:
+                raise ValueError(f"{env_name}: the model has {self.cartchain_model['n_pole']} pole(s)")
+            self.model = None
+            ms = cartchain_struct(self.cartchain_model)
+            _lib.check(self.ctx.lib.ilsx_vecenv_create_cartchain(self.ctx.h, C.byref(ms), self.env_num, C.c_uint64(seed), C.byref(self.h)))
+        elif env_name in CLASSIC:       # classic-control engine (CartPole, Pendulum)
             if model is not None:
                 raise ValueError(f"{env_name}: a classic-control task has no model description")
             if obs_shift is not None:

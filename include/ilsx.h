@@ -616,9 +616,36 @@ int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_model* model, i
  * + 0.1 theta_dot^2 + 0.001 u^2) of the state before the step; theta_dot' = clip(theta_dot + (15 sin theta + 3 u) * 0.05, +-8), theta' =
  * theta + theta_dot' * 0.05; never done (max_path_length ends episodes); reset: theta ~ U[-pi, pi), theta_dot ~ U[-1, 1).  The replay
  * record holds the action as the policy gave it, before the map.
+ * ILSX_CLASSIC_INVERTED_PENDULUM / ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM — gym 0.22's InvertedPendulumEnv / InvertedDoublePendulumEnv
+ * (envs_dict `invertedpendulum` / `inverteddoublependulum`) behind NormalizedBoxEnv, on this library's own rigid-body dynamics of a cart
+ * on a rail carrying 1 or 2 poles (ilsx_cartchain_model below; no MuJoCo): float64 state qpos = (x, theta_1[, theta_2]), qvel likewise
+ * (nq = nv = 2 or 3), RK4 with a soft joint-limit solve in every stage, frame_skip substeps; Box(-1, 1) actions of width 1, ctrl =
+ * clip(lb + (a + 1) * 0.5 * (ub - lb), lb, ub) in float32.  InvertedPendulum: observation float32 (qpos | qvel), reward 1, done = a
+ * non-finite state or |theta| > 0.2, reset = U(+-0.01) on qpos and qvel.  InvertedDoublePendulum: observation float32 (x, sin theta_1,
+ * sin theta_2, cos theta_1, cos theta_2, clip(qvel, +-10), clip(qfrc_constraint, +-10)) (11 wide, the layout
+ * ILSX_TERM_INVERTED_DOUBLE_PENDULUM reads), qfrc_constraint = J^T f of the last RK4 stage of the last substep (0 after a reset),
+ * reward = 10 - (0.01 x_tip^2 + (y_tip - 2)^2) - (1e-3 qvel_1^2 + 5e-3 qvel_2^2) of the state after the step, done = y_tip <= 1, reset
+ * qpos = U(+-0.1), qvel = 0.1 N(0, 1).  ilsx_vecenv_create_classic builds them from the built-in constants (the values of
+ * ilswiss_amd/envs/models_cartchain.py); ilsx_vecenv_create_cartchain takes the constants from the caller.
  * Reset / step / rollout / evaluation entry points are the ordinary ones; ilsx_vecenv_set_obs_affine is not available. */
-enum { ILSX_CLASSIC_CARTPOLE = 0, ILSX_CLASSIC_PENDULUM = 1 };
+enum { ILSX_CLASSIC_CARTPOLE = 0, ILSX_CLASSIC_PENDULUM = 1, ILSX_CLASSIC_INVERTED_PENDULUM = 2, ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM = 3 };
 int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out);
+/* A cart on a rail (DoF 0, slide along x) carrying n_pole poles in a chain (DoF k = hinge of pole k, angle relative to its parent).
+ * Body 0 is the cart, body k pole k; a pole's absolute angle is jsign * (q_1 + ... + q_k), counter-clockwise in (x, z).  anchor[k] =
+ * hinge k in the parent's frame, com[k] = centre of mass in the body's frame, tip = the reward's site in the last pole's frame.  The
+ * actuator (gear, ctrl_range) drives the slide only.  Limits are soft unilateral rows (limit_solref = (timeconst, dampratio),
+ * limit_solimp = (d0, dmax, width)); DoF 0 and DoF 1 may be limited. */
+#define ILSX_CARTCHAIN_MAX_DOF 3
+typedef struct {
+  int n_pole, frame_skip, pgs_iters;      /* n_pole 1 (InvertedPendulum rules) or 2 (InvertedDoublePendulum rules) */
+  int limited[ILSX_CARTCHAIN_MAX_DOF];
+  double mass[ILSX_CARTCHAIN_MAX_DOF], inertia[ILSX_CARTCHAIN_MAX_DOF];   /* inertia about the COM, axis normal to the plane */
+  double com[ILSX_CARTCHAIN_MAX_DOF][2], anchor[ILSX_CARTCHAIN_MAX_DOF][2];
+  double armature[ILSX_CARTCHAIN_MAX_DOF], damping[ILSX_CARTCHAIN_MAX_DOF], range[ILSX_CARTCHAIN_MAX_DOF][2];
+  double tip[2], gear, ctrl_range[2], jsign;
+  double timestep, gravity, limit_solref[2], limit_solimp[3];
+} ilsx_cartchain_model;
+int ilsx_vecenv_create_cartchain(ilsx_ctx* ctx, const ilsx_cartchain_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
 /* discrete_n = n of a Discrete(n) action space, 0 for Box actions */
 int ilsx_vecenv_action_space(const ilsx_vecenv* env, int* discrete_n);
 /* Path mode of the fused rollout (ilsx_rollout_step with a replay ring): 0 (default) = every transition enters the ring when it

@@ -53,7 +53,12 @@ def cmd_rate(args):
     return res, "pendulum_rate.json"
 
 
-def _run_spec(spec_rel, script, seeds, epochs, out_dir, tag, serial, over=None):
+def _pendulum_fields(rets):
+    return dict(first_epoch_above_minus_1000=next((i for i, r in enumerate(rets) if r > -1000), None))
+
+
+def _run_spec(spec_rel, script, seeds, epochs, out_dir, tag, serial, over=None, prefix="pendulum", fields=_pendulum_fields):
+    """prefix: the copies of progress.csv are <prefix>_<tag>_seed<S>.csv; fields(returns) -> the task's own entries of a run's summary."""
     import yaml
     spec = yaml.safe_load(open(os.path.join(ROOT, "exp_specs", spec_rel)))
     if epochs:
@@ -82,12 +87,11 @@ def _run_spec(spec_rel, script, seeds, epochs, out_dir, tag, serial, over=None):
             if rc != 0 or not found:
                 run["tail"] = open(os.path.join(d, "stdout.txt")).read()[-2000:]
             else:
-                shutil.copy(found[0], os.path.join(out_dir, f"pendulum_{tag}_seed{seed}.csv"))
+                shutil.copy(found[0], os.path.join(out_dir, f"{prefix}_{tag}_seed{seed}.csv"))
                 rows = list(csv.DictReader(open(found[0])))
                 rets = [float(r["AverageReturn"]) for r in rows]
                 run.update(n_epochs=len(rows), wall_s_per_epoch=wall / max(1, len(rows)), last_return=rets[-1], best_return=max(rets),
-                           best_epoch=int(max(range(len(rets)), key=rets.__getitem__)), first_return=rets[0],
-                           first_epoch_above_minus_1000=next((i for i, r in enumerate(rets) if r > -1000), None))
+                           best_epoch=int(max(range(len(rets)), key=rets.__getitem__)), first_return=rets[0], **fields(rets))
             res["runs"][str(seed)] = run
 
         if serial:
