@@ -71,6 +71,20 @@ class CartChainModel(C.Structure):  # ilsx_cartchain_model
                 ("timestep", C.c_double), ("gravity", C.c_double), ("limit_solref", C.c_double * 2), ("limit_solimp", C.c_double * 3)]
 
 
+_MSL = 4            # ILSX_SWIMMER_MAX_LINK
+_MSD = _MSL + 2     # ILSX_SWIMMER_MAX_DOF
+
+
+class SwimmerModel(C.Structure):  # ilsx_swimmer_model
+    _fields_ = [("n_link", C.c_int32), ("frame_skip", C.c_int32), ("pgs_iters", C.c_int32), ("limited", C.c_int32 * _MSD),
+                ("mass", C.c_double * _MSL), ("inertia", (C.c_double * 3) * _MSL), ("box", (C.c_double * 3) * _MSL),
+                ("com", (C.c_double * 2) * _MSL), ("anchor", (C.c_double * 2) * _MSL),
+                ("armature", C.c_double * _MSD), ("damping", C.c_double * _MSD), ("range", (C.c_double * 2) * _MSD),
+                ("gear", C.c_double * _MSD), ("init_qpos", C.c_double * _MSD),
+                ("ctrl_range", C.c_double * 2), ("timestep", C.c_double), ("density", C.c_double), ("viscosity", C.c_double),
+                ("limit_solref", C.c_double * 2), ("limit_solimp", C.c_double * 3)]
+
+
 class SpatialModel(C.Structure):  # ilsx_spatial_model
     _fields_ = [("task", C.c_int32), ("n_link", C.c_int32), ("n_act", C.c_int32), ("n_contact", C.c_int32),
                 ("n_body", C.c_int32), ("frame_skip", C.c_int32), ("pgs_iters", C.c_int32), ("max_rows", C.c_int32),
@@ -337,6 +351,7 @@ PROTOTYPES = {
     "ilsx_policy_log_pis": (C.c_int, [vp, vp, C.c_int, vp]),
     "ilsx_vecenv_create_classic": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]),
     "ilsx_vecenv_create_cartchain": (C.c_int, [vp, C.POINTER(CartChainModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "ilsx_vecenv_create_swimmer": (C.c_int, [vp, C.POINTER(SwimmerModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
     "ilsx_vecenv_action_space": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "ilsx_dsac_create": (C.c_int, [vp, C.POINTER(DsacCfg), vp, vp, vp, C.POINTER(vp)]),
     "ilsx_dsac_destroy": (C.c_int, [vp]),

@@ -66,6 +66,7 @@ struct ilsx_vecenv {
   int engine = 0, nq = 0, nv = 0;   // engine: 0 planar, 1 3-D, 2 classic control (classic_env.h)
   int classic = -1, discrete_n = 0;  // engine 2: ILSX_CLASSIC_* task and the size of its Discrete action space (0 = Box actions)
   struct CartChainDev* cc = nullptr; // engine 2, InvertedPendulum / InvertedDoublePendulum: the constants k_cartchain_step takes by value
+  struct SwimmerDev* sw = nullptr;   // engine 2, classic == ILSX_SWIMMER_TASK: the constants k_swimmer_step takes by value (swimmer_env.h)
   bool wave3 = true;   // wave-per-env kernels (env3d_wave.h); ILSX_ENV3D_LANE=1 selects the lane-per-env form (env3d.h) for A/B runs
   Spatial3Dev* hm3 = nullptr; Spatial3Dev* dm3 = nullptr; double* scr3 = nullptr;
   const float* policy_obs() const { return norm_obs ? obs_n : obs_cur; }
@@ -483,6 +484,7 @@ __device__ __forceinline__ void env_reset_state(const PlanarModelDev& m, uint64_
 
 #include "env2d_group.h"
 #include "classic_env.h"
+#include "swimmer_env.h"
 #ifdef ILSX_EG_PROFILE
 extern "C" int ilsx_debug_eg_prof(unsigned long long* out16, int reset) {   // measurement build only
   if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_eg_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
@@ -867,6 +869,8 @@ static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
       ILSX_LAUNCH(ps, k_cartchain_step<1>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->cc);
     else if (e->classic == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM)
       ILSX_LAUNCH(ps, k_cartchain_step<2>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->cc);
+    else if (e->classic == ILSX_SWIMMER_TASK)
+      ILSX_LAUNCH(ps, k_swimmer_step<3>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->sw);
     else
       ILSX_LAUNCH(ps, k_cartpole_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
     HIPCHK(hipGetLastError());
@@ -910,6 +914,12 @@ static int launch_env_reset(ilsx_vecenv* e, const int* ids_dev, int n_ids, float
     else
       hipLaunchKernelGGL(k_cartchain_reset<2>, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids,
                          obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
+    HIPCHK(hipGetLastError());
+    return ILSX_OK;
+  }
+  if (e->engine == 2 && e->classic == ILSX_SWIMMER_TASK) {
+    hipLaunchKernelGGL(k_swimmer_reset<3>, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, obs,
+                       e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step, *e->sw);
     HIPCHK(hipGetLastError());
     return ILSX_OK;
   }
@@ -1073,8 +1083,9 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
   return ILSX_OK;
 }
 // Classic control (classic_env.h): CartPole, Pendulum and the cart-and-poles tasks, one lane per env, the same handle and protocol entry
-// points as the other engines.  cc != null: InvertedPendulum / InvertedDoublePendulum with these constants.
-static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n_env, uint64_t seed, ilsx_vecenv** out) {
+// points as the other engines.  cc != null: InvertedPendulum / InvertedDoublePendulum with these constants; sw != null: Swimmer with these.
+static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n_env, uint64_t seed, ilsx_vecenv** out,
+                          const SwimmerDev* sw = nullptr) {
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_vecenv* e = new ilsx_vecenv();
   struct Guard {   // every early return below gives back what was allocated so far (the handle, its buffers, the constants)
@@ -1086,8 +1097,10 @@ static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n
   if (kind == ILSX_CLASSIC_PENDULUM) { e->discrete_n = 0; e->n = 1; e->nq = 1; e->nv = 1; e->o = 3; e->a = 1; }   // Box(-1, 1) actions
   else if (kind == ILSX_CLASSIC_INVERTED_PENDULUM) { e->discrete_n = 0; e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1; }
   else if (kind == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM) { e->discrete_n = 0; e->n = 3; e->nq = 3; e->nv = 3; e->o = 11; e->a = 1; }
+  else if (kind == ILSX_SWIMMER_TASK) { e->discrete_n = 0; e->n = 5; e->nq = 5; e->nv = 5; e->o = 8; e->a = 2; }
   else { e->discrete_n = 2; e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1; }
   if (cc) e->cc = new CartChainDev(*cc);
+  if (sw) e->sw = new SwimmerDev(*sw);
   const size_t N = (size_t)n_env;
   int rc = ctx_alloc(ctx, N * e->nq * 8, (void**)&e->qpos);
   if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->nv * 8, (void**)&e->qvel);
@@ -1185,6 +1198,68 @@ extern "C" int ilsx_vecenv_create_cartchain(ilsx_ctx* ctx, const ilsx_cartchain_
   return create_classic(ctx, pm->n_pole == 1 ? ILSX_CLASSIC_INVERTED_PENDULUM : ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM, &d, n_env, seed, out);
 }
 
+// Swimmer (swimmer_env.h): the caller's model is the one source of the constants.  Every field is checked before anything is allocated;
+// create_classic gives back whatever it allocated when it fails.
+extern "C" int ilsx_vecenv_create_swimmer(ilsx_ctx* ctx, const ilsx_swimmer_model* pm, int n_env, uint64_t seed, ilsx_vecenv** out) {
+  if (!ctx || !pm || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_swimmer: bad argument");
+  if (pm->n_link != 3) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "n_link=%d: the swimmer kernels exist for 3 links", pm->n_link);
+  const int nl = pm->n_link, n = nl + 2;
+  if (pm->frame_skip < 1 || pm->pgs_iters < 1 || !(pm->timestep > 0.0)) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: frame_skip, pgs_iters and timestep must be positive");
+  if (!(pm->ctrl_range[0] < pm->ctrl_range[1])) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: empty ctrl_range");
+  if (!(pm->limit_solref[0] > 0.0) || !(pm->limit_solref[1] > 0.0) || !(pm->limit_solimp[0] > 0.0) || !(pm->limit_solimp[1] > 0.0))
+    ILSX_FAIL(ILSX_ERR_ARG, "swimmer: limit_solref and the impedances of limit_solimp must be positive");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(pm->limit_solimp[k]) || (k < 2 && !std::isfinite(pm->limit_solref[k])) || (k < 2 && !std::isfinite(pm->ctrl_range[k])))
+      ILSX_FAIL(ILSX_ERR_ARG, "swimmer: limit_solref, limit_solimp and ctrl_range must be finite");
+  if (!std::isfinite(pm->timestep) || pm->limit_solimp[2] < 0.0) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: the time step must be finite and the impedance width not negative");
+  if (!(pm->density >= 0.0) || !(pm->viscosity >= 0.0) || !std::isfinite(pm->density) || !std::isfinite(pm->viscosity))
+    ILSX_FAIL(ILSX_ERR_ARG, "swimmer: the medium's density and viscosity must be finite and not negative");
+  SwimmerDev d;
+  memset(&d, 0, sizeof d);
+  d.frame_skip = pm->frame_skip; d.pgs_iters = pm->pgs_iters;
+  const double pi = 3.141592653589793, rho = pm->density, beta = pm->viscosity;
+  for (int b = 0; b < nl; ++b) {
+    if (!(pm->mass[b] > 0.0) || !std::isfinite(pm->mass[b])) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: link %d needs a finite mass > 0", b);
+    for (int k = 0; k < 3; ++k) {
+      if (!(pm->inertia[b][k] >= 0.0) || !std::isfinite(pm->inertia[b][k])) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: link %d needs finite inertias >= 0", b);
+      if (!(pm->box[b][k] > 0.0) || !std::isfinite(pm->box[b][k])) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: link %d needs finite box sides > 0", b);
+    }
+    d.mass[b] = pm->mass[b]; d.inertia[b] = pm->inertia[b][2];
+    for (int k = 0; k < 2; ++k) {
+      if (!std::isfinite(pm->com[b][k]) || !std::isfinite(pm->anchor[b][k])) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: link %d needs a finite com and anchor", b);
+      d.com[b][k] = pm->com[b][k]; d.anchor[b][k] = pm->anchor[b][k];
+    }
+    const double bx = pm->box[b][0], by = pm->box[b][1], bz = pm->box[b][2], dd = (bx + by + bz) / 3.0;
+    d.drag[b][0] = 3.0 * pi * beta * dd;
+    d.drag[b][1] = 0.5 * rho * by * bz;
+    d.drag[b][2] = 0.5 * rho * bx * bz;
+    d.drag[b][3] = pi * beta * (dd * dd * dd);
+    d.drag[b][4] = rho * bz * (bx * bx * bx * bx + by * by * by * by) / 64.0;
+  }
+  if (pm->anchor[0][0] != 0.0 || pm->anchor[0][1] != 0.0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "swimmer: the root joints sit at the first link's origin");
+  for (int i = 0; i < n; ++i) {
+    if (!(pm->armature[i] >= 0.0) || !(pm->damping[i] >= 0.0)) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: DoF %d needs armature >= 0 and damping >= 0", i);
+    if (i < 3 && pm->limited[i]) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "swimmer: DoF %d is a root joint; only the hinges between links may be limited", i);
+    if (i < 3 && pm->gear[i] != 0.0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "swimmer: DoF %d is a root joint; the actuators drive the hinges between links", i);
+    if (!std::isfinite(pm->gear[i]) || !std::isfinite(pm->init_qpos[i])) ILSX_FAIL(ILSX_ERR_ARG, "swimmer: DoF %d needs a finite gear and init_qpos", i);
+    d.armature[i] = pm->armature[i]; d.damping[i] = pm->damping[i]; d.init_qpos[i] = pm->init_qpos[i];
+    if (i >= 3) {
+      const int j = i - 3;
+      d.limited[j] = pm->limited[i] != 0; d.gear[j] = pm->gear[i];
+      d.range[j][0] = pm->range[i][0]; d.range[j][1] = pm->range[i][1];
+      if (d.limited[j] && (!std::isfinite(d.range[j][0]) || !std::isfinite(d.range[j][1]) || !(d.range[j][0] < d.range[j][1])))
+        ILSX_FAIL(ILSX_ERR_ARG, "swimmer: DoF %d is limited to an empty or non-finite range", i);
+    }
+  }
+  d.timestep = pm->timestep;
+  for (int k = 0; k < 3; ++k) d.solimp[k] = pm->limit_solimp[k];
+  const double tc = pm->limit_solref[0], dr = pm->limit_solref[1], dmax = pm->limit_solimp[1];
+  d.lim_b = 2.0 / (dmax * tc);
+  d.lim_k = 1.0 / (dmax * dmax * tc * tc * dr * dr);
+  d.ctrl_lo = (float)pm->ctrl_range[0]; d.ctrl_hi = (float)pm->ctrl_range[1];
+  return create_classic(ctx, ILSX_SWIMMER_TASK, nullptr, n_env, seed, out, &d);
+}
+
 extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out) {
   if (!ctx || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_classic: bad argument");
   if (kind == ILSX_CLASSIC_INVERTED_PENDULUM || kind == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM) {
@@ -1222,6 +1297,7 @@ extern "C" int ilsx_vecenv_destroy(ilsx_vecenv* e) {
   if (e->grp_flush_dev) ctx_free(e->ctx, e->grp_flush_dev);
   delete e->hm3;
   delete e->cc;
+  delete e->sw;
   delete e;
   return ILSX_OK;
 }

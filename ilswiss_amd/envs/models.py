@@ -29,6 +29,16 @@ def capsule_mass_inertia(p1, p2, r, density=DENSITY):
     return m_c + m_s, i_c + i_s
 
 
+def capsule_axial_inertia(p1, p2, r, density=DENSITY):
+    """The same capsule's inertia about its own long axis (cylinder m r^2 / 2, the two caps as one sphere 2 m r^2 / 5), with the cap
+    mass of capsule_mass_inertia.  A planar engine never turns a body about that axis; the Swimmer's drag model needs all three
+    principal inertias (models_swimmer.py)."""
+    L = math.hypot(p2[0] - p1[0], p2[1] - p1[1])
+    m_c = density * math.pi * r * r * L
+    m_s = density * math.pi * r ** 3
+    return m_c * (r * r / 2.0) + m_s * (2.0 * r * r / 5.0)
+
+
 def _body(name, parent, anchor_world, p1_world, p2_world, radius, friction, extra_geoms=(), **joint):
     """extra_geoms: further capsules (p1_world, p2_world, radius, friction) rigidly attached to the same body."""
     return dict(name=name, parent=parent, anchor_world=anchor_world, p1_world=p1_world, p2_world=p2_world,

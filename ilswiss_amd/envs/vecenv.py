@@ -14,6 +14,7 @@ from ..device import as_dev, get_context, host_ptr
 from .models import MODELS
 from .models3d import MODELS3D
 from .models_cartchain import MODELS_CARTCHAIN
+from .models_swimmer import MODELS_SWIMMER
 
 
 class Box:  # minimal gym.spaces.Box stand-in (gym is not installed here)
@@ -49,6 +50,10 @@ CLASSIC = {"cartpole": 0, "pendulum": 1}
 # the library (ilsx_vecenv_create_cartchain), so they are listed apart; CLASSIC_KINDS holds every name of the engine.
 CARTCHAIN = {"invertedpendulum": 2, "inverteddoublependulum": 3}
 CLASSIC_KINDS = {**CLASSIC, **CARTCHAIN}
+# the free planar chain in a viscous medium (k_swimmer_step of csrc/swimmer_env.h; ILSX_SWIMMER_TASK), under the envs_dict spelling.  A
+# stepper of its own beside the classic-control kinds: its task id is outside theirs and ilsx_vecenv_create_classic does not build it; the
+# constants always come from the model description (models_swimmer.py) through ilsx_vecenv_create_swimmer.
+SWIMMER = {"swimmer": 16}
 
 
 def model_struct(m):
@@ -94,6 +99,31 @@ def cartchain_struct(m):
     for k in (0, 1, 2):
         s.limit_solimp[k] = m["limit_solimp"][k]
     s.gear, s.jsign, s.timestep, s.gravity = m["gear"], m["jsign"], m["timestep"], m["gravity"]
+    return s
+
+
+def swimmer_struct(m):
+    """models_swimmer dict -> ilsx_swimmer_model (include/ilsx.h).  Raises ValueError for a chain the struct cannot hold."""
+    nl = m["n_link"]
+    if not 1 <= nl <= _lib._MSL:
+        raise ValueError(f"swimmer: n_link={nl}, ilsx_swimmer_model holds 1 to {_lib._MSL} links")
+    s = _lib.SwimmerModel()
+    s.n_link, s.frame_skip, s.pgs_iters = nl, m["frame_skip"], m["pgs_iters"]
+    for b in range(nl):
+        s.mass[b] = m["mass"][b]
+        for k in (0, 1, 2):
+            s.inertia[b][k], s.box[b][k] = m["inertia"][b][k], m["box"][b][k]
+        for k in (0, 1):
+            s.com[b][k], s.anchor[b][k] = m["com"][b][k], m["anchor"][b][k]
+    for i in range(nl + 2):
+        s.limited[i], s.armature[i], s.damping[i], s.gear[i], s.init_qpos[i] = m["limited"][i], m["armature"][i], m["damping"][i], m["gear"][i], m["init_qpos"][i]
+        for k in (0, 1):
+            s.range[i][k] = m["range"][i][k]
+    for k in (0, 1):
+        s.ctrl_range[k], s.limit_solref[k] = m["ctrl_range"][k], m["limit_solref"][k]
+    for k in (0, 1, 2):
+        s.limit_solimp[k] = m["limit_solimp"][k]
+    s.timestep, s.density, s.viscosity = m["timestep"], m["density"], m["viscosity"]
     return s
 
 
@@ -196,7 +226,14 @@ class HipVectorEnv:
         self.env_name = env_name
         self.env_num = int(env_num)
         self.h = C.c_void_p()
-        if env_name in CARTCHAIN:       # classic-control engine, cart and poles: the constants always come from the model description
+        if env_name in SWIMMER:         # the free chain in a viscous medium: the model description is the one source of the constants
+            if obs_shift is not None:
+                raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for this task")
+            self.swimmer_model = model or MODELS_SWIMMER[env_name]()
+            self.model = None
+            ms = swimmer_struct(self.swimmer_model)
+            _lib.check(self.ctx.lib.ilsx_vecenv_create_swimmer(self.ctx.h, C.byref(ms), self.env_num, C.c_uint64(seed), C.byref(self.h)))
+        elif env_name in CARTCHAIN:     # classic-control engine, cart and poles: the constants always come from the model description
             if obs_shift is not None:
                 raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for classic-control tasks")
             self.cartchain_model = model or MODELS_CARTCHAIN[env_name]()

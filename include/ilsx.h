@@ -646,6 +646,32 @@ typedef struct {
   double timestep, gravity, limit_solref[2], limit_solimp[3];
 } ilsx_cartchain_model;
 int ilsx_vecenv_create_cartchain(ilsx_ctx* ctx, const ilsx_cartchain_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
+/* Swimmer — gym 0.22's SwimmerEnv rules (envs_dict `swimmer`) behind NormalizedBoxEnv, on this library's own dynamics of a free planar
+ * chain of n_link links in a viscous medium (csrc/swimmer_env.h; no MuJoCo).  DoF (x, y, theta_0, q_1, ...): the
+ * first link carries two slides and a hinge at its origin, link k >= 1 hinges on link k - 1 at anchor[k] (the parent's frame); a link's
+ * absolute angle is theta_0 + q_1 + ... + q_k, counter-clockwise.  float64 state, nq = nv = n_link + 2; RK4 with a soft joint-limit solve
+ * in every stage, frame_skip substeps; no gravity in the plane, no contacts.  Each link feels the drag of its inertia box: box[k] holds
+ * the box's full sides (along the link, across it in the plane, normal to the plane), which the caller derives from mass and
+ * inertia[k] = (I_x, I_y, I_z) about the COM; force and torque are in the header of swimmer_env.h.  The arrays indexed by DoF
+ * (limited, armature, damping, range, gear, init_qpos) have n_link + 2 entries; only the hinges q_k may be limited, and gear drives them
+ * (ctrl = clip(lb + (a + 1) * 0.5 * (ub - lb), lb, ub) in float32 per actuator).  Box(-1, 1) actions of width n_link - 1; observation
+ * float32 (qpos[2:] | qvel); reward = (x' - x) / (frame_skip * timestep) - 1e-4 * sum ctrl^2; never done; reset = init_qpos + U(+-0.1)
+ * on qpos, U(+-0.1) on qvel.  The kernels are instantiated for n_link = 3.  The handle is an ordinary ilsx_vecenv of the classic-control
+ * kind (ilsx_vecenv_set_obs_affine is not available); ilsx_vecenv_create_classic does not build it: the caller is the one source of the
+ * constants (ilswiss_amd/envs/models_swimmer.py). */
+#define ILSX_SWIMMER_MAX_LINK 4
+#define ILSX_SWIMMER_MAX_DOF (ILSX_SWIMMER_MAX_LINK + 2)
+enum { ILSX_SWIMMER_TASK = 16 };   /* the task id of the handle, outside ILSX_CLASSIC_* */
+typedef struct {
+  int n_link, frame_skip, pgs_iters;
+  int limited[ILSX_SWIMMER_MAX_DOF];
+  double mass[ILSX_SWIMMER_MAX_LINK], inertia[ILSX_SWIMMER_MAX_LINK][3], box[ILSX_SWIMMER_MAX_LINK][3];
+  double com[ILSX_SWIMMER_MAX_LINK][2], anchor[ILSX_SWIMMER_MAX_LINK][2];
+  double armature[ILSX_SWIMMER_MAX_DOF], damping[ILSX_SWIMMER_MAX_DOF], range[ILSX_SWIMMER_MAX_DOF][2], gear[ILSX_SWIMMER_MAX_DOF];
+  double init_qpos[ILSX_SWIMMER_MAX_DOF];
+  double ctrl_range[2], timestep, density, viscosity, limit_solref[2], limit_solimp[3];
+} ilsx_swimmer_model;
+int ilsx_vecenv_create_swimmer(ilsx_ctx* ctx, const ilsx_swimmer_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
 /* discrete_n = n of a Discrete(n) action space, 0 for Box actions */
 int ilsx_vecenv_action_space(const ilsx_vecenv* env, int* discrete_n);
 /* Path mode of the fused rollout (ilsx_rollout_step with a replay ring): 0 (default) = every transition enters the ring when it
