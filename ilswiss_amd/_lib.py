@@ -101,7 +101,8 @@ class SpatialModel(C.Structure):  # ilsx_spatial_model
                 ("contact_solref", C.c_double * 2), ("contact_solimp", C.c_double * 3),
                 ("limit_solref", C.c_double * 2), ("limit_solimp", C.c_double * 3),
                 ("ctrl_cost", C.c_double), ("alive_bonus", C.c_double), ("vel_weight", C.c_double), ("z_min", C.c_double),
-                ("z_max", C.c_double), ("init_qpos", C.c_double * (_ML3 + 6))]
+                ("z_max", C.c_double), ("init_qpos", C.c_double * (_ML3 + 6)),
+                ("obs_trunc", C.c_int32), ("pad0", C.c_int32)]
 
 
 class Td3Cfg(C.Structure):  # ilsx_td3_cfg

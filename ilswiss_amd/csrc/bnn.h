@@ -15,6 +15,10 @@
 // H = 200); wave w owns output columns [16w, 16w+16) of every layer.  Each layer is a chain of exact-fp32 MFMAs
 // (v_mfma_f32_16x16x4_f32); the layer's input rows sit in LDS, the member's weights stream from L2.  Fragment maps (MI355X guide 3):
 //   lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15]; lane l, register v receives D[row = 4*(l>>4) + v][col = l&15].
+// Widths above 256 (up to 400, the reference's Humanoid spec) take the wide kernel k_bnn_wide further down: HP/16 would be up to 25 waves,
+// so a wave owns TWO 16-column slices of a layer, w and w + nwaves (13 waves for H = 400; the last wave has one slice when the slice count
+// is odd), two accumulators fed by one LDS read of the input fragment, and the two LDS tiles get a 404-float row stride (51.7 KB).  Same
+// math, layout, fragment maps and MFMA chain per column.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,6 +28,9 @@
 #define ILSX_BNN_MAX_LAYERS 9       // hidden layers + head
 #define ILSX_BNN_LDA 260            // LDS row stride of an activation tile (widths <= 256, +4 against bank conflicts)
 #define ILSX_BNN_MAX_WAVES 16
+#define ILSX_BNN_MAX_WIDE 400       // widest hidden layer (k_bnn_wide); in_dim and the head stay <= 256
+#define ILSX_BNN_LDA_WIDE 404       // its row stride: 404 = 20 mod 64, so the 16 rows x 4 k of an A fragment fall in 64 distinct banks
+#define ILSX_BNN_SPW_WIDE 2         // 16-column slices per wave of k_bnn_wide
 
 enum { BNN_PREDICT = 0, BNN_TRAIN = 1, BNN_MSE = 2 };
 
@@ -80,6 +87,7 @@ __device__ __forceinline__ f32x4 bnn_tile_mm(const float (*in)[ILSX_BNN_LDA], co
 
 // Forward of the whole ensemble (and, for BNN_TRAIN, the loss gradient and the backward chain down to the first layer's
 // pre-activation gradient).  grid (ntiles, E), block 64 * max(HP, KP_0, NOP) / 16.
+// KEEP IN STEP with k_bnn_wide below: input staging, head split, loss gradient and partial sums are the same text in both kernels.
 template <int MODE>
 __global__ __launch_bounds__(1024) void k_bnn_fwd(const BnnFwdArgs A) {
   __shared__ float sbuf[2][16][ILSX_BNN_LDA];
@@ -224,6 +232,208 @@ __global__ __launch_bounds__(1024) void k_bnn_fwd(const BnnFwdArgs A) {
           A.dpre[o_] = dp;
         }
         sbuf[cur ^ 1][r][col] = dp;
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+// ---- hidden widths 257..400: k_bnn_fwd with SPW = 2 slices per wave and 404-float LDS rows.  A kernel of its own rather than a
+// template parameter of k_bnn_fwd: the narrow kernel's instruction stream is pinned (tests/test_pendulum_cpu.py compares every existing
+// kernel with its earlier build), and sharing one body moves its schedule.  Everything outside the two matrix chains is k_bnn_fwd's text.
+// The wide instantiation's bnn_tile_mm: one layer of one 16-row tile, the first NS slices of wave w: acc[j] is the
+// 16-column slice w + j * nw (nw = waves of the workgroup).  One LDS read of the A fragment feeds every slice; each slice is its own
+// k-ascending MFMA chain, so the sum order of a column does not depend on NS.
+template <int NS, int SPW, int LDA>
+__device__ __forceinline__ void bnn_wide_mm_n(const float (*in)[LDA], const float* __restrict__ W, int kp, int ldw, int w, int nw, int lane,
+                                              f32x4 (&acc)[SPW]) {
+  const int i = lane & 15, kk = lane >> 4;
+  const float* wp = W + (size_t)kk * ldw + 16 * w + i;
+  for (int k0 = 0; k0 < kp; k0 += 4) {
+    const float av = in[i][k0 + kk];
+    float bv[NS];                    // every slice's load in flight before the first MFMA; static register indices: no scratch
+#pragma unroll
+    for (int j = 0; j < NS; ++j) bv[j] = wp[(size_t)k0 * ldw + 16 * j * nw];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[j], acc[j], 0, 0, 0);
+  }
+}
+
+// The wave's slices of a layer with ns = NP / 16 slices (slice w exists; slice w + nw when it is below ns; w is wave-uniform).
+template <int SPW, int LDA>
+__device__ __forceinline__ void bnn_wide_mm(const float (*in)[LDA], const float* __restrict__ W, int kp, int ldw, int w, int nw, int ns,
+                                            int lane, f32x4 (&acc)[SPW]) {
+  static_assert(SPW == 1 || SPW == 2, "one or two slices per wave");
+#pragma unroll
+  for (int j = 0; j < SPW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (SPW == 2 && w + nw < ns) bnn_wide_mm_n<SPW, SPW, LDA>(in, W, kp, ldw, w, nw, lane, acc);
+  else bnn_wide_mm_n<1, SPW, LDA>(in, W, kp, ldw, w, nw, lane, acc);
+}
+
+// Forward of the whole ensemble, wide (and, for BNN_TRAIN, the loss gradient and the backward chain down to the first layer's
+// pre-activation gradient).  grid (ntiles, E), block 64 * nw with nw = max(ceil(HP / 16 / SPW), KP_0 / 16, NOP / 16) <= 16 waves.
+// Wave w owns slices w, w + nw, ... (SPW of them at most) of every layer, in the forward and in the backward chain alike.
+// KEEP IN STEP with k_bnn_fwd above: input staging, head split, loss gradient and partial sums are the same text in both kernels; a fix
+// to one is a fix to the other.
+template <int MODE>
+__global__ __launch_bounds__(1024) void k_bnn_wide(const BnnFwdArgs A) {
+  constexpr int SPW = ILSX_BNN_SPW_WIDE, LDA = ILSX_BNN_LDA_WIDE;
+  __shared__ float sbuf[2][16][LDA];
+  __shared__ float sred[ILSX_BNN_MAX_WAVES][2];
+  const BnnNet& N = A.net;
+  const int tile = blockIdx.x, e = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
+  const int lane = tid & 63, nw = nthr >> 6;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // decides which slices exist: kept in a scalar register
+  const int row0 = tile * 16;
+  const float* Pm = N.P + (size_t)e * N.mstride;
+  const int kp0 = N.kp[0], in_dim = N.in_dim, D = N.D;
+
+  // ---- input tile, normalised on the load: (x - mean) / std, padded columns / rows zero
+  for (int t = tid; t < 16 * kp0; t += nthr) {
+    const int r = t / kp0, k = t - r * kp0, gr = row0 + r;
+    float v = 0.f;
+    if (gr < A.rows && k < in_dim) {
+      float raw;
+      if (A.ring) {
+        long long slot = A.idx[(size_t)e * A.idx_ms + gr];
+        if (slot < 0 || slot >= A.cap) slot = 0;
+        raw = A.ring[(size_t)slot * A.rec + k];      // record: obs | act | ...
+      } else {
+        raw = A.x[(size_t)gr * in_dim + k];
+      }
+      v = (raw - N.mean[k]) / N.std[k];
+    }
+    sbuf[0][r][k] = v;
+    if (MODE == BNN_TRAIN && gr < A.rows) A.xs[((size_t)e * A.ldr + gr) * kp0 + k] = v;
+  }
+  __syncthreads();
+
+  int cur = 0;
+  for (int l = 0; l < N.nl; ++l) {
+    const int kp = N.kp[l], np = N.np[l];
+    const bool head = (l == N.nl - 1);
+    if (w < np / 16) {
+      f32x4 acc[SPW];
+      bnn_wide_mm<SPW, LDA>(sbuf[cur], Pm + N.off_w[l], kp, np, w, nw, np / 16, lane, acc);
+#pragma unroll
+      for (int j = 0; j < SPW; ++j) {
+        if (j == 0 || w + j * nw < np / 16) {
+          const int col = 16 * (w + j * nw) + (lane & 15);
+          const float bias = Pm[N.off_b[l] + col];
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const int r = 4 * (lane >> 4) + v, gr = row0 + r;
+            const float x = acc[j][v] + bias;
+            if (head) {
+              sbuf[cur ^ 1][r][col] = x;
+            } else {
+              const float h = bnn_silu(x);
+              sbuf[cur ^ 1][r][col] = h;
+              if (MODE == BNN_TRAIN && gr < A.rows) {
+                const size_t o_ = (((size_t)l * gridDim.y + e) * A.ldr + gr) * N.HP + col;
+                A.pre[o_] = x;
+                A.hs[o_] = h;
+              }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // ---- head split (BNN.forward, networks.py:241-263): mean | log-var soft-clamped into [min_lv, max_lv]
+  const float max_lv = 0.5f, min_lv = -10.0f;
+  float s0 = 0.f, s1 = 0.f;
+  for (int t = tid; t < 16 * N.NOP; t += nthr) {
+    const int r = t / N.NOP, c = t - r * N.NOP, gr = row0 + r;
+    if (c >= D) {
+      if (MODE == BNN_TRAIN && c >= 2 * D) sbuf[cur ^ 1][r][c] = 0.f;
+      continue;
+    }
+    const float mu = sbuf[cur][r][c], raw = sbuf[cur][r][D + c];
+    const float lv1 = max_lv - bnn_softplus(max_lv - raw);
+    const float lv = min_lv + bnn_softplus(lv1 - min_lv);
+    if (MODE == BNN_PREDICT) {
+      if (gr < A.rows) {
+        const size_t o_ = ((size_t)e * A.rows + gr) * D + c;
+        A.out_mean[o_] = mu;
+        A.out_lv[o_] = A.out_var ? expf(lv) : lv;
+      }
+      continue;
+    }
+    float gmu = 0.f, graw = 0.f;
+    if (gr < A.rows) {
+      const long long slot0 = A.idx[(size_t)e * A.idx_ms + gr];
+      const long long slot = (slot0 < 0 || slot0 >= A.cap) ? 0 : slot0;
+      const float* R = A.ring + (size_t)slot * A.rec;
+      // target [reward_scale * rew | next_obs - obs] (bnn_trainer.py:92-97)
+      const float tg = c == 0 ? A.reward_scale * R[A.o + A.a] : R[A.o + A.a + 2 + (c - 1)] - R[c - 1];
+      const float diff = mu - tg, sq = diff * diff;
+      if (MODE == BNN_MSE && !A.add_var) {
+        s0 += sq;
+      } else {
+        const float inv = expf(-lv);
+        s0 += sq * inv;
+        s1 += lv;
+        if (MODE == BNN_TRAIN) {   // d/dmu, d/dlv of mean_e[ mean((mu - t)^2 e^-lv) + mean(lv) ]; lv = f(raw) through both softplus
+          gmu = A.gscale * 2.0f * diff * inv;
+          const float glv = A.gscale * (1.0f - sq * inv);
+          graw = glv * bnn_sigmoid(lv1 - min_lv) * bnn_sigmoid(max_lv - raw);
+        }
+      }
+    }
+    if (MODE == BNN_TRAIN) {
+      sbuf[cur ^ 1][r][c] = gmu;
+      sbuf[cur ^ 1][r][D + c] = graw;
+      if (gr < A.rows) {
+        float* dh = A.dhead + ((size_t)e * A.ldr + gr) * N.NOP;
+        dh[c] = gmu;
+        dh[D + c] = graw;
+      }
+    }
+  }
+  if (MODE == BNN_PREDICT) return;
+  // per-(member, tile) partial sums, fixed order
+  s0 = bnn_wave_sum(s0);
+  s1 = bnn_wave_sum(s1);
+  if (lane == 0) { sred[w][0] = s0; sred[w][1] = s1; }
+  __syncthreads();
+  if (tid == 0) {
+    float a0 = 0.f, a1 = 0.f;
+    for (int q = 0; q < (nthr >> 6); ++q) { a0 += sred[q][0]; a1 += sred[q][1]; }
+    A.partial[((size_t)e * A.ntiles + tile) * 2 + 0] = a0;
+    A.partial[((size_t)e * A.ntiles + tile) * 2 + 1] = a1;
+  }
+  if (MODE != BNN_TRAIN) return;
+  // padded head columns of the gradient tile (written above for c >= 2D) and columns [D, 2D) were set by the owners of c < D
+  cur ^= 1;
+  // ---- backward chain: dh_{l-1} = dpre_l @ W_l^T, dpre_{l-1} = dh_{l-1} * silu'(pre_{l-1})
+  for (int l = N.nl - 1; l >= 1; --l) {
+    const int kp = N.kp[l], np = N.np[l];
+    if (w < kp / 16) {
+      f32x4 acc[SPW];
+      bnn_wide_mm<SPW, LDA>(sbuf[cur], Pm + N.off_wt[l], np, kp, w, nw, kp / 16, lane, acc);
+#pragma unroll
+      for (int j = 0; j < SPW; ++j) {
+        if (j == 0 || w + j * nw < kp / 16) {
+          const int col = 16 * (w + j * nw) + (lane & 15);
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const int r = 4 * (lane >> 4) + v, gr = row0 + r;
+            float dp = 0.f;
+            if (gr < A.rows) {
+              const size_t o_ = (((size_t)(l - 1) * gridDim.y + e) * A.ldr + gr) * N.HP + col;
+              const float x = A.pre[o_];           // written by this very lane in the forward (same wave / slice / column / row map)
+              const float sg = bnn_sigmoid(x);
+              dp = acc[j][v] * (sg * (1.0f + x * (1.0f - sg)));
+              A.dpre[o_] = dp;
+            }
+            sbuf[cur ^ 1][r][col] = dp;
+          }
+        }
       }
     }
     __syncthreads();

@@ -24,7 +24,7 @@
 #define E3_MAXOBS 384
 
 struct Spatial3Dev {
-  int nl, nv, nq, task, frame_skip, pgs_iters, max_rows, n_act, obs_dim, n_contact, n_body, pad0;
+  int nl, nv, nq, task, frame_skip, pgs_iters, max_rows, n_act, obs_dim, n_contact, n_body, obs_trunc;   // obs_trunc: the observation ends after qpos[2:] | qvel
   int parent[E3_MAXL], limited[E3_MAXL], act_link[E3_MAXL], contact_link[E3_MAXC], body_link[E3_MAXB], body_first[E3_MAXB];
   double anchor[E3_MAXL][3], axis[E3_MAXL][3], axis_p[E3_MAXL][3], Rq0[E3_MAXL][9], com[E3_MAXL][3], mass[E3_MAXL], inertia[E3_MAXL][6];
   double armature[E3_MAXL], damping[E3_MAXL], stiffness[E3_MAXL], range[E3_MAXL][2], gear[E3_MAXL];
@@ -487,14 +487,17 @@ __device__ double e3_com(const E3Ctx& C, double* com3) {
 }
 
 // observation of the state at (Q0, V0) (oracle obs()): KIN must hold the kinematics of that state.  `put(i, value)` receives the
-// raw components; the caller applies the ScaledEnv map and the float conversion.
-template <class Put>
+// raw components; the caller applies the ScaledEnv map and the float conversion.  TRUNC: whether the observation ends after
+// qpos[2:] | qvel (the model's obs_trunc) — -1 reads the model's flag, 0 / 1 fix it at compile time (the full-observation kernels keep
+// their instruction streams; the truncated tasks get kernels of their own).
+template <int TRUNC = -1, class Put>
 __device__ void e3_observe(const E3Ctx& C, Put put) {
   const Spatial3Dev& m = *C.m;
   double* scr = C.scr; const int n_env = C.n_env, env = C.env;
   int at = 0;
   for (int i = 2; i < m.nq; ++i) put(at++, E3S(E3St::Q0 + i));
   for (int i = 0; i < m.nv; ++i) put(at++, E3S(E3St::V0 + i));
+  if (TRUNC > 0 || (TRUNC < 0 && m.obs_trunc)) return;   // the MBPO tasks' qpos[2:] | qvel: no COM, cinert, cvel or actuator work at all
   const int nb = m.n_body;
   if (m.task == 3) {   // Ant-v2: clip(cfrc_ext, -1, 1) of 14 bodies — zeros (see oracle/spatial_env.py::obs_extras)
     for (int i = 0; i < (nb + 1) * 6; ++i) put(at++, 0.0);
@@ -624,7 +627,8 @@ static inline const char* e3_build_model(const ilsx_spatial_model* sm, Spatial3D
   m.ctrl_cost = sm->ctrl_cost; m.alive = sm->alive_bonus; m.vel_weight = sm->vel_weight; m.z_min = sm->z_min; m.z_max = sm->z_max;
   for (int i = 0; i < m.nq; ++i) m.init_qpos[i] = sm->init_qpos[i];
   const int base = (m.nq - 2) + m.nv, nb1 = m.n_body + 1;
-  m.obs_dim = m.task == ILSX_TASK_HUMANOID ? base + nb1 * 10 + nb1 * 6 + m.nv + nb1 * 6 : base + nb1 * 6;
+  m.obs_trunc = sm->obs_trunc != 0;
+  m.obs_dim = m.obs_trunc ? base : m.task == ILSX_TASK_HUMANOID ? base + nb1 * 10 + nb1 * 6 + m.nv + nb1 * 6 : base + nb1 * 6;
   if (m.obs_dim > E3_MAXOBS) return "observation wider than E3_MAXOBS";
   for (int i = 0; i < E3_MAXOBS; ++i) { m.obs_shift[i] = 0.0; m.obs_inv_scale[i] = 1.0; }
   {

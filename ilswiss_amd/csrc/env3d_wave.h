@@ -852,12 +852,13 @@ __device__ __forceinline__ void e3w_task_step(e3w_lds* S, const Spatial3Dev& m, 
 }
 
 // observation of the state at (Q0, V0) (oracle obs()); KIN must hold its kinematics.  put(i, value) is called once per component,
-// components spread over the lanes.
-template <class Put>
+// components spread over the lanes.  TRUNC as in e3_observe: -1 reads m.obs_trunc, 0 / 1 fix it at compile time.
+template <int TRUNC = -1, class Put>
 __device__ __forceinline__ void e3w_observe(const e3w_lds* S, const Spatial3Dev& m, int lane, Put put) {
   const int nq2 = m.nq - 2, nv = m.nv, nb = m.n_body;
   E3W_FOR(i, nq2) put(i, S[E3WOff::Q0 + 2 + i]);
   E3W_FOR(i, nv) put(nq2 + i, S[E3WOff::V0 + i]);
+  if (TRUNC > 0 || (TRUNC < 0 && m.obs_trunc)) return;   // the MBPO tasks' qpos[2:] | qvel: skips e3w_com and the cinert / cvel / actuator loops
   int at = nq2 + nv;
   if (m.task == 3) {   // Ant-v2: clip(cfrc_ext, -1, 1) of 14 bodies — zeros (oracle/spatial_env.py::obs_extras)
     E3W_FOR(i, (nb + 1) * 6) put(at + i, 0.0);

@@ -34,7 +34,20 @@ struct ilsx_bnn {
 
 static int r16(int x) { return (x + 15) / 16 * 16; }
 
-static int bnn_threads(const ilsx_bnn* b) { return 64 * (std::max(std::max(b->HP, b->KP0), b->NOP) / 16); }
+// hidden widths above 256 run k_bnn_wide: a wave owns ILSX_BNN_SPW_WIDE slices of a hidden layer
+static bool bnn_wide(const ilsx_bnn* b) { return b->HP > 256; }
+
+static int bnn_threads(const ilsx_bnn* b) {
+  const int hs = b->HP / 16, hw = bnn_wide(b) ? (hs + ILSX_BNN_SPW_WIDE - 1) / ILSX_BNN_SPW_WIDE : hs;
+  return 64 * std::max(std::max(hw, b->KP0 / 16), b->NOP / 16);
+}
+
+template <int MODE>
+static void bnn_launch_fwd(const ilsx_bnn* b, int ntiles, const BnnFwdArgs& A) {
+  const dim3 grid(ntiles, b->cfg.ensemble), block(bnn_threads(b));
+  if (bnn_wide(b)) hipLaunchKernelGGL(k_bnn_wide<MODE>, grid, block, 0, b->ctx->stream, A);
+  else hipLaunchKernelGGL(k_bnn_fwd<MODE>, grid, block, 0, b->ctx->stream, A);
+}
 
 static BnnNet bnn_net(const ilsx_bnn* b) {
   BnnNet N{};
@@ -62,8 +75,9 @@ extern "C" int ilsx_bnn_create(ilsx_ctx* ctx, const ilsx_bnn_cfg* cfg, ilsx_bnn*
   if (c.ensemble < 1 || c.in_dim < 1 || c.out_dim < 2 || c.hidden < 1 || c.max_batch < 1)
     ILSX_FAIL(ILSX_ERR_ARG, "ilsx_bnn_create: bad shape (E=%d in=%d out=%d H=%d max_batch=%d)", c.ensemble, c.in_dim, c.out_dim, c.hidden, c.max_batch);
   if (c.n_hidden < 1 || c.n_hidden > ILSX_BNN_MAX_HID) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_bnn_create: n_hidden=%d outside 1..%d", c.n_hidden, ILSX_BNN_MAX_HID);
-  if (r16(c.hidden) > 256 || r16(c.in_dim) > 256 || r16(2 * c.out_dim) > 256)
-    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_bnn_create: widths above 256 (hidden %d, in %d, head %d) are not supported", c.hidden, c.in_dim, 2 * c.out_dim);
+  if (r16(c.hidden) > ILSX_BNN_MAX_WIDE || r16(c.in_dim) > 256 || r16(2 * c.out_dim) > 256)
+    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_bnn_create: hidden width above %d or input / head width above 256 (hidden %d, in %d, head %d) is not supported",
+              ILSX_BNN_MAX_WIDE, c.hidden, c.in_dim, 2 * c.out_dim);
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_bnn* b = new ilsx_bnn();
   b->ctx = ctx; b->cfg = c;
@@ -297,7 +311,7 @@ extern "C" int ilsx_bnn_train_batch(ilsx_bnn* b, ilsx_replay* rb, const int32_t*
   A.xs = b->xs; A.pre = b->pre; A.hs = b->hs; A.dhead = b->dhead; A.dpre = b->dpre; A.ldr = b->ldr;
   A.gscale = (float)(1.0 / ((double)E * B * b->D));
   A.partial = b->part; A.add_var = 1;
-  hipLaunchKernelGGL(k_bnn_fwd<BNN_TRAIN>, dim3(nt, E), dim3(bnn_threads(b)), 0, c->stream, A);
+  bnn_launch_fwd<BNN_TRAIN>(b, nt, A);
   HIPCHK(hipGetLastError());
   // torch Adam: t += 1; step_size = lr / (1 - b1^t); denom = sqrt(v) / sqrt(1 - b2^t) + eps (bnn_trainer.py:81-87,150-154)
   b->t += 1;
@@ -338,7 +352,7 @@ extern "C" int ilsx_bnn_mse(ilsx_bnn* b, ilsx_replay* rb, const int32_t* idx, in
   ILSX_TRY(bnn_grow(b, &b->part, &b->part_n, (size_t)E * nt * 2));
   BnnFwdArgs A = bnn_fwd_args(b, rb, idx, idx_member_stride, n);
   A.partial = b->part; A.add_var = add_var ? 1 : 0;
-  hipLaunchKernelGGL(k_bnn_fwd<BNN_MSE>, dim3(nt, E), dim3(bnn_threads(b)), 0, c->stream, A);
+  bnn_launch_fwd<BNN_MSE>(b, nt, A);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_bnn_reduce, dim3((E + 63) / 64), dim3(64), 0, c->stream, b->part, E, nt, (float)((double)n * b->D), b->loss);
   HIPCHK(hipGetLastError());
@@ -348,10 +362,10 @@ extern "C" int ilsx_bnn_mse(ilsx_bnn* b, ilsx_replay* rb, const int32_t* idx, in
 }
 
 static int bnn_forward_rows(ilsx_bnn* b, const float* x, int n, float* mean, float* lv, int out_var) {
-  const int E = b->cfg.ensemble, nt = (n + 15) / 16;
+  const int nt = (n + 15) / 16;
   BnnFwdArgs A = bnn_fwd_args(b, nullptr, nullptr, 0, n);
   A.x = x; A.out_mean = mean; A.out_lv = lv; A.out_var = out_var;
-  hipLaunchKernelGGL(k_bnn_fwd<BNN_PREDICT>, dim3(nt, E), dim3(bnn_threads(b)), 0, b->ctx->stream, A);
+  bnn_launch_fwd<BNN_PREDICT>(b, nt, A);
   HIPCHK(hipGetLastError());
   return ILSX_OK;
 }

@@ -638,88 +638,8 @@ __device__ void e3_reset_state(const E3Ctx& C, uint64_t seed, uint32_t stream, u
   for (int k = 0; k < m.n_act; ++k) E3S(E3St::CTRL + k) = 0.0;   // qfrc_actuator of a freshly reset model is zero
 }
 
-__global__ __launch_bounds__(64) void k_env3d_step(const EnvStepArgs A, const Spatial3Dev* mp, double* scr) {
-  const Spatial3Dev& m = *mp;
-  const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= A.n_ids) return;
-  const int env = A.ids ? A.ids[t] : t, n_env = A.n_env;
-  if (A.frozen && A.frozen[env]) return;
-  const E3Ctx C{scr, n_env, env, mp};
-  const int o = m.obs_dim, na = m.n_act;
-  for (int i = 0; i < m.nq; ++i) E3S(E3St::Q0 + i) = A.qpos[(size_t)i * n_env + env];
-  for (int i = 0; i < m.nv; ++i) E3S(E3St::V0 + i) = A.qvel[(size_t)i * n_env + env];
-  float* rec = nullptr;
-  if (A.replay) {   // fused replay insert: the observation the policy acted on is the stored current observation
-    long long slot = A.top + env;
-    if (slot >= A.cap) slot -= A.cap;
-    rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
-    for (int i = 0; i < o; ++i) rec[i] = A.obs_cur[(size_t)env * o + i];
-  }
-  double reward; bool done;
-  e3_task_step(C, A.act + (size_t)t * na, reward, done);
-  bool end = false; int len = 0; double ret = 0.0;
-  if (A.auto_reset) {
-    len = A.ep_len[env] + 1; ret = A.ep_ret[env] + reward;
-    bool finite = isfinite(reward);
-    end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // see k_env_step: no_terminal keeps stepping an unhealthy env
-  }
-  float* obs_out = A.obs ? A.obs + (size_t)t * o : nullptr;
-  float* cur = (A.obs_cur && !end) ? A.obs_cur + (size_t)env * o : nullptr;
-  float* rnext = rec ? rec + o + na + 2 : nullptr;
-  e3_observe(C, [&](int i, double val) {
-    const float f = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]);
-    if (obs_out) obs_out[i] = f;
-    if (cur) cur[i] = f;
-    if (rnext) rnext[i] = f;
-  });
-  if (A.rew) A.rew[t] = (float)reward;
-  if (A.done) A.done[t] = done ? 1 : 0;
-  if (rec) {
-    const float* ra = A.rec_act ? A.rec_act : A.act;
-    for (int k = 0; k < na; ++k) rec[o + k] = ra[(size_t)t * na + k];
-    rec[o + na] = (float)reward;
-    rec[o + na + 1] = (done && !A.no_terminal) ? 1.0f : 0.0f;
-    rec[2 * o + na + 2] = 0.0f; rec[2 * o + na + 3] = 0.0f;
-  }
-  if (A.auto_reset) {
-    if (end) {
-      atomicAdd(&A.stats[0], 1.0);
-      atomicAdd(&A.stats[1], ret);
-      e3_reset_state(C, A.seed, A.stream, A.step, (uint32_t)env);
-      e3_kinematics(C, E3St::Q0, E3St::V0);
-      float* c2 = A.obs_cur + (size_t)env * o;
-      e3_observe(C, [&](int i, double val) { c2[i] = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]); });
-    }
-    A.ep_len[env] = end ? 0 : len;
-    A.ep_ret[env] = end ? 0.0 : ret;
-    if (A.flush_len) A.flush_len[env] = end ? (len | ((done && !A.no_terminal) ? (1 << 30) : 0)) : 0;
-  }
-  for (int i = 0; i < m.nq; ++i) A.qpos[(size_t)i * n_env + env] = E3S(E3St::Q0 + i);
-  for (int i = 0; i < m.nv; ++i) A.qvel[(size_t)i * n_env + env] = E3S(E3St::V0 + i);
-}
-
-__global__ __launch_bounds__(64) void k_env3d_reset(const Spatial3Dev* mp, double* scr, double* qpos, double* qvel, int n_env, const int* ids,
-                                                    int n_ids, float* obs, float* obs_cur, int* ep_len, double* ep_ret, uint64_t seed,
-                                                    uint32_t stream, unsigned long long step) {
-  const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= n_ids) return;
-  const int env = ids ? ids[t] : t;
-  const Spatial3Dev& m = *mp;
-  const E3Ctx C{scr, n_env, env, mp};
-  e3_reset_state(C, seed, stream, step, (uint32_t)env);
-  e3_kinematics(C, E3St::Q0, E3St::V0);
-  const int o = m.obs_dim;
-  e3_observe(C, [&](int i, double val) {
-    const float f = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]);
-    if (obs) obs[(size_t)t * o + i] = f;
-    if (obs_cur) obs_cur[(size_t)env * o + i] = f;
-  });
-  ep_len[env] = 0; ep_ret[env] = 0.0;
-  for (int i = 0; i < m.nq; ++i) qpos[(size_t)i * n_env + env] = E3S(E3St::Q0 + i);
-  for (int i = 0; i < m.nv; ++i) qvel[(size_t)i * n_env + env] = E3S(E3St::V0 + i);
-}
-
-// ---- wave-per-env form (env3d_wave.h): one 64-lane workgroup per env, working set in that wave's LDS
+// ---- wave-per-env form (env3d_wave.h): one 64-lane workgroup per env, working set in that wave's LDS (its reset draws; the kernels of
+// both forms are in env3d_kernels.inc)
 __device__ __forceinline__ void e3w_reset_state(e3w_lds* S, const Spatial3Dev& m, int lane, uint64_t seed, uint32_t stream, unsigned long long step,
                                                 uint32_t envu) {
   // same draws as e3_reset_state: component i of qpos uses counter i, qvel nq + i (uniform) or nq + 2i, nq + 2i + 1 (Box-Muller)
@@ -741,99 +661,16 @@ __device__ __forceinline__ void e3w_reset_state(e3w_lds* S, const Spatial3Dev& m
   E3W_SYNC();
 }
 
-template <int NV>
-__global__ __launch_bounds__(64) void k_env3dw_step(const EnvStepArgs A, const Spatial3Dev* mp) {
-  extern __shared__ __attribute__((aligned(16))) double e3w_smem[];
-  e3w_lds* S = (e3w_lds*)e3w_smem;
-  const Spatial3Dev& m = *mp;
-  const int t = blockIdx.x, lane = threadIdx.x;
-  const int env = A.ids ? A.ids[t] : t, n_env = A.n_env;
-  if (A.frozen && A.frozen[env]) return;
-  const int o = m.obs_dim, na = m.n_act;
-  E3W_FOR(i, m.nq) S[E3WOff::Q0 + i] = A.qpos[(size_t)i * n_env + env];
-  E3W_FOR(i, m.nv) S[E3WOff::V0 + i] = A.qvel[(size_t)i * n_env + env];
-  float* rec = nullptr;
-  if (A.replay) {   // fused replay insert: the observation the policy acted on is the stored current observation
-    long long slot = A.top + env;
-    if (slot >= A.cap) slot -= A.cap;
-    rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
-    E3W_FOR(i, o) rec[i] = A.obs_cur[(size_t)env * o + i];
-  }
-  E3W_SYNC();
-  E3WRegs regs[1];
-  e3w_regs_init(regs[0], m, lane);
-  e3w_regs_pin(regs[0]);
-  double reward; bool done;
-  e3w_task_step<NV>(S, m, lane, regs, A.act + (size_t)t * na, reward, done);
-  bool end = false; int len = 0; double ret = 0.0;
-  if (A.auto_reset) {
-    len = A.ep_len[env] + 1; ret = A.ep_ret[env] + reward;
-    bool finite = isfinite(reward);
-    end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // see k_env_step: no_terminal keeps stepping an unhealthy env
-  }
-  float* obs_out = A.obs ? A.obs + (size_t)t * o : nullptr;
-  float* cur = (A.obs_cur && !end) ? A.obs_cur + (size_t)env * o : nullptr;
-  float* rnext = rec ? rec + o + na + 2 : nullptr;
-  e3w_observe(S, m, lane, [&](int i, double val) {
-    const float f = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]);
-    if (obs_out) obs_out[i] = f;
-    if (cur) cur[i] = f;
-    if (rnext) rnext[i] = f;
-  });
-  if (lane == 0) {
-    if (A.rew) A.rew[t] = (float)reward;
-    if (A.done) A.done[t] = done ? 1 : 0;
-  }
-  if (rec) {
-    const float* ra = A.rec_act ? A.rec_act : A.act;
-    E3W_FOR(k, na) rec[o + k] = ra[(size_t)t * na + k];
-    if (lane == 0) {
-      rec[o + na] = (float)reward;
-      rec[o + na + 1] = (done && !A.no_terminal) ? 1.0f : 0.0f;
-      rec[2 * o + na + 2] = 0.0f; rec[2 * o + na + 3] = 0.0f;
-    }
-  }
-  if (A.auto_reset) {
-    if (end) {
-      if (lane == 0) { atomicAdd(&A.stats[0], 1.0); atomicAdd(&A.stats[1], ret); }
-      E3W_SYNC();
-      e3w_reset_state(S, m, lane, A.seed, A.stream, A.step, (uint32_t)env);
-      e3w_kinematics(S, m, lane, regs, E3WOff::Q0, E3WOff::V0);
-      float* c2 = A.obs_cur + (size_t)env * o;
-      e3w_observe(S, m, lane, [&](int i, double val) { c2[i] = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]); });
-    }
-    if (lane == 0) {
-      A.ep_len[env] = end ? 0 : len; A.ep_ret[env] = end ? 0.0 : ret;
-      if (A.flush_len) A.flush_len[env] = end ? (len | ((done && !A.no_terminal) ? (1 << 30) : 0)) : 0;
-    }
-  }
-  E3W_FOR(i, m.nq) A.qpos[(size_t)i * n_env + env] = S[E3WOff::Q0 + i];
-  E3W_FOR(i, m.nv) A.qvel[(size_t)i * n_env + env] = S[E3WOff::V0 + i];
-}
-
-__global__ __launch_bounds__(64) void k_env3dw_reset(const Spatial3Dev* mp, double* qpos, double* qvel, int n_env, const int* ids, float* obs,
-                                                     float* obs_cur, int* ep_len, double* ep_ret, uint64_t seed, uint32_t stream,
-                                                     unsigned long long step) {
-  extern __shared__ __attribute__((aligned(16))) double e3w_smem[];
-  e3w_lds* S = (e3w_lds*)e3w_smem;
-  const Spatial3Dev& m = *mp;
-  const int t = blockIdx.x, lane = threadIdx.x;
-  const int env = ids ? ids[t] : t;
-  e3w_reset_state(S, m, lane, seed, stream, step, (uint32_t)env);
-  E3WRegs regs[1];
-  e3w_regs_init(regs[0], m, lane);
-  e3w_regs_pin(regs[0]);
-  e3w_kinematics(S, m, lane, regs, E3WOff::Q0, E3WOff::V0);
-  const int o = m.obs_dim;
-  e3w_observe(S, m, lane, [&](int i, double val) {
-    const float f = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]);
-    if (obs) obs[(size_t)t * o + i] = f;
-    if (obs_cur) obs_cur[(size_t)env * o + i] = f;
-  });
-  if (lane == 0) { ep_len[env] = 0; ep_ret[env] = 0.0; }
-  E3W_FOR(i, m.nq) qpos[(size_t)i * n_env + env] = S[E3WOff::Q0 + i];
-  E3W_FOR(i, m.nv) qvel[(size_t)i * n_env + env] = S[E3WOff::V0 + i];
-}
+#define E3K(name) name
+#define E3K_TRUNC 0
+#include "env3d_kernels.inc"
+#undef E3K
+#undef E3K_TRUNC
+#define E3K(name) name##_trunc
+#define E3K_TRUNC 1
+#include "env3d_kernels.inc"
+#undef E3K
+#undef E3K_TRUNC
 
 // ------------------------------------------------------------------------------------------------ host
 template <int NB, int MR, int BLOCK>
@@ -873,6 +710,17 @@ static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
       ILSX_LAUNCH(ps, k_swimmer_step<3>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->sw);
     else
       ILSX_LAUNCH(ps, k_cartpole_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
+    HIPCHK(hipGetLastError());
+    return ILSX_OK;
+  }
+  if (e->engine == 1 && e->hm3->obs_trunc) {   // the *_trunc_obs tasks: the same steppers with the observation ending after qvel
+    ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
+    if (e->wave3 && e->nv == 23)
+      ILSX_LAUNCH(ps, k_env3dw_step_trunc<23>, dim3(A.n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, A, (const Spatial3Dev*)e->dm3);
+    else if (e->wave3 && e->nv == 14)
+      ILSX_LAUNCH(ps, k_env3dw_step_trunc<14>, dim3(A.n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, A, (const Spatial3Dev*)e->dm3);
+    else   // the lane-per-env form (ILSX_ENV3D_LANE)
+      ILSX_LAUNCH(ps, k_env3d_step_trunc, dim3((A.n_ids + 63) / 64), dim3(64), 0, e->ctx->stream, A, (const Spatial3Dev*)e->dm3, e->scr3);
     HIPCHK(hipGetLastError());
     return ILSX_OK;
   }
@@ -926,6 +774,16 @@ static int launch_env_reset(ilsx_vecenv* e, const int* ids_dev, int n_ids, float
   if (e->engine == 2) {
     hipLaunchKernelGGL(k_cartpole_reset, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, obs,
                        e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
+    HIPCHK(hipGetLastError());
+    return ILSX_OK;
+  }
+  if (e->engine == 1 && e->hm3->obs_trunc) {
+    if (e->wave3)
+      hipLaunchKernelGGL(k_env3dw_reset_trunc, dim3(n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, (const Spatial3Dev*)e->dm3, e->qpos,
+                         e->qvel, e->n_env, ids_dev, obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
+    else
+      hipLaunchKernelGGL(k_env3d_reset_trunc, dim3((n_ids + 63) / 64), dim3(64), 0, e->ctx->stream, (const Spatial3Dev*)e->dm3, e->scr3, e->qpos,
+                         e->qvel, e->n_env, ids_dev, n_ids, obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
     HIPCHK(hipGetLastError());
     return ILSX_OK;
   }
@@ -1049,10 +907,18 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
     HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<14>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<0>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
     HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_reset, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step_trunc<23>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step_trunc<14>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_reset_trunc, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
   }
   e->hm3 = new Spatial3Dev();
   Spatial3Dev& m = *e->hm3;
   if (const char* why = e3_build_model(sm, m)) { delete e->hm3; delete e; ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_spatial: %s", why); }
+  if (m.obs_trunc && m.nv != 23 && m.nv != 14) {   // the truncated wave kernel is built for the Humanoid's and the Ant's dof counts only
+    const int nv = m.nv;
+    delete e->hm3; delete e;
+    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_spatial: obs_trunc is available for the Ant (14 dofs) and the Humanoid (23), not for %d dofs", nv);
+  }
   e->n = m.nq; e->nq = m.nq; e->nv = m.nv; e->o = m.obs_dim; e->a = m.n_act;
   const size_t N = (size_t)n_env;
   int rc = ctx_alloc(ctx, sizeof m, (void**)&e->dm3);

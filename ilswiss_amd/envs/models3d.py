@@ -245,4 +245,18 @@ def humanoid():
     return m
 
 
-MODELS3D = {"ant": ant, "humanoid": humanoid}
+def _trunc_obs(mf):
+    """The MBPO tasks (mbpo_ant.yaml / mbpo_humanoid.yaml: ant_trunc_obs, humanoid_trunc_obs): the same model whose observation
+    stops after qpos[2:] | qvel.  Reward, termination and reset are those of the full task."""
+    def make():
+        m = mf()
+        m["obs_trunc"] = 1
+        m["obs_dim"] = (m["nq"] - 2) + m["nv"]
+        return m
+    make.__name__ = mf.__name__ + "_trunc_obs"
+    return make
+
+
+ant_trunc_obs, humanoid_trunc_obs = _trunc_obs(ant), _trunc_obs(humanoid)
+
+MODELS3D = {"ant": ant, "humanoid": humanoid, "ant_trunc_obs": ant_trunc_obs, "humanoid_trunc_obs": humanoid_trunc_obs}

@@ -161,6 +161,7 @@ def spatial_struct(m):
     s.ctrl_cost, s.alive_bonus, s.vel_weight, s.z_min, s.z_max = m["ctrl_cost"], m["alive_bonus"], m["vel_weight"], m["z_min"], m["z_max"]
     for i, v in enumerate(m["init_qpos"]):
         s.init_qpos[i] = v
+    s.obs_trunc = int(bool(m.get("obs_trunc", 0)))
     return s
 
 

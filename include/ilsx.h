@@ -583,7 +583,8 @@ int ilsx_vecenv_create(ilsx_ctx* ctx, const ilsx_planar_model* model, int n_env,
  * qvel = world linear + BODY-frame angular velocity); every other link hangs off its parent by one hinge (a MuJoCo body with k
  * hinges is a chain of k links, the first k-1 massless).  Constants come from the caller (ilswiss_amd/envs/models3d.py); the
  * engine is stated in oracle/spatial_env.py; physics parity with MuJoCo is UNPINNED.  The handle is an ordinary
- * ilsx_vecenv: reset / step / rollout / evaluation entry points are the ones below. */
+ * ilsx_vecenv: reset / step / rollout / evaluation entry points are the ones below.  obs_trunc selects MBPO's truncated tasks
+ * (ant_trunc_obs / humanoid_trunc_obs): the same task observed as qpos[2:] | qvel only. */
 #define ILSX_ENV3_MAX_LINK 20
 #define ILSX_ENV3_MAX_CONTACT 32
 #define ILSX_ENV3_MAX_BODY 16
@@ -603,6 +604,9 @@ typedef struct {
   double contact_solref[2], contact_solimp[3], limit_solref[2], limit_solimp[3];
   double ctrl_cost, alive_bonus, vel_weight, z_min, z_max;
   double init_qpos[ILSX_ENV3_MAX_LINK + 6];
+  int32_t obs_trunc, pad0;   /* != 0: the observation is qpos[2:] | qvel only (MBPO's ant_trunc_obs / humanoid_trunc_obs: 27 / 45
+                              * columns); reward, termination, reset and the state layout are those of the full task; refused for trees with
+                              * other dof counts than the Ant's 14 and the Humanoid's 23.  0: as above */
 } ilsx_spatial_model;
 int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
 /* Classic control — gym 0.22's CartPoleEnv (gym/envs/classic_control/cartpole.py; rlkit/envs/envs_dict.py:2): closed-form Euler
@@ -766,7 +770,7 @@ typedef struct {
   int32_t ensemble;     /* num_nets */
   int32_t in_dim;       /* obs_dim + act_dim */
   int32_t out_dim;      /* obs_dim + 1 (BNN output_size; the head is 2 * out_dim wide) */
-  int32_t hidden;       /* net_size (<= 256) */
+  int32_t hidden;       /* net_size (<= 400; above 256 the wide kernel runs, two column slices per wave); in_dim and 2 * out_dim <= 256 */
   int32_t n_hidden;     /* num_hidden_layers, 1..ILSX_BNN_MAX_HID */
   int32_t max_batch;    /* largest ilsx_bnn_train_batch B */
   float lr, reward_scale, init_w;

@@ -1,21 +1,25 @@
 #!/usr/bin/env python
 """MBPO experiment script on the MI355X engine — the contract of the reference's run_scripts/mbpo_exp_script.py:
 `python run_scripts/mbpo_exp_script.py -e <spec.yaml> -g <gpu>`, variant keys env_specs / mbpo_params / bnn_params / sac_params /
-seed / exp_name / exp_id (load_params resumes).  The planar tasks (hopper, walker, halfcheetah) at any BNN width up to 256; the
-reference's Ant / Humanoid specs use *_trunc_obs envs this project does not have and are refused."""
+seed / exp_name / exp_id (load_params resumes).  The planar tasks (hopper, walker, halfcheetah) and the truncated-observation 3-D
+tasks of the reference's Ant / Humanoid specs (ant_trunc_obs, humanoid_trunc_obs: qpos[2:] | qvel), at any BNN width up to 400.
+Plain `ant` / `humanoid` are refused: the terminal predicates are written for the truncated layout, and a model over the 111- /
+376-wide observations is not wanted."""
 from _common import flatten_spec, ia, main, make_envs, start, train  # noqa: F401
 
 from ilswiss_amd.envs.terminals import get_terminal_func
 from ilswiss_amd.mbpo import BNN, MBPO, BNNTrainer
 
-# env_name -> the terminal predicate's name (rlkit/envs/terminals.py); the planar tasks only
-TERMINALS = dict(hopper="hopper", walker="walker2d", walker2d="walker2d", halfcheetah="halfcheetah", half_cheetah="halfcheetah")
+# env_name -> the terminal predicate's name (rlkit/envs/terminals.py): the planar tasks and the truncated-observation 3-D tasks
+TERMINALS = dict(hopper="hopper", walker="walker2d", walker2d="walker2d", halfcheetah="halfcheetah", half_cheetah="halfcheetah",
+                 ant_trunc_obs="ant", humanoid_trunc_obs="humanoid")
 
 
 def experiment(variant, gpu=0, log_dir=None):
     name = variant["env_specs"]["env_name"]
     if name not in TERMINALS:
-        raise NotImplementedError(f"MBPO on env_name={name!r}: the device model rollout covers {sorted(TERMINALS)}")
+        hint = f" (use {name}_trunc_obs, the task the reference's MBPO spec names)" if name in ("ant", "humanoid") else ""
+        raise NotImplementedError(f"MBPO on env_name={name!r}: the device model rollout covers {sorted(TERMINALS)}{hint}")
     ctx = start(variant, gpu)
     training_env, eval_env, env = make_envs(variant, ctx)
     obs_dim, action_dim = training_env.obs_dim, training_env.act_dim

@@ -7,7 +7,9 @@
     early stopping, 4 rollouts of 1e5 rows at length `--rollout-length`, and 1000 SAC steps of B = 256 (20 per env step x 1000 env steps
     in the reference; this leg times one model training + one rollout and adds the SAC steps from bench.py's rate, see --sac-us);
   - baseline: the same train step as a torch-ROCm restatement on the same GPU (tests/mbpo_restatement.py's arithmetic).
-Device-event timing after warm-up."""
+Device-event timing after warm-up; the train-batch windows are taken --repeats times, library and restatement alternating, and the
+JSON carries every window, the median and the spread (max - min) / median.  --hidden / --obs / --act / --terminal choose another shape
+(the Humanoid spec: --hidden 400 --obs 45 --act 17 --terminal humanoid); --spec chooses the shipped spec --epoch runs."""
 import argparse
 import ctypes as C
 import json
@@ -42,7 +44,7 @@ def timed_epochs(args):
     import tempfile
 
     import yaml
-    spec = yaml.safe_load(open(os.path.join(ROOT, "exp_specs", "mbpo", "mbpo_hopper_hip.yaml")))
+    spec = yaml.safe_load(open(os.path.join(ROOT, "exp_specs", "mbpo", args.spec)))
     spec["constants"]["mbpo_params"]["num_epochs"] = args.epochs
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "spec.yaml")
@@ -52,7 +54,7 @@ def timed_epochs(args):
                        stdout=subprocess.DEVNULL)
         rows = list(csv.DictReader(open(glob.glob(os.path.join(d, "logs", "*", "*", "progress.csv"))[0])))
     t = [float(r["Epoch Time (s)"]) for r in rows]
-    res = dict(metric="mbpo_hopper_epoch_s", epoch_s=t, epoch_s_after_first=round(float(np.mean(t[1:])), 3) if len(t) > 1 else None,
+    res = dict(metric=args.spec.replace("_hip.yaml", "") + "_epoch_s", spec=args.spec, epoch_s=t, epoch_s_after_first=round(float(np.mean(t[1:])), 3) if len(t) > 1 else None,
                train_time_s=[float(r["Train Time (s)"]) for r in rows], sample_time_s=[float(r["Sample Time (s)"]) for r in rows],
                mean_rollout_length=[float(r["mean_rollout_length"]) for r in rows], bnn_loss=[float(r["BNN Loss"]) for r in rows])
     line = json.dumps(res)
@@ -73,6 +75,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--epoch", action="store_true", help="instead: time MBPO Hopper epochs at the reference schedule through the run script")
     ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--spec", default="mbpo_hopper_hip.yaml", help="with --epoch: the spec under exp_specs/mbpo/ to run")
+    ap.add_argument("--hidden", type=int, default=200, help="ensemble hidden width")
+    ap.add_argument("--obs", type=int, default=11, help="observation width (Hopper 11, ant_trunc_obs 27, humanoid_trunc_obs 45)")
+    ap.add_argument("--act", type=int, default=3, help="action width (Hopper 3, Ant 8, Humanoid 17)")
+    ap.add_argument("--terminal", default="hopper", help="terminal predicate of the model step")
+    ap.add_argument("--repeats", type=int, default=3, help="timed train-batch windows per implementation, alternating")
     args = ap.parse_args()
     if args.epoch:
         return timed_epochs(args)
@@ -86,7 +94,7 @@ def main():
     from ilswiss_amd.replay import SimpleReplayBuffer
 
     ctx = ia.Context(0, seed=3)
-    E, o, a, H, nh, B = 7, 11, 3, 200, 4, 256
+    E, o, a, H, nh, B = 7, args.obs, args.act, args.hidden, 4, 256
     rng = np.random.default_rng(0)
     N = args.real_rows
     obs = rng.normal(0, 1, (N, o)).astype(np.float32)
@@ -100,18 +108,17 @@ def main():
                     logger=type("Q", (), {"log": staticmethod(lambda s: None)})())
     n_tab = B * (args.steps + args.warmup)
     table = ctx.from_numpy(rng.integers(0, N, (E, n_tab)).astype(np.int32), np.int32)
-    for s in range(args.warmup):
-        tr._train_batch(rb, table, s * B, n_tab, B)
-    ctx.sync()
     import torch.cuda as tc
-    ev0, ev1 = tc.Event(enable_timing=True), tc.Event(enable_timing=True)
     stream = tc.ExternalStream(ctx.stream)
-    ev0.record(stream)
-    for s in range(args.warmup, args.warmup + args.steps):
-        tr._train_batch(rb, table, s * B, n_tab, B)
-    ev1.record(stream)
-    ev1.synchronize()
-    us_train = ev0.elapsed_time(ev1) * 1e3 / args.steps
+
+    def lib_window(first, count, timed):
+        ev0, ev1 = tc.Event(enable_timing=True), tc.Event(enable_timing=True)
+        ev0.record(stream)
+        for s in range(first, first + count):
+            tr._train_batch(rb, table, s * B, n_tab, B)
+        ev1.record(stream)
+        ev1.synchronize()
+        return ev0.elapsed_time(ev1) * 1e3 / count if timed else None
     fl = flops_per_step(E, o + a, H, nh, o + 1, B)
 
     # torch-ROCm restatement of the same step on the same GPU
@@ -130,24 +137,33 @@ def main():
         opt.zero_grad()
         loss.backward()
         opt.step()
-    for s in range(args.warmup):
-        torch_step(s)
-    torch.cuda.synchronize()
-    e0, e1 = tc.Event(enable_timing=True), tc.Event(enable_timing=True)
-    e0.record()
-    for s in range(args.warmup, args.warmup + args.steps):
-        torch_step(s)
-    e1.record()
-    e1.synchronize()
-    us_torch = e0.elapsed_time(e1) * 1e3 / args.steps
+
+    def torch_window(first, count, timed):
+        e0, e1 = tc.Event(enable_timing=True), tc.Event(enable_timing=True)
+        e0.record()
+        for s in range(first, first + count):
+            torch_step(s)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / count if timed else None
+    lib_window(0, args.warmup, False)
+    torch_window(0, args.warmup, False)
+    lib_us, torch_us = [], []
+    for _ in range(max(1, args.repeats)):      # the same index windows every time: the rows differ, the work does not
+        lib_us.append(lib_window(args.warmup, args.steps, True))
+        torch_us.append(torch_window(args.warmup, args.steps, True))
+    us_train, us_torch = float(np.median(lib_us)), float(np.median(torch_us))
+
+    def spread(v):
+        return round((max(v) - min(v)) / float(np.median(v)), 4)
 
     # model step at 1e5 rows
     n = args.rows
     pol = ia.ReparamTanhMultivariateGaussianPolicy([256, 256], o, a, ctx=ctx)
     mring = SimpleReplayBuffer(10 * n, o, a, ctx=ctx)
-    kind = terminal_kind(get_terminal_func("hopper"))
+    kind = terminal_kind(get_terminal_func(args.terminal))
     o0 = np.zeros((n, o), np.float32)
-    o0[:, 0] = 1.25
+    o0[:, 0] = dict(ant=0.6).get(args.terminal, 1.25)      # a height inside every task's healthy range
     cur, nxt = ctx.from_numpy(o0), ctx.empty((n, o))
     el = np.arange(5, dtype=np.int32)
     ns = C.c_int()
@@ -173,11 +189,14 @@ def main():
     t_model = time.perf_counter() - t0
     t_rollout = args.rollout_length * dt_step
     epoch_s = 4 * (t_model + t_rollout) + 1000 * 20 * args.sac_us * 1e-6
-    res = dict(metric="mbpo_bnn_train_batch_us", bnn_train_batch_us=round(us_train, 2), gflop_per_step=round(fl / 1e9, 3),
+    res = dict(metric="mbpo_bnn_train_batch_us", shape=dict(E=E, obs=o, act=a, hidden=H, n_hidden=nh, B=B, terminal=args.terminal),
+               bnn_train_batch_us=round(us_train, 2), bnn_train_batch_us_windows=[round(v, 2) for v in lib_us],
+               bnn_train_batch_spread=spread(lib_us), torch_rocm_train_batch_us_windows=[round(v, 2) for v in torch_us],
+               torch_rocm_train_batch_spread=spread(torch_us), gflop_per_step=round(fl / 1e9, 3),
                mfma_fp32_peak_share=round(fl / (us_train * 1e-6) / FP32_MFMA_PEAK, 4), torch_rocm_train_batch_us=round(us_torch, 2),
                speedup_vs_torch=round(us_torch / us_train, 2), model_step_rows_per_s=round(n / dt_step, 1), model_step_ms=round(dt_step * 1e3, 3),
                model_train_s=round(t_model, 3), model_train_epochs=out["epochs"], model_train_grad_steps=out["grad_updates"],
-               real_rows=N, rollout_length=args.rollout_length, hopper_epoch_s_estimate=round(epoch_s, 2))
+               real_rows=N, rollout_length=args.rollout_length, hopper_epoch_s_estimate=round(epoch_s, 2) if args.terminal == "hopper" else None)
     line = json.dumps(res)
     print(line, flush=True)
     if args.out:
