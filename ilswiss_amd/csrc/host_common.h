@@ -157,7 +157,8 @@ int launch_fwd(ilsx_ctx* ctx, const FwdArgs& A, int H, int act, int KP, int cs =
 int launch_bwd_dx(ilsx_ctx* ctx, const BwdArgs& A, int H, int act, int cs = 1);
 int launch_policy_finish(ilsx_ctx* ctx, const PolicyFinishArgs& P);
 // merged phase kernels of the single-run SAC step (kernels.h); phase_fits: every workgroup of such a launch is resident at once
-bool phase_fits(ilsx_ctx* ctx, int rows, int H, int cs, int ntasks);
+bool phase_fits(ilsx_ctx* ctx, int rows, int H, int cs, int ntasks, bool own_rows = false);
+bool phase_own_rows(ilsx_ctx* ctx, int rows, int H, int cs, int ntasks);   // phase A: the target critics on grid rows of their own (PhaseAArgs::own_rows)
 // The phase kernels' descriptor blocks in CONSTANT memory (kernels.h g_phase_a_tab / g_phase_c_tab, `CT` instances): one slot per agent, the
 // host's copy of what the slot holds.  slot < 0: none (table full, or ILSX_PHASE_CT=0): the block travels in the kernel arguments as before.
 struct PhaseConst {

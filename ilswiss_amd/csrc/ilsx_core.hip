@@ -553,17 +553,26 @@ void phase_wgs_per_cu(int H, int cs, int* occ_a, int* occ_c) {
   }
   *occ_a = oa[i]; *occ_c = oc[i];
 }
-bool phase_fits(ilsx_ctx* ctx, int rows, int H, int cs, int ntasks) {
+bool phase_fits(ilsx_ctx* ctx, int rows, int H, int cs, int ntasks, bool own_rows) {
   const int n_cu = device_cus(ctx);
   if (!((H == 256 && cs == 4) || (H == 128 && cs == 2))) return false;
   const int tiles = (rows + 15) / 16, work = tiles * ntasks * cs;
   // (padding tiles and the idle part of the bookkeeping rows exit at once.)  Two conditions: the launch is the latency shape the phase kernels
-  // are built for — at most one working workgroup per CU — and EVERY workgroup another one waits for is resident at once by the device's own
-  // occupancy figure, not by assumption: phase A = its four task rows plus the bookkeeping row's tail workgroup, whose flag the critics'
-  // backward waits for (+1); phase C = its three working rows (nobody waits for its bookkeeping row, which may run after them)
+  // are built for — at most one stage-1 workgroup per CU — and EVERY workgroup another one waits for is resident at once by the device's own
+  // occupancy figure, not by assumption: phase A = its working rows — the four task rows, and with the target critics on rows of their own
+  // (PhaseAArgs::own_rows) those two as well — plus the bookkeeping row's tail workgroup, whose flag the critics' backward waits for (+1);
+  // phase C = its three working rows (nobody waits for its bookkeeping row, which may run after them)
   int occ_a = 1, occ_c = 1;
   phase_wgs_per_cu(H, cs, &occ_a, &occ_c);
-  return tiles <= PHASE_MAX_TILES && work <= n_cu && work + 1 <= occ_a * n_cu && tiles * 3 * cs <= occ_c * n_cu;
+  const int work_a = work + (own_rows ? tiles * 2 * cs : 0);
+  return tiles <= PHASE_MAX_TILES && work <= n_cu && work_a + 1 <= occ_a * n_cu && tiles * 3 * cs <= occ_c * n_cu;
+}
+// Phase A's mapping for this shape: the target critics on rows of their own where those fit beside the rest (two workgroups per CU: a
+// compiler that takes the kernel past 256 registers costs this mapping, not the phase path).  ILSX_PHASE_OWN_ROWS=0 keeps them on the
+// workgroups of the policy rows; read per call, as ILSX_NO_PHASE is: tests switch it.
+bool phase_own_rows(ilsx_ctx* ctx, int rows, int H, int cs, int ntasks) {
+  const char* e = getenv("ILSX_PHASE_OWN_ROWS");
+  return !(e && atoi(e) == 0) && phase_fits(ctx, rows, H, cs, ntasks, true);
 }
 
 // ---- the phase kernels' descriptor blocks in constant memory (kernels.h g_phase_a_tab / g_phase_c_tab)
@@ -618,7 +627,7 @@ int launch_phase_a(ilsx_ctx* ctx, const PhaseAArgs& P0, int H, int act, int KPma
   P.dbg = upload_only ? nullptr : ctx->dbg_next();   // (a dry pass takes no slab of the trace buffer)
   if (P.b1.ga_parts < 1) P.b1.ga_parts = 1;
   const int tiles = (P.f1.rows + 15) / 16;
-  dim3 grid((tiles + 7) & ~7, 5, cs), block(4 * H / cs);
+  dim3 grid((tiles + 7) & ~7, P.own_rows ? 7 : 5, cs), block(4 * H / cs);   // y: the four tasks of stage 1, the bookkeeping row, the target critics' own rows
   const size_t lds = phase_lds_bytes(H, KPmax, cs);
   const bool use_ct = ct && phase_const_ready(ctx, ct, P, key, ct->a, ct->valid_a, ct->key_a, HIP_SYMBOL(g_phase_a_tab));
   if (upload_only) return ILSX_OK;

@@ -75,7 +75,7 @@ struct ilsx_sac {
   hipGraphExec_t graph = nullptr;
   ilsx_replay* graph_rb = nullptr;
   int graph_B = 0;
-  bool graph_defer = false, graph_phase = false;
+  bool graph_defer = false, graph_phase = false, graph_own = false;
   // split runs: the step as three captured segments with the two all-reduces between them (sac_split_segments)
   hipGraphExec_t seg_graph[3] = {nullptr, nullptr, nullptr};
   ilsx_replay* seg_rb = nullptr;
@@ -452,6 +452,7 @@ static int sac_dw(ilsx_sac* s, const DwArgs& table, int rows, const AdamFuse* F)
 
 // What the phase launches' descriptor blocks are built from besides the agent's fixed allocations: the ring they draw from, the batch, and the
 // step-form flags.  Two builds under the same key give the same blocks (PhaseConst::key_a / key_c); never 0.
+static bool sac_own_rows(const ilsx_sac* s) { return phase_own_rows(s->ctx, s->B, s->Lq.cfg.hidden, s->cs, 4); }   // phase A's mapping for the step being built
 static unsigned long long sac_phase_key(const ilsx_sac* s) {
   unsigned long long k = 1469598103934665603ull;
   auto mix = [&k](unsigned long long v) { k = (k ^ v) * 1099511628211ull; };
@@ -460,6 +461,7 @@ static unsigned long long sac_phase_key(const ilsx_sac* s) {
   mix(rb ? (unsigned long long)rb->rec : 0); mix(rb ? (unsigned long long)rb->seed : 0); mix(rb ? (unsigned long long)rb->rng_stream : 0);
   mix((unsigned long long)s->B); mix(s->defer_tail ? 1 : 0); mix(s->eps_explicit ? 1 : 0); mix(s->fuse_now ? 1 : 0); mix((unsigned long long)s->cs);
   mix((unsigned long long)(uintptr_t)s->tail_dev); mix((unsigned long long)(uintptr_t)s->slab);
+  mix(sac_own_rows(s) ? 1 : 0);
   return k ? k : 1;
 }
 
@@ -530,6 +532,7 @@ static int sac_critic_backward(ilsx_sac* s) {
     }
     if (s->phase_now) {
       PA.b1 = A; PA.flags = s->phase_flags; PA.err = s->phase_err;
+      PA.own_rows = sac_own_rows(s) ? 1 : 0;
       {   // pi(s) is finished inside this launch (kernels.h policy_fin_tile): the policy phase starts from finished actions
         FwdArgs Fz;
         memset(&Fz, 0, sizeof Fz);
@@ -1149,14 +1152,15 @@ static int sac_train_from_replay_once(ilsx_sac* s, ilsx_replay* rb, int n_steps,
   } else {
     const bool phase = sac_phase_ok(s, B);
     s->phase_last = phase;
+    const bool own = phase && sac_own_rows(s);   // phase A's mapping is part of what the cached graph holds (grid, descriptor)
     // The phase kernels' descriptor blocks into this agent's constant-memory slots — before a capture begins, and before EVERY replay of a
     // cached graph too: between two calls another step form of the same agent (an explicit-batch step, the adversarial-IRL loop, a profiled
     // window: direct launches under another state key) may have put ITS blocks there, and the graph's launches would read those.  The dry pass
     // costs a few host microseconds when the slots are current.
     static const bool no_reprime = getenv("ILSX_PHASE_CT_NO_REPRIME") != nullptr;   // test aid: shows what the re-prime is for (tests/test_hip_parity.py)
-    const bool rebuild = !s->graph || s->graph_rb != rb || s->graph_B != B || s->graph_defer != s->defer_tail || s->graph_phase != phase;
+    const bool rebuild = !s->graph || s->graph_rb != rb || s->graph_B != B || s->graph_defer != s->defer_tail || s->graph_phase != phase || s->graph_own != own;
     if (phase && (rebuild || !no_reprime)) ILSX_TRY(sac_phase_const_prime(s, rb));
-    if (!s->graph || s->graph_rb != rb || s->graph_B != B || s->graph_defer != s->defer_tail || s->graph_phase != phase) {
+    if (rebuild) {
       if (s->graph) { hipGraphExecDestroy(s->graph); s->graph = nullptr; }
       hipGraph_t g = nullptr;
       HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -1167,7 +1171,7 @@ static int sac_train_from_replay_once(ilsx_sac* s, ilsx_replay* rb, int n_steps,
       e = hipGraphInstantiate(&s->graph, g, nullptr, nullptr, 0);
       hipGraphDestroy(g);
       if (e != hipSuccess) { s->graph = nullptr; ILSX_FAIL(ILSX_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e)); }
-      s->graph_rb = rb; s->graph_B = B; s->graph_defer = s->defer_tail; s->graph_phase = phase;
+      s->graph_rb = rb; s->graph_B = B; s->graph_defer = s->defer_tail; s->graph_phase = phase; s->graph_own = own;
     }
     for (int i = 0; i < n_steps; ++i) {
       if (stats && i == n_steps - 1) ILSX_TRY(sac_request_stats(s));

@@ -1130,7 +1130,13 @@ __global__ __launch_bounds__(4 * H / CS, (MT > 1 ? ILSX_MT_WAVES : GRP == 3 ? IL
 #define PHASE_FLAG_WORDS ((PHASE_NFLAGS + PHASE_MAX_TILES) * 32)
 struct PhaseAArgs {
   FwdArgs f1, f2; BwdArgs b1; unsigned* flags; int* err; unsigned long long* dbg;
-  PolicyFinishArgs fin_pi; int fin_pi_on, pad;   // finish pi(s) (task 3 of stage 1) here, on the lead slice of the first critic's backward row (policy_fin_tile)
+  PolicyFinishArgs fin_pi; int fin_pi_on;   // finish pi(s) (task 3 of stage 1) here, on the lead slice of the first critic's backward row (policy_fin_tile)
+  // own_rows (workgroup-uniform): the target critics (stage 2) run on grid rows of their own, y = 5 / 6, which request their weights at
+  // entry, wait for the tile's policy slices and run the one stage; the workgroups of y = 0 / 3 then return after their stage-1 arrival.
+  // A workgroup that starts polling right behind a weight burst of its own gets the poll, the payload and buffer_inv back only after the
+  // burst has landed (vector loads return in order): on these rows the burst is long through when the producers arrive.  0 = stage 2
+  // on the workgroups of y = 0 / 3 (grid.y = 5).
+  int own_rows;
 };
 struct PhaseCArgs {
   FwdArgs f3; BwdArgs b2, b3; unsigned* flags; int* err; unsigned long long* dbg;
@@ -1177,6 +1183,13 @@ __device__ __forceinline__ unsigned xcc_id() {
   unsigned v;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
   return v & 15u;
+}
+// which CU: the XCD and, from HW_REG_HW_ID, shader engine / array / CU (bits 15:8).  Measurement build only (tools/phase_gantt.py: which
+// workgroups of a launch share a CU, and with it a memory queue)
+__device__ __forceinline__ unsigned cu_key() {
+  unsigned v;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
+  return (xcc_id() << 8) | ((v >> 8) & 255u);
 }
 // every working workgroup of a phase launch ORs its XCD into its tile's mask (fire and forget): more than one bit in a mask = the
 // placement the exchange relies on did not hold, the host fails the call (ilsx_sac_train_from_replay) and falls back
@@ -1237,7 +1250,8 @@ __device__ __forceinline__ void policy_fin_tile(const PolicyFinishArgs& P, int r
 }
 
 // Phase A: stage 1 = fwd{pi(s') | Q1(s,a) | Q2(s,a) | pi(s)} (tasks y = 0..3, rows drawn from the replay ring);
-//          stage 2 = fwd{TQ1, TQ2 (s', a')} on the workgroups of y = 0 / 3 (prologue: finish pi(s'); next_obs as the policy task published it);
+//          stage 2 = fwd{TQ1, TQ2 (s', a')} on rows of their own, y = 5 / 6 (PhaseAArgs::own_rows), or on the workgroups of y = 0 / 3
+//                    (prologue: finish pi(s'); next_obs as the policy task published it);
 //          stage 3 = bwd{Q1, Q2 <- TD target} on the workgroups of y = 1 / 2;  y = 4: the deferred tail of the previous step.
 // CT: the descriptor block is read from a `__constant__` copy (g_phase_a_tab[slot], uploaded once when the step is built) instead of the
 // kernel-argument segment: see g_fwd_tab above — fields come as scalar loads where they are used instead of sitting in (and spilling out
@@ -1266,39 +1280,47 @@ __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_a(const PhaseAArgs Pk,
   if (bx * 16 >= P.f1.rows) return;   // padding tiles (grid.x is a multiple of 8): no member of such a tile takes part
   unsigned* f1 = P.flags + (3 * bx) * 32;
   unsigned* f2 = P.flags + (3 * bx + 1) * 32;
+  unsigned* f0 = P.flags + (3 * bx + 2) * 32;
+  const bool own = y >= 5;   // a target critic's row of its own (PhaseAArgs::own_rows: grid.y = 7)
   ILSX_STAMP(P.dbg, 0);
 #if defined(ILSX_STAMPS) && defined(ILSX_STAMPS_FINE)
   if (P.dbg && threadIdx.x == 0 && (y == 1 || y == 2)) P.dbg[(size_t)ILSX_WG_LINEAR * ILSX_TRACE_SLOTS + 5] = clock64();   // shader clock (s_memtime) beside the 100 MHz stamps
 #endif
   xch_mark_xcd(P.flags + PHASE_MASK_WORD(bx));
-  {
-    const FwdArgs& A = P.f1;
-    const FwdTask& T = A.t[y];
-    const bool first_task = y == 0;
+#if defined(ILSX_STAMPS) && !defined(ILSX_STAMPS_FINE)
+  if (P.dbg && threadIdx.x == 0 && ILSX_WG_LINEAR < ILSX_TRACE_MAXWG) P.dbg[(size_t)ILSX_WG_LINEAR * ILSX_TRACE_SLOTS + 7] = 0x10000u | cu_key();   // slot 7: not a time
+#endif
+  if (!own) {
+    {
+      const FwdArgs& A = P.f1;
+      const FwdTask& T = A.t[y];
+      const bool first_task = y == 0;
 #define XCH_HOOK_STAGE
 #define XCH_HOOK_FIN
 #include "fwd_split_tile.inc"
 #undef XCH_HOOK_STAGE
 #undef XCH_HOOK_FIN
-  }
-  ILSX_STAMP(P.dbg, 1);
-  unsigned* f0 = P.flags + (3 * bx + 2) * 32;
-  if (y == 0) {   // the policy-on-next_obs slices: what the target critics wait for (they do not need the critics' own stage 1)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      __hip_atomic_fetch_add(f0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(f1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-  } else {
-    xch_arrive(f1);
+    ILSX_STAMP(P.dbg, 1);
+    if (y == 0) {   // the policy-on-next_obs slices: what the target critics wait for (they do not need the critics' own stage 1)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        __hip_atomic_fetch_add(f0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(f1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    } else {
+      xch_arrive(f1);
+    }
+    ILSX_STAMP(P.dbg, 2);
+    if (P.own_rows && (y == 0 || y == 3)) return;   // workgroup-uniform: rows 5 / 6 run the target critics
   }
-  ILSX_STAMP(P.dbg, 2);
-  if (y == 0 || y == 3) {
+  if (y == 0 || y == 3 || own) {
     {   // the target critic's weights are on their way while the tile's policy slices finish; next_obs = the rows stage 1 published
       const FwdArgs& A = P.f2;
-      const FwdTask& T = A.t[y == 0 ? 0 : 1];
-      const bool first_task = y == 0;
+      const int tq = own ? y - 5 : (y == 0 ? 0 : 1);
+      const FwdTask& T = A.t[tq];
+      const bool first_task = tq == 0;
 #define XCH_HOOK_STAGE ILSX_STAMP_SYNC(P.dbg, 7); xch_wait(f0, CS, P.err); ILSX_STAMP(P.dbg, 3);
 #define XCH_HOOK_FIN
 #define XCH_FINE_DBG P.dbg

@@ -38,4 +38,6 @@ for rnd in range(10):   # interleaved rounds, order reversed every other round: 
         res.setdefault(label, []).extend(vals)
 for k, v in res.items():
     v = sorted(v)
-    print(f"{k:24s} min {v[0]:6.2f}  median {v[len(v)//2]:6.2f}  mean {sum(v)/len(v):6.2f}  max {v[-1]:6.2f}  us/step   ({len(v)} x {STEPS} steps)")
+    mean = sum(v) / len(v)
+    sd = (sum((x - mean) ** 2 for x in v) / max(len(v) - 1, 1)) ** 0.5
+    print(f"{k:24s} min {v[0]:6.2f}  median {v[len(v)//2]:6.2f}  mean {mean:6.2f}  sd {sd:5.2f}  max {v[-1]:6.2f}  us/step   ({len(v)} x {STEPS} steps)")

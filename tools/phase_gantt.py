@@ -2,6 +2,11 @@
 (make STAMPS=1): per launch and per task row, the median time of every stage boundary after the launch's first workgroup start.
 
     python tools/phase_gantt.py
+
+Under the rows, per launch, the hand-offs between the stages: for every consuming workgroup the time from the LAST arrival of its tile's
+producers to the return of its wait.  Phase A with the target critics on rows of their own (PhaseAArgs::own_rows) has rows 5 / 6; their
+hand-off is also split by the row of the workgroup they share a CU with (slot 7 of the measurement build holds XCD / CU, not a time).
+ILSX_GANTT_NO_BUILD=1 with ILSX_LIB set traces that library (another commit's measurement build) instead of building this tree's.
 """
 import ctypes as C
 import os
@@ -14,12 +19,30 @@ os.environ["ILSX_NO_GRAPH"] = "1"
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if not os.environ.get("ILSX_GANTT_NO_BUILD"):
     subprocess.check_call(["make", "-C", os.path.join(_ROOT, "ilswiss_amd", "csrc"), "-j8", "STAMPS=1"], stdout=subprocess.DEVNULL)
-os.environ["ILSX_LIB"] = os.path.join(_ROOT, "ilswiss_amd", "libilsx_stamps.so")
+if not (os.environ.get("ILSX_GANTT_NO_BUILD") and os.environ.get("ILSX_LIB")):
+    os.environ["ILSX_LIB"] = os.path.join(_ROOT, "ilswiss_amd", "libilsx_stamps.so")
 sys.path.insert(0, _ROOT)
 import ilswiss_amd as ia  # noqa: E402
 from ilswiss_amd import _lib  # noqa: E402
 
 MAXWG, SLOTS, MAXL = 2048, 8, 14
+ROWS_A = {0: "pi(s')", 1: "Q1 fwd, bwd", 2: "Q2 fwd, bwd", 3: "pi(s)", 5: "TQ1, own row", 6: "TQ2, own row"}
+ROWS_A_OLD = {0: "pi(s') then TQ1", 1: "Q1 fwd, bwd", 2: "Q2 fwd, bwd", 3: "pi(s) then TQ2"}
+ROWS_C = {0: "Q1 fwd, bwd", 1: "Q2 fwd, bwd", 2: "pi bwd"}
+
+
+def handoff(name, tl, bx, prod, pslot, cons, cslot, s0):
+    """per consuming workgroup: its wait's return minus the last arrival among its tile's producers"""
+    d = []
+    for w in np.flatnonzero(cons):
+        p = prod & (bx == bx[w]) & (tl[:, pslot] > 0)
+        if p.any() and tl[w, cslot] > 0:
+            d.append(tl[w, cslot] - tl[p, pslot].max())
+    if d:
+        d = np.array(d)
+        print(f"    hand-off {name}: last arrival -> wait returns  median {np.median(d):5.2f}  max {d.max():5.2f} us  ({d.size} workgroups;"
+              f" last arrival of all @ {tl[prod & (tl[:, pslot] > 0), pslot].max() - s0:5.2f}, returns median @ {np.median(tl[cons & (tl[:, cslot] > 0), cslot]) - s0:5.2f})")
+    return d
 ctx = ia.Context(0, seed=0)
 o, a, H, B, CAP = 11, 3, 256, 256, 100_000
 rng = np.random.default_rng(0)
@@ -54,17 +77,21 @@ for rep in range(2):
         kind = "ACAC"[L % 4] if False else ("A", "D1", "C", "D2")[L % 4]
         print(f"launch {L} ({kind}): {live.size} workgroups, begins {s0 - base:7.2f} us after the step's first launch")
         if kind in ("A", "C"):
-            ny = 5 if kind == "A" else 4
+            own = kind == "A" and live.max() >= 16 * 5 * 4   # grid.y = 7: the target critics on rows of their own
+            ny = (7 if own else 5) if kind == "A" else 4
+            names = (ROWS_A if own else ROWS_A_OLD) if kind == "A" else ROWS_C
             y = (live // 16) % ny
-            for yy in range(ny - 1):
+            cu = buf_raw[L][live, 7]
+            has_cu = bool(((cu >> 16) == 1).all())   # slot 7 of the measurement build: 0x10000 | XCD << 8 | SE / SH / CU, not a time
+            for yy in sorted(names):
                 m = live[y == yy]
                 row = []
-                for sl in range(8):
+                for sl in range(7 if has_cu else 8):
                     v = t[L][m, sl]
                     ok = v > 0
                     if ok.any():
                         row.append(f"s{sl}@{np.median(v[ok]) - s0:6.2f}(max {v[ok].max() - s0:6.2f})")
-                print(f"    task row {yy}: " + "  ".join(row))
+                print(f"    task row {yy} ({names[yy]}): " + "  ".join(row))
                 if kind == "A" and yy in (1, 2):     # fine build: slots 5 / 6 hold the shader clock at the same two points as stamps 0 / 4
                     raw = buf_raw[L][m]
                     ok = (raw[:, 5] > 0) & (raw[:, 6] > 0) & (raw[:, 4] > 0)
@@ -72,6 +99,23 @@ for rep in range(2):
                         cyc = (raw[ok, 6] - raw[ok, 5]).astype(np.float64)
                         us = (raw[ok, 4] - raw[ok, 0]).astype(np.float64) * 0.01
                         print(f"        shader clock over the workgroup's life: {np.median(cyc / us):.0f} MHz (s_memtime cycles / 100 MHz stamps)")
+            tl, bx = t[L][live], live % 16
+            if kind == "A":
+                tq = (y >= 5) if own else ((y == 0) | (y == 3))
+                handoff("pi(s') -> target critics", tl, bx, y == 0, 2, tq, 3, s0)
+                if own and has_cu:
+                    for part, label in ((1, "a critic row (1 / 2)"), (0, "a policy row (0 / 3)"), (-1, "no stage-1 workgroup")):
+                        sel = np.zeros(live.size, bool)
+                        for w in np.flatnonzero(tq):
+                            mates = y[(cu == cu[w]) & (y < 5)]
+                            kind_w = -1 if not mates.size else (1 if ((mates == 1) | (mates == 2)).any() else 0)
+                            sel[w] = kind_w == part
+                        if sel.any():
+                            handoff(f"    ... sharing a CU with {label}", tl, bx, y == 0, 2, sel, 3, s0)
+                handoff("target critics -> critics' backward", tl, bx, tq, 5, (y == 1) | (y == 2), 3, s0)
+            else:
+                handoff("Q forward -> Q backward", tl, bx, y < 2, 1, y < 2, 2, s0)
+                handoff("Q backward -> pi backward", tl, bx, y < 2, 3, y == 2, 4, s0)
         else:
             e = t[L][live, 7]
             p1, p2 = t[L][live, 1], t[L][live, 2]
