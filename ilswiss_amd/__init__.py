@@ -13,3 +13,4 @@ from .sac import SoftActorCritic, SoftActorCriticGroup  # noqa: F401
 from .trainer import DeviceTrainer, Trainer  # noqa: F401
 from .mbpo import BNN, MBPO, BNNTrainer, FakeEnv  # noqa: F401
 from .discrete_sac import DiscreteSoftActorCritic  # noqa: F401
+from .ddpg import DDPG, GaussianStrategy, MlpPolicy, OUStrategy, PolicyWrappedWithExplorationStrategy  # noqa: F401

@@ -118,6 +118,24 @@ class Td3Stats(C.Structure):  # ilsx_td3_stats
                 ("bellman1", C.c_float * 4), ("bellman2", C.c_float * 4), ("policy_action", C.c_float * 4)]
 
 
+class DdpgCfg(C.Structure):  # ilsx_ddpg_cfg
+    _fields_ = [("discount", C.c_float), ("policy_lr", C.c_float), ("qf_lr", C.c_float), ("qf_weight_decay", C.c_float),
+                ("soft_target_tau", C.c_float), ("use_soft_update", C.c_int32), ("target_update_period", C.c_int32),
+                ("policy_pre_activation_weight", C.c_float), ("min_q_value", C.c_float), ("max_q_value", C.c_float),
+                ("max_act", C.c_float), ("max_batch", C.c_int32)]
+
+
+class DdpgStats(C.Structure):  # ilsx_ddpg_stats
+    _fields_ = [("qf_loss", C.c_float), ("policy_loss", C.c_float), ("raw_policy_loss", C.c_float),
+                ("preactivation_policy_loss", C.c_float), ("q_pred", C.c_float * 4), ("q_target", C.c_float * 4),
+                ("bellman", C.c_float * 4), ("policy_action", C.c_float * 4)]
+
+
+class ExploreCfg(C.Structure):  # ilsx_explore_cfg
+    _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("mu", C.c_double), ("theta", C.c_double), ("max_sigma", C.c_double),
+                ("min_sigma", C.c_double), ("decay_period", C.c_double), ("low", C.c_double), ("high", C.c_double)]
+
+
 class DsacCfg(C.Structure):  # ilsx_dsac_cfg
     _fields_ = [("discount", C.c_float), ("reward_scale", C.c_float), ("alpha", C.c_float), ("soft_target_tau", C.c_float),
                 ("policy_lr", C.c_float), ("qf_lr", C.c_float), ("beta_1", C.c_float), ("max_batch", C.c_int32)]
@@ -195,6 +213,17 @@ PROTOTYPES = {
     "ilsx_td3_train_from_replay": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(Td3Stats)]),
     "ilsx_td3_get_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
     "ilsx_td3_set_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_ddpg_create": (C.c_int, [vp, C.POINTER(DdpgCfg), vp, vp, C.POINTER(vp)]),
+    "ilsx_ddpg_destroy": (C.c_int, [vp]),
+    "ilsx_ddpg_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(DdpgStats)]),
+    "ilsx_ddpg_train_from_replay": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(DdpgStats)]),
+    "ilsx_ddpg_get_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_ddpg_set_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_ddpg_get_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
+    "ilsx_ddpg_set_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
+    "ilsx_vecenv_set_exploration": (C.c_int, [vp, C.POINTER(ExploreCfg)]),
+    "ilsx_vecenv_set_exploration_t": (C.c_int, [vp, C.c_int64]),
+    "ilsx_vecenv_explore": (C.c_int, [vp, vp, vp, C.c_int64]),
     "ilsx_sacv_create": (C.c_int, [vp, C.POINTER(SacvCfg), vp, vp, vp, vp, C.POINTER(vp)]),
     "ilsx_sacv_destroy": (C.c_int, [vp]),
     "ilsx_sacv_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(SacvStats)]),

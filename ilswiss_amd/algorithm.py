@@ -179,6 +179,9 @@ class DeviceRLAlgorithm:
     def _vec_step(self, begin_only=False):
         """One sampling iteration of all envs: policy -> physics -> replay record -> auto-reset.  begin_only: enqueue it and return; the
         caller ends it with _vec_step_end() (which, with insert_at_episode_end, waits for the step and inserts the finished episodes)."""
+        set_t = getattr(self.exploration_policy, "set_num_steps_total", None)   # base_algorithm.py:375 (annealed exploration strategies)
+        if set_t is not None:
+            set_t(self._n_env_steps_total)
         random_actions = self.replay_buffer.num_steps_can_sample() < self.min_steps_before_training
         label = getattr(self.trainer, "expert_policy", None)
         self._vec_step_open = bool(begin_only) and label is None and hasattr(self.training_env, "rollout_step_end")
@@ -443,7 +446,7 @@ class DeviceRLAlgorithmGroup:
         ok = all(hasattr(a.training_env, "h") and hasattr(a.exploration_policy, "h") and hasattr(a.replay_buffer, "h") and
                  getattr(a.trainer, "expert_policy", None) is None and a.max_path_length == a0.max_path_length and
                  a.no_terminal == a0.no_terminal and type(a.training_env).rollout_step is type(a0.training_env).rollout_step and
-                 not hasattr(a.exploration_policy, "_ppo") for a in algs)
+                 not hasattr(a.exploration_policy, "_ppo") and not hasattr(a.exploration_policy, "before_rollout_step") for a in algs)
         if not ok or not hasattr(a0.trainer.ctx.lib, "ilsx_rollout_steps_lockstep"):
             return None
         from .envs.vecenv import HipVectorEnv

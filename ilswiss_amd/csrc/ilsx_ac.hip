@@ -1,6 +1,7 @@
-// ilsx_ac.hip — the two other off-policy actor-critic trainers of the hot path, on the same kernels as SAC-alpha:
+// ilsx_ac.hip — the other off-policy actor-critic trainers of the hot path, on the same kernels as SAC-alpha:
 //   TD3    rlkit/torch/algorithms/td3/td3.py:21-124,180-183 + MlpGaussianNoisePolicy (common/policies.py:130-188)
 //   SAC-V  rlkit/torch/algorithms/sac/sac.py:23-179,242-243 (state-value variant, fixed temperature)
+//   DDPG   rlkit/torch/algorithms/ddpg/ddpg.py:21-235 + MlpPolicy (common/policies.py:106-127); step structure at its section below
 //
 // One agent = one trainable arena P = [Q1 | Q2 | (V |) pi] with gradient / Adam-moment arenas of the same layout and a
 // target arena T of the same layout (only the slices the algorithm has targets for are ever read).  Adam runs in the
@@ -551,6 +552,288 @@ extern "C" int ilsx_td3_get_opt(ilsx_td3* t, int which, float* m_host, float* v_
   return ILSX_OK;
 }
 extern "C" int ilsx_td3_set_opt(ilsx_td3* t, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  ilsx_opt_meta m2; if (meta) m2 = *meta;
+  ILSX_TRY(ac_opt(&t->g, which, true, const_cast<float*>(m_host), const_cast<float*>(v_host), n, meta ? &m2 : nullptr));
+  if (meta) t->n_steps = meta->n_train_steps;
+  return ILSX_OK;
+}
+
+// ================================================================================================ DDPG
+// rlkit/torch/algorithms/ddpg/ddpg.py:102-235.  Arena P = [Q | pi].  Every forward of the step reads PRE-update weights (the policy's
+// Q is taken before the critic steps, unlike TD3), so the three critic passes share a launch and the critic keeps two sets of saved
+// activations: g->h[DD_Q] for Q(s, a) (weight gradients) and hq2 for Q(s, pi(s)) (dQ/da only).
+//   fwd{pi_tgt(s') ; pi(s)} ; fwd{Q_tgt(s', a') ; Q(s, a) ; Q(s, pi(s))} ; k_ddpg_critic_grad ; bwd{Q <- 2 (q - y) / B ; Q -> dQ/da} ;
+//   k_ddpg_policy_grad ; bwd{pi} ; dW+Adam{pi} ; dW(+Adam){Q} (; k_ddpg_adam_decay) ; polyak | hard copy | nothing ; tick
+// (column-split path: Q(s, pi(s)) runs in a launch of its own, because a launch finishes ONE policy head in its prologue.)
+// The loss heads of the fused kernels stay as they are: the clamped target and the pre-activation penalty are formed by the two side
+// kernels below and enter the backward launches as LOSS_GIVEN.
+enum { DD_Q = 0, DD_PI = 1 };
+
+// y = clamp(r + (1 - d) * gamma * Q_tgt, lo, hi) (ddpg.py:140-142) ; dL/dq = 2 (q - y) / B (nn.MSELoss, :145)
+__global__ __launch_bounds__(256) void k_ddpg_critic_grad(PartVal q, PartVal tq, const float* __restrict__ rew, const float* __restrict__ done,
+                                                          float* __restrict__ y_out, float* __restrict__ dq, int B, float gamma, float lo,
+                                                          float hi, float inv_B) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  float y = rew[i] + (1.0f - done[i]) * gamma * tq.get(i);
+  y = fminf(fmaxf(y, lo), hi);
+  y_out[i] = y;
+  dq[i] = 2.0f * (q.get(i) - y) * inv_B;
+}
+// dL/d pre = dL/da * max_act * (1 - tanh(pre)^2) (identity output: dL/da * max_act) + 2 w pre / B (ddpg.py:113-124); ga = d(-mean Q)/da
+// in `parts` column-slice partial slabs of `stride` rows
+__global__ __launch_bounds__(256) void k_ddpg_policy_grad(const float* __restrict__ ga, const float* __restrict__ pre, float* __restrict__ out,
+                                                          int n, int a, int parts, int stride, float max_act, int linear, float pw2_B) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float g = ga[i];
+  for (int pc = 1; pc < parts; ++pc) g += ga[(size_t)pc * stride * a + i];
+  const float z = pre[i];
+  const float th = linear ? 0.0f : tanhf(z);
+  out[i] = g * max_act * (1.0f - th * th) + pw2_B * z;
+}
+// Adam over the critic's arena slice with the decay term 2 wd W added to the gradients of the weight matrices only (ddpg.py:165-169,
+// core.py:62-72: biases are not regularised); adam_apply's expressions in its order.  Elements inside a [blo, bhi) range are biases.
+struct DdpgBiasRanges { int lo[ILSX_MAX_HID + 1], hi[ILSX_MAX_HID + 1], n; };
+__global__ __launch_bounds__(256) void k_ddpg_adam_decay(float* __restrict__ G, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
+                                                         int n, DdpgBiasRanges R, float wd2, float b1, float b2, float eps,
+                                                         const float* __restrict__ step_size, const float* __restrict__ bc2_sqrt) {
+  const float step = *step_size, bc2s = *bc2_sqrt;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    bool bias = false;
+    for (int k = 0; k < R.n; ++k) bias = bias || (i >= R.lo[k] && i < R.hi[k]);
+    const float p0 = P[i];
+    const float g = bias ? G[i] : G[i] + wd2 * p0;
+    const float m = M[i] * b1 + (1.0f - b1) * g;
+    const float v = V[i] * b2 + (1.0f - b2) * g * g;
+    G[i] = g; M[i] = m; V[i] = v;
+    P[i] = p0 - step * (m / (sqrtf(v) / bc2s + eps));
+  }
+}
+// ptu.copy_model_params_from_to (pytorch_util.py) over the whole arena; n is a multiple of 4
+__global__ __launch_bounds__(256) void k_ddpg_hard_copy(const float4* __restrict__ p, float4* __restrict__ t, int n4) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) t[i] = p[i];
+}
+
+struct ilsx_ddpg {
+  AcAgent g;
+  ilsx_ddpg_cfg cfg;
+  long long n_steps = 0;   // ddpg.py's _n_env_steps_total: one per train step, tested before its increment
+  float *a2 = nullptr, *tq = nullptr, *q = nullptr, *qn = nullptr, *y = nullptr, *dq = nullptr;
+  float *pa = nullptr, *pre = nullptr, *ga = nullptr, *dpre = nullptr, *ppt = nullptr, *ppc = nullptr;
+  float* hq2[ILSX_MAX_HID] = {nullptr, nullptr, nullptr};   // the critic's activations at (s, pi(s))
+  bool out_linear = false;
+  int det_head() const { return out_linear ? HEAD_DET_LIN_NOISE : HEAD_DET_TANH_NOISE; }
+};
+
+extern "C" int ilsx_ddpg_create(ilsx_ctx* ctx, const ilsx_ddpg_cfg* cfg, ilsx_net* pi, ilsx_net* qf, ilsx_ddpg** out) {
+  if (!ctx || !cfg || !pi || !qf || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_ddpg_create: NULL argument");
+  const ilsx_mlp_cfg &cp = pi->lay.cfg, &cq = qf->lay.cfg;
+  if (cp.n_heads != 1) ILSX_FAIL(ILSX_ERR_ARG, "DDPG policy is a single-head Mlp (policies.py:106-127)");
+  if (pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "DDPG trains a continuous policy; this one is categorical");
+  if (cq.n_heads != 1 || cq.out_dim != 1) ILSX_FAIL(ILSX_ERR_ARG, "qf must be a single-output FlattenMlp");
+  if (cq.in_dim != cp.in_dim + cp.out_dim) ILSX_FAIL(ILSX_ERR_ARG, "qf input %d != obs %d + act %d", cq.in_dim, cp.in_dim, cp.out_dim);
+  if (cfg->max_batch < 1 || cfg->max_batch > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "max_batch=%d out of range", cfg->max_batch);
+  if (!cfg->use_soft_update && cfg->target_update_period < 1) ILSX_FAIL(ILSX_ERR_ARG, "target_update_period must be >= 1");
+  if (!(cfg->min_q_value <= cfg->max_q_value)) ILSX_FAIL(ILSX_ERR_ARG, "min_q_value must not exceed max_q_value");
+  if (cfg->qf_weight_decay < 0.f || cfg->policy_pre_activation_weight < 0.f) ILSX_FAIL(ILSX_ERR_ARG, "negative regularisation weight");
+  HIPCHK(hipSetDevice(ctx->device));
+  ilsx_ddpg* t = new ilsx_ddpg();
+  t->cfg = *cfg;
+  ilsx_net* nets[2] = {qf, pi};
+  const int opt_of[2] = {0, 1};
+  AcAgent* g = &t->g;
+  g->lr[0] = cfg->qf_lr; g->lr[1] = cfg->policy_lr; g->beta_1 = 0.9f;   // optimizer_class defaults, ddpg.py:86-93
+  int rc = ac_init(g, ctx, nets, 2, opt_of, cfg->max_batch, cp.in_dim, cp.out_dim);
+  const size_t B = (size_t)cfg->max_batch, a = (size_t)cp.out_dim, CS = (size_t)g->cs;
+  float** bufs[] = {&t->tq, &t->q, &t->qn};
+  for (float** b : bufs) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B);
+  float** rows[] = {&t->y, &t->dq};
+  for (float** b : rows) if (rc == ILSX_OK) rc = ac_alloc(g, b, std::max<size_t>(B, 4) );
+  float** acts[] = {&t->a2, &t->pa, &t->pre, &t->dpre};
+  for (float** b : acts) if (rc == ILSX_OK) rc = ac_alloc(g, b, B * std::max<size_t>(a, 4));
+  float** parts[] = {&t->ga, &t->ppt, &t->ppc};
+  for (float** b : parts) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B * a);
+  for (int l = 0; l < cq.n_hidden; ++l) if (rc == ILSX_OK) rc = ac_alloc(g, &t->hq2[l], B * (size_t)g->H);
+  if (rc == ILSX_OK) rc = ac_tick(g, 0, 0);
+  if (rc != ILSX_OK) { delete t; return rc; }
+  pi->noise = 0.f; pi->noise_clip = 0.f; pi->max_act = cfg->max_act; pi->noise_policy = true;   // MlpPolicy: deterministic
+  t->out_linear = pi->out_linear;
+  *out = t;
+  return ILSX_OK;
+}
+extern "C" int ilsx_ddpg_destroy(ilsx_ddpg* t) {
+  if (!t) return ILSX_OK;
+  ac_release(&t->g);
+  delete t;
+  return ILSX_OK;
+}
+
+static void ddpg_policy_task(ilsx_ddpg* t, FwdTask& f, bool target, const float* obs, bool save, float* action, float* pre, float* part) {
+  AcAgent* g = &t->g;
+  ac_fwd(g, f, DD_PI, target, obs, g->o, nullptr, 0, save);
+  f.head = t->det_head(); f.rng_stream = g->rng_stream;
+  if (g->cs > 1) { f.part = part; return; }
+  f.action = action; f.out = pre; f.max_act = t->cfg.max_act; f.noise = 0.0f; f.noise_clip = 0.0f;
+}
+static void ddpg_policy_fin(ilsx_ddpg* t, FwdArgs& A, const float* part, float* action, float* pre) {
+  ac_policy_fin(&t->g, A, t->det_head(), part, nullptr, pre, action, nullptr, nullptr, 0.0f, 0.0f, t->cfg.max_act);
+}
+static void ddpg_actor_q_task(ilsx_ddpg* t, FwdTask& f) {   // Q(s, pi(s)), activations into the second set
+  AcAgent* g = &t->g;
+  ac_fwd(g, f, DD_Q, false, g->s, g->o, t->pa, g->a, false);
+  for (int l = 0; l < g->L[DD_Q].cfg.n_hidden; ++l) f.hsave[l] = t->hq2[l];
+  ac_out(g, f, t->qn);
+}
+
+static int ddpg_step(ilsx_ddpg* t, ilsx_ddpg_stats* stats) {
+  AcAgent* g = &t->g;
+  const ilsx_ddpg_cfg& c = t->cfg;
+  hipStream_t st = g->ctx->stream;
+  const int na = g->B * g->a;
+  const float inv_B = 1.0f / (float)g->B;
+  double w_sq = 0.0;   // sum ||W||^2 of the critic's pre-update weight matrices: the statistics' decay term (ddpg.py:165-169,193)
+  if (stats && c.qf_weight_decay > 0.f) {
+    const NetLayout& L = g->L[DD_Q];
+    std::vector<float> flat(L.n_flat);
+    ILSX_TRY(net_download_flat(g->ctx, L, g->p(DD_Q), flat.data(), flat.size(), 0));
+    HIPCHK(hipStreamSynchronize(st));
+    size_t f = 0;
+    for (int l = 0; l < L.cfg.n_hidden; ++l) {
+      const size_t nw = (size_t)L.out_of(l) * L.in_of(l);
+      for (size_t i = 0; i < nw; ++i) w_sq += (double)flat[f + i] * flat[f + i];
+      f += nw + L.out_of(l);
+    }
+    const size_t nwh = (size_t)L.cfg.out_dim * L.out_of(L.cfg.n_hidden - 1);
+    for (size_t i = 0; i < nwh; ++i) w_sq += (double)flat[f + i] * flat[f + i];
+  }
+  {  // pi_tgt(s') (ddpg.py:134) ; pi(s) with its pre-activations (:114-117,126)
+    FwdArgs A = ac_fwd_args(g, 2);
+    ddpg_policy_task(t, A.t[0], true, g->s2, false, t->a2, nullptr, t->ppt);
+    ddpg_policy_task(t, A.t[1], false, g->s, true, t->pa, t->pre, t->ppc);
+    ILSX_TRY(ac_launch_fwd(g, A, g->L[DD_PI].KP));
+  }
+  {  // Q_tgt(s', a') (:136-139) ; Q(s, a) (:143) ; Q(s, pi(s)) (:119,127) — all at pre-update weights
+    const bool one = g->cs == 1;
+    FwdArgs A = ac_fwd_args(g, one ? 3 : 2);
+    ac_fwd(g, A.t[0], DD_Q, true, g->s2, g->o, t->a2, g->a, false); ac_out(g, A.t[0], t->tq);
+    ac_fwd(g, A.t[1], DD_Q, false, g->s, g->o, g->ac, g->a, true); ac_out(g, A.t[1], t->q); A.t[1].no_fin = 1;
+    if (one) ddpg_actor_q_task(t, A.t[2]);
+    ddpg_policy_fin(t, A, t->ppt, t->a2, nullptr);
+    ILSX_TRY(ac_launch_fwd(g, A, g->L[DD_Q].KP));
+    if (!one) {
+      FwdArgs A2 = ac_fwd_args(g, 1);
+      ddpg_actor_q_task(t, A2.t[0]);
+      ddpg_policy_fin(t, A2, t->ppc, t->pa, t->pre);
+      ILSX_TRY(ac_launch_fwd(g, A2, g->L[DD_Q].KP));
+    }
+  }
+  hipLaunchKernelGGL(k_ddpg_critic_grad, dim3((g->B + 255) / 256), dim3(256), 0, st, pv(g, t->q), pv(g, t->tq), (const float*)g->r,
+                     (const float*)g->d, t->y, t->dq, g->B, c.discount, c.min_q_value, c.max_q_value, inv_B);
+  HIPCHK(hipGetLastError());
+  {  // critic: head gradient given (-> weight gradients) ; the same critic at (s, pi(s)): -1/B at the head -> d(-mean Q)/da
+    BwdArgs A = ac_bwd_args(g, 2, 0.f, 0.f);
+    BwdTask& b0 = A.t[0];
+    ac_bwd(g, b0, DD_Q, true);
+    b0.loss = LOSS_GIVEN; b0.given = t->dq;
+    BwdTask& b1 = A.t[1];
+    ac_bwd(g, b1, DD_Q, false);
+    for (int l = 0; l < g->L[DD_Q].cfg.n_hidden; ++l) b1.hsave[l] = t->hq2[l];
+    b1.loss = LOSS_CONST; b1.coef = -1.0f;
+    b1.dx = t->ga; b1.dx_col0 = g->o; b1.dx_cols = g->a;
+    ILSX_TRY(ac_launch_bwd(g, A));
+  }
+  hipLaunchKernelGGL(k_ddpg_policy_grad, dim3((na + 255) / 256), dim3(256), 0, st, (const float*)t->ga, (const float*)t->pre, t->dpre, na, g->a,
+                     g->cs, g->max_batch, c.max_act, t->out_linear ? 1 : 0, 2.0f * c.policy_pre_activation_weight * inv_B);
+  HIPCHK(hipGetLastError());
+  {
+    BwdArgs A = ac_bwd_args(g, 1, 0.f, 0.f);
+    BwdTask& b = A.t[0];
+    ac_bwd(g, b, DD_PI, true);
+    b.loss = LOSS_GIVEN; b.given = t->dpre;
+    ILSX_TRY(ac_launch_bwd(g, A));
+  }
+  ILSX_TRY(ac_dw_adam(g, DD_PI, 1, false, 0.f));   // ddpg.py:177-179
+  if (c.qf_weight_decay > 0.f) {                   // :181-183 with the decay term: gradients first, Adam in a pass that knows weights from biases
+    DwArgs table;
+    memset(&table, 0, sizeof table);
+    ILSX_TRY(build_dw_jobs(g->L[DD_Q], g->G + g->off[DD_Q], g->x[DD_Q], g->h[DD_Q], g->dl[DD_Q], g->dh[DD_Q], &table));
+    ILSX_TRY(launch_bwd_dw(g->ctx, table, g->B, nullptr));
+    const NetLayout& L = g->L[DD_Q];
+    DdpgBiasRanges R;
+    memset(&R, 0, sizeof R);
+    for (int l = 0; l < L.cfg.n_hidden; ++l) { R.lo[R.n] = L.off_b[l]; R.hi[R.n] = L.off_b[l] + L.cfg.hidden; ++R.n; }
+    R.lo[R.n] = L.off_bh; R.hi[R.n] = L.off_bh + L.NO; ++R.n;
+    const size_t o0 = g->off[DD_Q];
+    const int n = (int)L.n_int;
+    hipLaunchKernelGGL(k_ddpg_adam_decay, dim3(std::min(1024, (n + 255) / 256)), dim3(256), 0, st, g->G + o0, g->P + o0, g->M + o0, g->V + o0, n, R,
+                       2.0f * c.qf_weight_decay, g->beta_1, 0.999f, 1e-8f, (const float*)&g->sc->step[0], (const float*)&g->sc->bc2s[0]);
+    HIPCHK(hipGetLastError());
+  } else {
+    ILSX_TRY(ac_dw_adam(g, DD_Q, 1, false, 0.f));
+  }
+  if (c.use_soft_update) {   // ddpg.py:228-235
+    hipLaunchKernelGGL(k_ac_polyak, dim3(256), dim3(256), 0, st, (const float*)g->P, g->T, (int)g->off[2], c.soft_target_tau);
+    HIPCHK(hipGetLastError());
+  } else if (t->n_steps % c.target_update_period == 0) {   // decided on the host from the step counter: no device read, no sync
+    const int n4 = (int)(g->off[2] / 4);
+    hipLaunchKernelGGL(k_ddpg_hard_copy, dim3(std::min(1024, (n4 + 255) / 256)), dim3(256), 0, st, (const float4*)g->P, (float4*)g->T, n4);
+    HIPCHK(hipGetLastError());
+  }
+  ILSX_TRY(ac_tick(g, 3, 1));
+  t->n_steps += 1;
+  if (stats) {  // ddpg.py:187-225; the device buffers still hold this step's predictions
+    const size_t B = (size_t)g->B;
+    std::vector<float> q, qn, y, pa, pre, e;
+    ILSX_TRY(ac_fetch_pv(g, t->q, B, q)); ILSX_TRY(ac_fetch_pv(g, t->qn, B, qn));
+    ILSX_TRY(ac_fetch(g, t->y, B, y)); ILSX_TRY(ac_fetch(g, t->pa, B * g->a, pa)); ILSX_TRY(ac_fetch(g, t->pre, B * g->a, pre));
+    HIPCHK(hipStreamSynchronize(st));
+    stats->qf_loss = (float)((double)mean_sq_diff(q, y, &e) + (double)c.qf_weight_decay * w_sq);
+    double s = 0, p2 = 0;
+    for (float v : qn) s += v;
+    for (float v : pre) p2 += (double)v * v;
+    stats->raw_policy_loss = (float)(-s / (double)B);
+    const float pre_loss = c.policy_pre_activation_weight > 0.f ? (float)(p2 / (double)B * (double)c.policy_pre_activation_weight) : 0.0f;
+    stats->policy_loss = stats->raw_policy_loss + pre_loss;
+    stats->preactivation_policy_loss = stats->policy_loss - stats->raw_policy_loss;   // as the reference forms it (:198-201)
+    msmm(q.data(), B, stats->q_pred); msmm(y.data(), B, stats->q_target); msmm(e.data(), B, stats->bellman);
+    msmm(pa.data(), pa.size(), stats->policy_action);
+  }
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_ddpg_train_step(ilsx_ddpg* t, const float* obs, const float* act, const float* rew, const float* done,
+                                    const float* nobs, int B, ilsx_ddpg_stats* stats) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_ddpg_train_step: NULL handle");
+  ILSX_TRY(ac_stage(&t->g, obs, act, rew, done, nobs, B, nullptr));
+  return ddpg_step(t, stats);
+}
+extern "C" int ilsx_ddpg_train_from_replay(ilsx_ddpg* t, ilsx_replay* rb, int n_steps, int B, ilsx_ddpg_stats* stats) {
+  if (!t || n_steps < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_ddpg_train_from_replay: bad argument");
+  HIPCHK(hipSetDevice(t->g.ctx->device));
+  for (int i = 0; i < n_steps; ++i) {
+    ILSX_TRY(ac_sample(&t->g, rb, B));
+    ILSX_TRY(ddpg_step(t, i == 0 ? stats : nullptr));   // statistics of the first batch only (ddpg.py:187-192)
+  }
+  return ILSX_OK;
+}
+// which: 0 qf, 1 policy, 2 target_qf, 3 target_policy
+extern "C" int ilsx_ddpg_get_params(ilsx_ddpg* t, int which, float* dst_host, size_t n) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  return ac_params(&t->g, which, false, dst_host, n);
+}
+extern "C" int ilsx_ddpg_set_params(ilsx_ddpg* t, int which, const float* src_host, size_t n) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  return ac_params(&t->g, which, true, const_cast<float*>(src_host), n);
+}
+extern "C" int ilsx_ddpg_get_opt(ilsx_ddpg* t, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  ILSX_TRY(ac_opt(&t->g, which, false, m_host, v_host, n, meta));
+  if (meta) meta->n_train_steps = t->n_steps;
+  return ILSX_OK;
+}
+extern "C" int ilsx_ddpg_set_opt(ilsx_ddpg* t, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta) {
   if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
   ilsx_opt_meta m2; if (meta) m2 = *meta;
   ILSX_TRY(ac_opt(&t->g, which, true, const_cast<float*>(m_host), const_cast<float*>(v_host), n, meta ? &m2 : nullptr));

@@ -69,6 +69,11 @@ struct ilsx_vecenv {
   struct SwimmerDev* sw = nullptr;   // engine 2, classic == ILSX_SWIMMER_TASK: the constants k_swimmer_step takes by value (swimmer_env.h)
   bool wave3 = true;   // wave-per-env kernels (env3d_wave.h); ILSX_ENV3D_LANE=1 selects the lane-per-env form (env3d.h) for A/B runs
   Spatial3Dev* hm3 = nullptr; Spatial3Dev* dm3 = nullptr; double* scr3 = nullptr;
+  // exploration strategy of a deterministic policy (ilsx_vecenv_set_exploration): one process per env, float64
+  ilsx_explore_cfg explore = {0, 0, 0.0, 0.0, 0.0, 0.0, 1.0, -1.0, 1.0};
+  double *ou_state = nullptr, *ou_sigma = nullptr;   // [n_env][a]: the OU state, and the sigma its next evolve uses (the previous call's)
+  long long explore_t = 0;                // the t of the rollout's next steps (PolicyWrappedWithExplorationStrategy.set_num_steps_total)
+  unsigned long long explore_calls = 0;   // Philox counter of k_explore (one draw per call)
   const float* policy_obs() const { return norm_obs ? obs_n : obs_cur; }
 };
 
@@ -615,6 +620,45 @@ __global__ void k_random_actions(float* act, int n, uint64_t seed, uint32_t stre
   act[t] = (float)(2.0 * env_uniform(seed, stream, step, (uint32_t)env, (uint32_t)k) - 1.0);
 }
 
+// Exploration strategies of a deterministic policy, one process per env (rlkit/exploration_strategies/gaussian_strategy.py:25-33,
+// ou_strategy.py:46-60), float64 in the reference's order (FMA contraction is off for this file).  One thread per action component.
+//   Gaussian: act = clip(act + N(0,1) * sigma(t), low, high)
+//   OU      : x = state (mu at the first step of an episode: OUStrategy.reset) ; state = x + (theta * (mu - x) + sigma_prev * N(0,1)) ;
+//             sigma_prev = sigma(t) — annealed AFTER the evolve, so a call uses the sigma of the call before it ; act = clip(act + state)
+struct ExploreArgs {
+  int kind, n_env, a;
+  double mu, theta, max_sigma, min_sigma, decay_period, low, high;
+  long long t;
+};
+__global__ __launch_bounds__(256) void k_explore(const ExploreArgs X, float* __restrict__ act, const double* __restrict__ eps,
+                                                 double* __restrict__ state, double* __restrict__ sigma, const int* __restrict__ ep_len,
+                                                 uint64_t seed, uint32_t stream, unsigned long long step) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= X.n_env * X.a) return;
+  const int env = i / X.a, j = i - env * X.a;
+  double e;
+  if (eps) {
+    e = eps[i];
+  } else {
+    float z4[4];
+    philox_normal4(seed, step, stream, (uint32_t)env, (uint32_t)(j >> 2), z4);
+    const int q = j & 3;
+    e = (double)(q == 0 ? z4[0] : q == 1 ? z4[1] : q == 2 ? z4[2] : z4[3]);
+  }
+  const double sig_t = X.max_sigma - (X.max_sigma - X.min_sigma) * fmin(1.0, (double)X.t * 1.0 / X.decay_period);
+  double noise;
+  if (X.kind == 1) {
+    noise = e * sig_t;
+  } else {
+    const double x = ep_len[env] == 0 ? X.mu : state[i];
+    const double dx = X.theta * (X.mu - x) + sigma[i] * e;
+    noise = x + dx;
+    state[i] = noise;
+    sigma[i] = sig_t;
+  }
+  act[i] = (float)fmin(fmax((double)act[i] + noise, X.low), X.high);
+}
+
 // ================================================================================================ 3-D engine kernels
 __device__ void e3_reset_state(const E3Ctx& C, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t envu) {
   const Spatial3Dev& m = *C.m;
@@ -1156,7 +1200,7 @@ extern "C" int ilsx_vecenv_state_dims(const ilsx_vecenv* e, int* nq, int* nv) {
 
 extern "C" int ilsx_vecenv_destroy(ilsx_vecenv* e) {
   if (!e) return ILSX_OK;
-  void* ps[] = {e->dm, e->qpos, e->qvel, e->obs_cur, e->act, e->nobs, e->rew, e->done, e->ep_len, e->ep_ret, e->stats, e->ids, e->dm3, e->scr3, e->stage, e->flush_len};
+  void* ps[] = {e->dm, e->qpos, e->qvel, e->obs_cur, e->act, e->nobs, e->rew, e->done, e->ep_len, e->ep_ret, e->stats, e->ids, e->dm3, e->scr3, e->stage, e->flush_len, e->ou_state, e->ou_sigma};
   for (void* p : ps) if (p) ctx_free(e->ctx, p);
   if (e->flush_host) hipHostFree(e->flush_host);
   if (e->grp_flush_host) hipHostFree(e->grp_flush_host);
@@ -1402,6 +1446,49 @@ static int rollout_paths_finish(ilsx_vecenv* e, bool synced = false, const int* 
     if (flags[i]) { envs.push_back(i); lens.push_back(flags[i] & ((1 << 30) - 1)); term.push_back((flags[i] >> 30) & 1); }
   return replay_insert_paths(rb, e->stage, e->stage_len, envs.data(), lens.data(), term.data(), (int)envs.size());
 }
+// ---- exploration strategies (k_explore)
+static int env_explore(ilsx_vecenv* e, float* act, const double* eps, long long t) {
+  const ilsx_explore_cfg& c = e->explore;
+  ExploreArgs X;
+  X.kind = c.kind; X.n_env = e->n_env; X.a = e->a;
+  X.mu = c.mu; X.theta = c.theta; X.max_sigma = c.max_sigma; X.min_sigma = c.min_sigma; X.decay_period = c.decay_period;
+  X.low = c.low; X.high = c.high; X.t = t;
+  const int tot = e->n_env * e->a;
+  hipLaunchKernelGGL(k_explore, dim3((tot + 255) / 256), dim3(256), 0, e->ctx->stream, X, act, eps, e->ou_state, e->ou_sigma, (const int*)e->ep_len,
+                     e->seed, e->rng_stream ^ 0x45585000u, ++e->explore_calls);   // 'EXP': a Philox stream of its own
+  HIPCHK(hipGetLastError());
+  return ILSX_OK;
+}
+extern "C" int ilsx_vecenv_set_exploration(ilsx_vecenv* e, const ilsx_explore_cfg* cfg) {
+  if (!e || !cfg) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_set_exploration: NULL argument");
+  if (cfg->kind < 0 || cfg->kind > 2) ILSX_FAIL(ILSX_ERR_ARG, "exploration kind %d: 0 none, 1 Gaussian, 2 OU", cfg->kind);
+  if (cfg->kind && e->discrete_n > 0) ILSX_FAIL(ILSX_ERR_ARG, "exploration strategies add noise to Box actions; this env's action space is Discrete");
+  if (cfg->kind && (!(cfg->decay_period > 0.0) || !(cfg->low <= cfg->high))) ILSX_FAIL(ILSX_ERR_ARG, "exploration: decay_period must be > 0 and low <= high");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  e->explore = *cfg;
+  if (!cfg->kind) return ILSX_OK;
+  const size_t n = (size_t)e->n_env * e->a;
+  if (!e->ou_state) { ILSX_TRY(ctx_alloc(e->ctx, n * 8, (void**)&e->ou_state)); ILSX_TRY(ctx_alloc(e->ctx, n * 8, (void**)&e->ou_sigma)); }
+  std::vector<double> h(n, cfg->mu);   // OUStrategy.__init__: state = mu, sigma = max_sigma
+  HIPCHK(hipMemcpyAsync(e->ou_state, h.data(), n * 8, hipMemcpyHostToDevice, e->ctx->stream));
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  h.assign(n, cfg->max_sigma);
+  HIPCHK(hipMemcpyAsync(e->ou_sigma, h.data(), n * 8, hipMemcpyHostToDevice, e->ctx->stream));
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  return ILSX_OK;
+}
+extern "C" int ilsx_vecenv_set_exploration_t(ilsx_vecenv* e, int64_t t) {
+  if (!e) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_set_exploration_t: NULL env");
+  e->explore_t = (long long)t;
+  return ILSX_OK;
+}
+extern "C" int ilsx_vecenv_explore(ilsx_vecenv* e, float* act, const double* eps, int64_t t) {
+  if (!e || !act) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_explore: NULL argument");
+  if (!e->explore.kind) ILSX_FAIL(ILSX_ERR_STATE, "ilsx_vecenv_explore: no exploration strategy set (ilsx_vecenv_set_exploration)");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  return env_explore(e, act, eps, (long long)t);
+}
+
 // A policy acts in the env's kind of action space: a categorical policy writes indices (Discrete envs), every other policy writes
 // continuous actions (Box envs).  Crossed, either the stepper reads an index as a force or an index lands in a continuous column.
 static int env_policy_kind_check(const ilsx_vecenv* e, const ilsx_net* pi, const char* who) {
@@ -1438,6 +1525,7 @@ static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, i
     HIPCHK(hipGetLastError());
   } else {
     ILSX_TRY(ilsx_policy_act(pi, e->policy_obs(), e->n_env, deterministic, nullptr, e->act, nullptr));
+    if (e->explore.kind && !deterministic) ILSX_TRY(env_explore(e, e->act, nullptr, e->explore_t));
   }
   EnvStepArgs A;
   ILSX_TRY(rollout_env_args(e, rb, max_path_length, no_terminal, step, &A));
@@ -1490,6 +1578,7 @@ static bool rollout_runs_groupable(ilsx_vecenv* const* envs, ilsx_net* const* pi
   for (int k = 0; k < n_runs; ++k) {
     const ilsx_vecenv* e = envs[k];
     const ilsx_net* p = pis[k];
+    if (e->explore.kind) return false;   // a strategy's kernel runs between inference and the stepper: such runs step one by one
     if (e->engine != 0 || e->norm_obs || e->n_env != e0->n_env || e->hm.nb != e0->hm.nb || (e->hm.max_rows > 12) != (e0->hm.max_rows > 12) ||
         e->o != e0->o || e->a != e0->a || e->ctx->device != e0->ctx->device)
       return false;

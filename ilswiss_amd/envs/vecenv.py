@@ -363,6 +363,9 @@ class HipVectorEnv:
             _lib.check(self.ctx.lib.ilsx_rollout_step_relabel(self.h, policy.h, lp.h, int(det), replay.h if replay is not None else None,
                                                               int(max_path_length), int(bool(no_terminal))))
             return
+        hook = getattr(policy, "before_rollout_step", None)   # PolicyWrappedWithExplorationStrategy: installs its strategy here, forwards t
+        if hook is not None:
+            hook(self)
         fn = self.ctx.lib.ilsx_rollout_step_begin if begin_only else self.ctx.lib.ilsx_rollout_step
         _lib.check(fn(self.h, policy.h if policy is not None else None, replay.h if replay is not None else None, int(max_path_length),
                       int(bool(random_actions)), int(bool(deterministic)), int(bool(no_terminal))))

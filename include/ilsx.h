@@ -48,6 +48,7 @@ typedef struct ilsx_vecenv ilsx_vecenv;
 typedef struct ilsx_disc ilsx_disc;
 typedef struct ilsx_ppo ilsx_ppo;
 typedef struct ilsx_td3 ilsx_td3;
+typedef struct ilsx_ddpg ilsx_ddpg;
 typedef struct ilsx_sacv ilsx_sacv;
 typedef struct ilsx_bc ilsx_bc;
 typedef struct ilsx_dsac ilsx_dsac;
@@ -412,6 +413,34 @@ int ilsx_td3_train_from_replay(ilsx_td3* td3, ilsx_replay* rb, int n_steps, int 
 int ilsx_td3_get_params(ilsx_td3* td3, int which, float* dst_host, size_t n);
 int ilsx_td3_set_params(ilsx_td3* td3, int which, const float* src_host, size_t n);
 
+/* ---------------------------------------------------------------- DDPG
+ * Replaces rlkit/torch/algorithms/ddpg/ddpg.py:21-100 (ctor), :102-226 (train_step), :228-235 (target updates).  pi: a single-head Mlp
+ * with tanh or identity output (ilsx_net_set_output_linear), adopted as a noise policy with noise 0 (policies.py:106-127 MlpPolicy);
+ * qf: one single-output FlattenMlp.  `discount` is a field here because the reference reads self.discount without ever setting it.
+ * Policy loss -mean(Q(s, pi(s))) + policy_pre_activation_weight * mean_rows(sum_cols(pre^2)); target clamp(r + (1-d) * discount *
+ * Q_tgt(s', pi_tgt(s')), min_q_value, max_q_value) (+-inf allowed); critic loss MSE + qf_weight_decay * sum ||W||^2 over the critic's
+ * weight matrices (biases excluded, core.py:62-72).  Both gradients are taken at the pre-update parameters.  Targets: Polyak with
+ * soft_target_tau when use_soft_update, else a hard copy on the steps whose counter (tested before its increment, one per train step)
+ * is a multiple of target_update_period — the first step copies. */
+typedef struct {
+  float discount, policy_lr, qf_lr, qf_weight_decay, soft_target_tau;
+  int32_t use_soft_update, target_update_period;
+  float policy_pre_activation_weight, min_q_value, max_q_value, max_act;
+  int32_t max_batch;
+} ilsx_ddpg_cfg;
+typedef struct {   /* ddpg.py:187-225; qf_loss includes the decay term */
+  float qf_loss, policy_loss, raw_policy_loss, preactivation_policy_loss;
+  float q_pred[4], q_target[4], bellman[4], policy_action[4];
+} ilsx_ddpg_stats;
+int ilsx_ddpg_create(ilsx_ctx* ctx, const ilsx_ddpg_cfg* cfg, ilsx_net* pi, ilsx_net* qf, ilsx_ddpg** out);
+int ilsx_ddpg_destroy(ilsx_ddpg* ddpg);
+int ilsx_ddpg_train_step(ilsx_ddpg* ddpg, const float* obs, const float* act, const float* rew, const float* done,
+                         const float* nobs, int B, ilsx_ddpg_stats* stats);
+int ilsx_ddpg_train_from_replay(ilsx_ddpg* ddpg, ilsx_replay* rb, int n_steps, int B, ilsx_ddpg_stats* stats);
+/* which: 0 qf, 1 policy, 2 target_qf, 3 target_policy; HOST flat arrays */
+int ilsx_ddpg_get_params(ilsx_ddpg* ddpg, int which, float* dst_host, size_t n);
+int ilsx_ddpg_set_params(ilsx_ddpg* ddpg, int which, const float* src_host, size_t n);
+
 /* ---------------------------------------------------------------- discrete SAC
  * Replaces rlkit/torch/algorithms/discrete_sac/discrete_sac.py:23-58 (ctor), :62-181 (train_step), :196-198 (soft updates).  pi: a
  * categorical policy (ilsx_net_set_categorical) of n outputs; qf1 / qf2: identical FlattenMlp's obs -> n.  Batches carry the action INDEX
@@ -470,6 +499,8 @@ int ilsx_sacv_set_params(ilsx_sacv* sac, int which, const float* src_host, size_
 typedef struct { int64_t t; uint64_t rng_step; int64_t n_train_steps; } ilsx_opt_meta;
 int ilsx_td3_get_opt(ilsx_td3* td3, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);    /* 0 qf1, 1 qf2, 2 policy */
 int ilsx_td3_set_opt(ilsx_td3* td3, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
+int ilsx_ddpg_get_opt(ilsx_ddpg* ddpg, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);    /* 0 qf, 1 policy; n_train_steps = the hard-update counter */
+int ilsx_ddpg_set_opt(ilsx_ddpg* ddpg, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
 int ilsx_dsac_get_opt(ilsx_dsac* d, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);     /* 0 qf1, 1 qf2, 2 policy */
 int ilsx_dsac_set_opt(ilsx_dsac* d, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
 int ilsx_sacv_get_opt(ilsx_sacv* sac, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);  /* 0 qf1, 1 qf2, 2 vf, 3 policy */
@@ -726,6 +757,23 @@ int ilsx_ppo_rollout(ilsx_ppo* ppo, ilsx_vecenv* env, int T, int max_path_length
  * stored terminal flag is forced to 0 (base_algorithm.py:195-196,208-210; the adv-IRL configs). */
 int ilsx_rollout_step(ilsx_vecenv* env, ilsx_net* pi, ilsx_replay* rb, int max_path_length, int random_actions,
                       int deterministic, int no_terminal);
+/* Exploration strategies of deterministic policies on the device (rlkit/exploration_strategies/{gaussian,ou}_strategy.py behind
+ * base.py:39-60 PolicyWrappedWithExplorationStrategy), ONE process per env, float64 in the reference's order:
+ *   Gaussian: act = clip(act + sigma(t) * N(0,1), low, high), sigma(t) = max_sigma - (max_sigma - min_sigma) * min(1, t / decay_period);
+ *   OU      : state += theta * (mu - state) + sigma_prev * N(0,1) with the sigma of the env's PREVIOUS call, then sigma = sigma(t);
+ *             act = clip(act + state, low, high).  An env at the start of an episode (its step counter is 0) first puts its state back
+ *             to mu (OUStrategy.reset through the wrapper's reset()).
+ * ilsx_rollout_step applies the env's strategy to the policy's actions unless the step is deterministic or random_actions; evaluation
+ * rollouts never explore; runs with a strategy set do not share launches in ilsx_rollout_steps_lockstep (they step one by one). */
+typedef struct {
+  int32_t kind;   /* 0 none, 1 Gaussian, 2 OU */
+  int32_t pad;
+  double mu, theta, max_sigma, min_sigma, decay_period, low, high;
+} ilsx_explore_cfg;
+int ilsx_vecenv_set_exploration(ilsx_vecenv* env, const ilsx_explore_cfg* cfg);   /* (re)starts every env's process at mu, sigma at max_sigma */
+int ilsx_vecenv_set_exploration_t(ilsx_vecenv* env, int64_t t);                    /* the t of the rollout's next steps (set_num_steps_total) */
+/* one exploration step on act[n_env, a] (device, in place); eps: device float64 [n_env, a] N(0,1) draws or NULL = Philox */
+int ilsx_vecenv_explore(ilsx_vecenv* env, float* act, const double* eps, int64_t t);
 /* Evaluation on the device — VecPathSampler.obtain_samples / rollout (samplers/vec_sampler.py:5-93,124-142): reset all envs,
  * then every env plays ONE episode with `pi` (ilsx_net: tanh-Gaussian or noise policy) or `ppo`'s Gaussian policy; envs that
  * end (terminal or max_path_length) are frozen, not reset.  stats_host[18] (nullable, float64) accumulates what

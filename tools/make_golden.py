@@ -1529,6 +1529,130 @@ def gen_discrete_sac():
     save("g28_discrete_sac", **rec)
 
 
+DDPG_CASES = (   # (o, a, hidden, B, seed, tanh output, trainer keywords) — the smallest shapes that reach each path of the device step
+    (3, 1, [64, 64], 37, 3100, False, dict(target_update_period=2, policy_lr=1e-3, qf_lr=3e-3)),
+    (11, 3, [128, 128], 256, 3101, True, dict(use_soft_update=True, policy_pre_activation_weight=0.01, qf_weight_decay=1e-3)),
+    (11, 3, [256, 256, 256], 128, 3102, False, dict(min_q_value=-0.5, max_q_value=0.8)),
+    (111, 8, [256, 256], 64, 3103, True, dict(use_soft_update=True)),
+)
+DDPG_DISCOUNT = 0.99
+DDPG_STATS = ("Q Predictions", "Q Targets", "Bellman Errors", "Policy Action")
+
+
+def ddpg_init(seed, o, a, Hh):
+    """G31's initial parameters (regenerated by the tests from the seed: the fixture stays under the size limit)."""
+    rng = np.random.default_rng(seed)
+    pi0 = omlp.init_mlp(rng, o, Hh, a, init_w=1e-3)
+    pi0[-(Hh[-1] * a + a):] *= 300.0       # head weights up so that tanh bends and the pre-activation penalty has something to pull on
+    return rng, pi0, omlp.init_mlp(rng, o + a, Hh, 1)
+
+
+def _explore_trace(make, calls=40, A=3, seed=3131):
+    """One strategy object of the reference driven for `calls` single-env calls: t advances by 7 per call, reset() before calls 13 and 29;
+    the N(0,1) draws it consumes are recorded as it makes them (numpy's global generator, seeded)."""
+    import numpy.random as nr
+    rng = np.random.default_rng(seed)
+    raw = rng.uniform(-0.95, 0.95, (calls, A)).astype(np.float32)
+    drawn = []
+    orig_randn, orig_normal = nr.randn, nr.normal
+
+    def randn(*shape):
+        v = orig_randn(*shape)
+        drawn.append(np.array(v, np.float64))
+        return v
+
+    def normal(*aa, **kk):
+        v = orig_normal(*aa, **kk)
+        drawn.append(np.array(v, np.float64))
+        return v
+    es = make()
+    np.random.seed(seed)
+    nr.randn, nr.normal = randn, normal
+    try:
+        out = []
+        for k in range(calls):
+            if k in (13, 29):
+                es.reset()
+            out.append(np.asarray(es.get_action_from_raw_action(raw[k], t=7 * k), np.float64))
+    finally:
+        nr.randn, nr.normal = orig_randn, orig_normal
+    out, eps = np.stack(out), np.stack(drawn)
+    assert eps.shape == (calls, A)
+    clipped = np.abs(out) == 1.0
+    assert 0 < clipped.sum() < clipped.size, clipped.sum()    # the clip fires on some entries, not on all
+    return raw, eps, out
+
+
+def gen_ddpg():
+    """G31: DDPG.train_step (ddpg/ddpg.py:102-235) with the reference's own MlpPolicy and FlattenMlp, three chained steps per case of
+    DDPG_CASES (`discount`, which the reference reads and never sets, is put on the trainer object): per-step statistics, the first step's
+    gradients, the parameters of all four networks after every step of case 0 (hard-update schedule) and after the last step of the others.
+    Initial parameters come from ddpg_init(seed); vectors of the wide cases are kept at `idx` only (a fixed random subset).  ou_* / ga_*:
+    OUStrategy / GaussianStrategy traces (exploration_strategies/), 40 single-env calls with the draws they consumed."""
+    from types import SimpleNamespace
+    from rlkit.exploration_strategies.gaussian_strategy import GaussianStrategy
+    from rlkit.exploration_strategies.ou_strategy import OUStrategy
+    import rlkit.samplers as ref_samplers
+    if not hasattr(ref_samplers, "rollout"):   # ddpg.py:11 imports a name rlkit.samplers no longer has; only pretrain() (normalizers) calls it
+        ref_samplers.rollout = None
+    from rlkit.torch.algorithms.ddpg.ddpg import DDPG
+    from rlkit.torch.common.networks import FlattenMlp
+    from rlkit.torch.common.policies import MlpPolicy
+    steps = 3
+    rec = dict(steps=np.array(steps), discount=np.array(DDPG_DISCOUNT))
+    for c, (o, a, Hh, B, seed, tanh_out, kw) in enumerate(DDPG_CASES):
+        rng, pi0, q0 = ddpg_init(seed, o, a, Hh)
+        pol = MlpPolicy(hidden_sizes=Hh, obs_dim=o, action_dim=a, **(dict(output_activation=torch.tanh) if tanh_out else {}))
+        qf = FlattenMlp(hidden_sizes=Hh, input_size=o + a, output_size=1)
+        set_flat(pol, pi0), set_flat(qf, q0)
+        tr = DDPG(policy=pol, qf=qf, **kw)
+        tr.discount = DDPG_DISCOUNT
+        grads = {}
+        _hook_grads(grads, tr.qf_optimizer, "q", qf), _hook_grads(grads, tr.policy_optimizer, "pi", pol)
+        pre = f"c{c}_"
+        wide = pi0.size > 8192 or q0.size > 8192
+        idx_pi = np.sort(rng.choice(pi0.size, 2048, replace=False)) if wide else np.arange(pi0.size)
+        idx_q = np.sort(rng.choice(q0.size, 2048, replace=False)) if wide else np.arange(q0.size)
+        rec.update({pre + "idx_pi": idx_pi.astype(np.int64), pre + "idx_q": idx_q.astype(np.int64)})
+        for s in range(steps):
+            batch = _rand_batch(rng, B, o, a)
+            tr.eval_statistics = None
+            tr.train_step({k: t(v) for k, v in batch.items()})
+            st = tr.eval_statistics
+            rec.update({f"{pre}s{s}_{k}": v for k, v in batch.items()})
+            rec[f"{pre}s{s}_losses"] = np.array([st[k] for k in ("QF Loss", "Policy Loss", "Raw Policy Loss", "Preactivation Policy Loss")], np.float32)
+            for name in DDPG_STATS:
+                rec[f"{pre}s{s}_{name.lower().replace(' ', '_')}"] = np.array([st[f"{name} {k}"] for k in ("Mean", "Std", "Max", "Min")], np.float32)
+            if s == 0:
+                rec.update({pre + "grad_q": grads["q"][idx_q], pre + "grad_pi": grads["pi"][idx_pi]})
+            if np.isfinite(kw.get("min_q_value", -np.inf)):   # the clamp bites on between 10 % and 90 % of the rows of every step
+                with torch.no_grad():
+                    # (after the step: a 1e-3-sized parameter move does not carry a row across the bounds' 10 % / 90 % margins)
+                    y = t(batch["rewards"]) + (1.0 - t(batch["terminals"])) * DDPG_DISCOUNT * tr.target_qf(t(batch["next_observations"]), tr.target_policy(t(batch["next_observations"])))
+                frac = float(((y <= kw["min_q_value"]) | (y >= kw["max_q_value"])).float().mean())
+                assert 0.1 < frac < 0.9, (c, s, frac)
+                assert st["Q Targets Max"] == np.float32(kw["max_q_value"]) and st["Q Targets Min"] == np.float32(kw["min_q_value"])
+                rec[f"{pre}s{s}_clamp_frac"] = np.array(frac)
+            if c == 0:
+                rec.update({f"{pre}s{s}_pi": get_flat(pol), f"{pre}s{s}_q": get_flat(qf), f"{pre}s{s}_tpi": get_flat(tr.target_policy),
+                            f"{pre}s{s}_tq": get_flat(tr.target_qf)})
+                if s == 1:   # no copy on step 1: the targets are still step 0's and measurably away from the online networks
+                    assert np.abs(get_flat(qf) - get_flat(tr.target_qf)).max() > 1e-3 and np.abs(get_flat(pol) - get_flat(tr.target_policy)).max() > 1e-3
+                    assert np.array_equal(get_flat(tr.target_qf), rec[f"{pre}s0_q"])
+                else:
+                    assert np.array_equal(get_flat(tr.target_qf), get_flat(qf)) and np.array_equal(get_flat(tr.target_policy), get_flat(pol))
+        rec.update({pre + "pi": get_flat(pol)[idx_pi], pre + "q": get_flat(qf)[idx_q], pre + "tpi": get_flat(tr.target_policy)[idx_pi],
+                    pre + "tq": get_flat(tr.target_qf)[idx_q]})
+    space = SimpleNamespace(shape=(3,), low=-np.ones(3, np.float32), high=np.ones(3, np.float32))
+    ou_kw = dict(mu=0.1, theta=0.15, max_sigma=0.6, min_sigma=0.1, decay_period=140)
+    ga_kw = dict(max_sigma=0.8, min_sigma=0.05, decay_period=140)
+    rec["ou_raw"], rec["ou_eps"], rec["ou_out"] = _explore_trace(lambda: OUStrategy(space, **ou_kw))
+    rec["ga_raw"], rec["ga_eps"], rec["ga_out"] = _explore_trace(lambda: GaussianStrategy(space, **ga_kw))
+    rec["ou_kw"] = np.array([ou_kw[k] for k in ("mu", "theta", "max_sigma", "min_sigma", "decay_period")], np.float64)
+    rec["ga_kw"] = np.array([ga_kw[k] for k in ("max_sigma", "min_sigma", "decay_period")], np.float64)
+    save("g31_ddpg", **rec)
+
+
 def gen_gcsl():
     """G29: GCSL (gcsl/gcsl.py, relabel_horizon_replay_buffer.py) with the reference's own trainer, buffer, policies and DiscretEnv.
     buf_*: HindsightHorizonReplayBuffer.random_batch on point-reach-shaped paths in a 40-slot ring (the last path wraps it): the indices it
@@ -1690,7 +1814,7 @@ GROUPS = dict(mlp=gen_mlp, mlp_unequal=gen_mlp_unequal, head=gen_head, sac_alpha
               disc=gen_disc, disc_bn=gen_disc_bn, disc_blocks=gen_disc_blocks, disc_branches=gen_disc_branches, replay=gen_replay,
               replay_trajs=gen_replay_trajs, her=gen_her, absorbing=gen_absorbing, bc=gen_bc, rms=gen_rms_actionmap, terminals=gen_terminals,
               eval_stats=gen_eval_stats, variants=gen_variants, logger_csv=gen_logger_csv, logdir=gen_logdir, mbpo=gen_mbpo,
-              discrete_sac=gen_discrete_sac, gcsl=gen_gcsl)
+              discrete_sac=gen_discrete_sac, gcsl=gen_gcsl, ddpg=gen_ddpg)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GROUPS)
