@@ -143,10 +143,13 @@ class PPOOracle:
         """perms: list (one per epoch) of index permutations (torch.randperm in the reference, ppo.py:116)."""
         obs, act, R, A, V = self.calc_adv(trajs)
         lp_old = self.log_prob(obs, act)[0]
-        out = dict(returns=R, advantages=A, fixed_log_probs=lp_old)
+        out = dict(returns=R, advantages=A, fixed_log_probs=lp_old, values=V)
+        # every minibatch's gradients in order (value: with the L2 term; policy: before the norm clip) next to the last one's under the old keys
+        out.update(vf_grads=[], pi_grads=[], pi_grad_norms=[])
         for perm in perms:
             for s in range(0, len(perm), self.mb):
                 ind = perm[s:s + self.mb]
                 out["vf_loss"], out["vf_grad"] = self.value_step(obs[ind], R[ind], V[ind])
                 out["pg_loss"], out["pi_grad"], out["pi_grad_norm"] = self.policy_step(obs[ind], act[ind], A[ind], lp_old[ind])
+                out["vf_grads"].append(out["vf_grad"]); out["pi_grads"].append(out["pi_grad"]); out["pi_grad_norms"].append(out["pi_grad_norm"])
         return out
