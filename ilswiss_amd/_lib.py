@@ -258,6 +258,7 @@ PROTOTYPES = {
     "ilsx_her_gather": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]),
     "ilsx_debug_rng_stream": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "ilsx_debug_philox": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, vp, vp]),
+    "ilsx_debug_ctx_allocs": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
     "ilsx_disc_destroy": (C.c_int, [vp]),
     "ilsx_disc_num_params": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
     "ilsx_disc_set_params": (C.c_int, [vp, vp, C.c_size_t]),

@@ -18,104 +18,203 @@
 
 enum { CLASSIC_CARTPOLE = 0, CLASSIC_PENDULUM = 1, CLASSIC_INVERTED_PENDULUM = 2, CLASSIC_INVERTED_DOUBLE_PENDULUM = 3 };
 
-struct CartPoleC {
-  static constexpr double gravity = 9.8, masscart = 1.0, masspole = 0.1, length = 0.5, force_mag = 10.0, tau = 0.02;
-  static constexpr double x_threshold = 2.4;
+// ------------------------------------------------------------------------------------------------ the lane-per-env frame
+// One lane per env, one frame for every task of this engine (and for swimmer_env.h): the rollout protocol is written once here and a task
+// type supplies what differs —
+//   NQ, NV, O, NA      sizes of qpos, qvel, the observation and the action row
+//   Model              constants passed to the kernel by value (empty for CartPole and Pendulum)
+//   State              q[NQ], v[NV] and whatever else the task carries from the dynamics to the observation
+//   reset_state        the draws of reset_model() from the env's Philox stream
+//   write_obs          _get_obs()
+//   obs_before         the observation the record opens with: write_obs, unless the env showed something the state does not hold
+//   advance            one env step: the new state, its reward, done and whether the state is finite
+//   never_done         the task never reports done: done and the terminal bit of flush_len are constants
+// Everything the tail needs from the arguments is turned into per-lane values BEFORE advance (the addresses it stores to, the action the
+// record holds, the episode's length): a long dynamics loop then carries them in vector registers, of which there are plenty, instead of
+// keeping forty-odd scalar registers of arguments alive across it.
+struct LaneResetArgs {
+  double *qpos, *qvel;
+  int n_env;
+  const int* ids;   // nullable, compact indexing of obs as in EnvStepArgs
+  int n_ids;
+  float *obs, *obs_cur;
+  int* ep_len; double* ep_ret;
+  uint64_t seed; uint32_t stream; unsigned long long step;
 };
 
-__device__ __forceinline__ void cartpole_write_obs(double x, double xd, double th, double thd, float* dst) {
-  dst[0] = (float)x; dst[1] = (float)xd; dst[2] = (float)th; dst[3] = (float)thd;
-}
-
-// reset(): np_random.uniform(low=-0.05, high=0.05, size=(4,)) — component k from counter k of the env's Philox stream
-__device__ __forceinline__ void cartpole_reset_state(uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, double (&s)[4]) {
-  s[0] = -0.05 + 0.1 * env_uniform(seed, stream, step, env, 0);
-  s[1] = -0.05 + 0.1 * env_uniform(seed, stream, step, env, 1);
-  s[2] = -0.05 + 0.1 * env_uniform(seed, stream, step, env, 2);
-  s[3] = -0.05 + 0.1 * env_uniform(seed, stream, step, env, 3);
-}
-
-__global__ __launch_bounds__(256) void k_cartpole_step(const EnvStepArgs A) {
+template <class T>
+__device__ __forceinline__ void lane_step_frame(const EnvStepArgs& A, const typename T::Model& m) {
+  constexpr int NQ = T::NQ, NV = T::NV, O = T::O, NA = T::NA;
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= A.n_ids) return;
   const int env = A.ids ? A.ids[t] : t;
   if (A.frozen && A.frozen[env]) return;
   const size_t ne = (size_t)A.n_env;
-  double x = A.qpos[env], th = A.qpos[ne + env], xd = A.qvel[env], thd = A.qvel[ne + env];
-  float obs_before[4];
-  if (A.replay) cartpole_write_obs(x, xd, th, thd, obs_before);
-  const float av = A.act[t];
-  // cartpole.py step(): constants derived exactly as __init__ derives them
-  const double total_mass = CartPoleC::masspole + CartPoleC::masscart;
-  const double polemass_length = CartPoleC::masspole * CartPoleC::length;
-  const double theta_threshold = 12.0 * 2.0 * 3.141592653589793 / 360.0;
-  const double force = av == 1.0f ? CartPoleC::force_mag : -CartPoleC::force_mag;
-  const double costheta = cos(th), sintheta = sin(th);
-  const double temp = (force + polemass_length * (thd * thd) * sintheta) / total_mass;
-  const double thetaacc = (CartPoleC::gravity * sintheta - costheta * temp) /
-                          (CartPoleC::length * (4.0 / 3.0 - CartPoleC::masspole * (costheta * costheta) / total_mass));
-  const double xacc = temp - polemass_length * thetaacc * costheta / total_mass;
-  x = x + CartPoleC::tau * xd;
-  xd = xd + CartPoleC::tau * xacc;
-  th = th + CartPoleC::tau * thd;
-  thd = thd + CartPoleC::tau * thetaacc;
-  const bool done = x < -CartPoleC::x_threshold || x > CartPoleC::x_threshold || th < -theta_threshold || th > theta_threshold;
-  const double reward = 1.0;
-  float ob[4];
-  cartpole_write_obs(x, xd, th, thd, ob);
-  if (A.obs) for (int i = 0; i < 4; ++i) A.obs[(size_t)t * 4 + i] = ob[i];
-  if (A.rew) A.rew[t] = (float)reward;
-  if (A.done) A.done[t] = done ? 1 : 0;
-  if (A.replay) {   // fused replay insert (k_env_step's record layout with a 1-wide action column)
+  double* const qp = A.qpos + env;
+  double* const vp = A.qvel + env;
+  typename T::State s{};
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) s.q[i] = qp[i * ne];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) s.v[i] = vp[i * ne];
+  float* const obs_p = A.obs ? A.obs + (size_t)t * O : nullptr;
+  float* const rew_p = A.rew ? A.rew + t : nullptr;
+  unsigned char* const done_p = A.done ? A.done + t : nullptr;
+  float* const cur_p = A.obs_cur ? A.obs_cur + (size_t)env * O : nullptr;
+  float* rec = nullptr;   // fused replay insert (k_env_step's record layout: obs | act | rew | done | next_obs | absorbing[2])
+  if (A.replay) {
     long long slot = A.top + env;
     if (slot >= A.cap) slot -= A.cap;
-    float* rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
-    for (int i = 0; i < 4; ++i) rec[i] = obs_before[i];
-    rec[4] = A.rec_act ? A.rec_act[t] : av;
-    rec[5] = (float)reward;
-    rec[6] = (done && !A.no_terminal) ? 1.0f : 0.0f;
-    for (int i = 0; i < 4; ++i) rec[7 + i] = ob[i];
-    rec[11] = 0.0f; rec[12] = 0.0f;   // absorbing = [0, 0]
+    rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
   }
-  if (A.auto_reset) {
-    const int len = A.ep_len[env] + 1;
-    const double ret = A.ep_ret[env] + reward;
-    const bool finite = isfinite(x) && isfinite(xd) && isfinite(th) && isfinite(thd);
-    const bool end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // as k_env_step
+  float av[NA];
+#pragma unroll
+  for (int j = 0; j < NA; ++j) av[j] = A.act[(size_t)t * NA + j];
+  if (rec) {
+    float obs_before[O];
+    T::obs_before(s, cur_p, obs_before);
+#pragma unroll
+    for (int i = 0; i < O; ++i) rec[i] = obs_before[i];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) rec[O + j] = A.rec_act ? A.rec_act[(size_t)t * NA + j] : av[j];   // the record holds the unmapped action
+  }
+  // auto-reset bookkeeping that does not depend on the step: the episode's length and whether it ends at the path limit, the return so far
+  int len = 0;
+  bool limit = false;
+  double ret0 = 0.0;
+  int* const len_p = A.ep_len + env;
+  double* const ret_p = A.ep_ret + env;
+  int* const flush_p = (A.auto_reset && A.flush_len) ? A.flush_len + env : nullptr;
+  double* const stats_p = A.stats;
+  const bool auto_reset = A.auto_reset != 0, no_terminal = A.no_terminal != 0;
+  if (auto_reset) {
+    len = *len_p + 1;
+    ret0 = *ret_p;
+    limit = len >= A.max_path_length;
+  }
+  double reward;
+  bool done, finite;
+  T::advance(m, s, av, reward, done, finite);
+  const bool terminal = !T::never_done && done && !no_terminal;
+  float ob[O];
+  T::write_obs(s, ob);
+  if (obs_p) {
+#pragma unroll
+    for (int i = 0; i < O; ++i) obs_p[i] = ob[i];
+  }
+  if (rew_p) *rew_p = (float)reward;
+  if (done_p) *done_p = (!T::never_done && done) ? 1 : 0;
+  if (rec) {
+    rec[O + NA] = (float)reward;
+    rec[O + NA + 1] = terminal ? 1.0f : 0.0f;
+#pragma unroll
+    for (int i = 0; i < O; ++i) rec[O + NA + 2 + i] = ob[i];
+    rec[2 * O + NA + 2] = 0.0f; rec[2 * O + NA + 3] = 0.0f;   // absorbing = [0, 0]
+  }
+  if (auto_reset) {
+    const double ret = ret0 + reward;
+    const bool end = terminal || limit || !finite;   // as k_env_step
     if (end) {
-      atomicAdd(&A.stats[0], 1.0);
-      atomicAdd(&A.stats[1], ret);
-      double s[4];
-      cartpole_reset_state(A.seed, A.stream, A.step, (uint32_t)env, s);
-      x = s[0]; xd = s[1]; th = s[2]; thd = s[3];
-      cartpole_write_obs(x, xd, th, thd, ob);
+      atomicAdd(&stats_p[0], 1.0);
+      atomicAdd(&stats_p[1], ret);
+      T::reset_state(m, A.seed, A.stream, A.step, (uint32_t)env, s);   // drawn when an episode ends, not on every step
+      T::write_obs(s, ob);
     }
-    A.ep_len[env] = end ? 0 : len;
-    A.ep_ret[env] = end ? 0.0 : ret;
-    if (A.flush_len) A.flush_len[env] = end ? (len | ((done && !A.no_terminal) ? (1 << 30) : 0)) : 0;
+    *len_p = end ? 0 : len;
+    *ret_p = end ? 0.0 : ret;
+    if (flush_p) *flush_p = end ? (len | (terminal ? (1 << 30) : 0)) : 0;
   }
-  if (A.obs_cur) for (int i = 0; i < 4; ++i) A.obs_cur[(size_t)env * 4 + i] = ob[i];
-  A.qpos[env] = x; A.qpos[ne + env] = th; A.qvel[env] = xd; A.qvel[ne + env] = thd;
+  if (cur_p) {
+#pragma unroll
+    for (int i = 0; i < O; ++i) cur_p[i] = ob[i];
+  }
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) qp[i * ne] = s.q[i];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) vp[i * ne] = s.v[i];
 }
 
-__global__ __launch_bounds__(256) void k_cartpole_reset(double* qpos, double* qvel, int n_env, const int* ids, int n_ids, float* obs,
-                                                       float* obs_cur, int* ep_len, double* ep_ret, uint64_t seed, uint32_t stream,
-                                                       unsigned long long step) {
+template <class T>
+__device__ __forceinline__ void lane_reset_frame(const LaneResetArgs& R, const typename T::Model& m) {
+  constexpr int NQ = T::NQ, NV = T::NV, O = T::O;
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_ids) return;
-  const int env = ids ? ids[t] : t;
-  double s[4];
-  cartpole_reset_state(seed, stream, step, (uint32_t)env, s);
-  float ob[4];
-  cartpole_write_obs(s[0], s[1], s[2], s[3], ob);
-  for (int i = 0; i < 4; ++i) {
-    if (obs) obs[(size_t)t * 4 + i] = ob[i];
-    if (obs_cur) obs_cur[(size_t)env * 4 + i] = ob[i];
+  if (t >= R.n_ids) return;
+  const int env = R.ids ? R.ids[t] : t;
+  typename T::State s{};
+  T::reset_state(m, R.seed, R.stream, R.step, (uint32_t)env, s);
+  float ob[O];
+  T::write_obs(s, ob);
+#pragma unroll
+  for (int i = 0; i < O; ++i) {
+    if (R.obs) R.obs[(size_t)t * O + i] = ob[i];
+    if (R.obs_cur) R.obs_cur[(size_t)env * O + i] = ob[i];
   }
-  ep_len[env] = 0; ep_ret[env] = 0.0;
-  const size_t ne = (size_t)n_env;
-  qpos[env] = s[0]; qpos[ne + env] = s[2]; qvel[env] = s[1]; qvel[ne + env] = s[3];
+  R.ep_len[env] = 0; R.ep_ret[env] = 0.0;
+  const size_t ne = (size_t)R.n_env;
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) R.qpos[i * ne + env] = s.q[i];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) R.qvel[i * ne + env] = s.v[i];
 }
+
+// What most tasks share: the state is (q, v) and the record opens with the observation of that state
+template <int NQ_, int NV_>
+struct LaneStateQV { double q[NQ_], v[NV_]; };
+struct LaneNoModel {};
+
+// ------------------------------------------------------------------------------------------------ CartPole
+
+struct CartPoleC {
+  static constexpr double gravity = 9.8, masscart = 1.0, masspole = 0.1, length = 0.5, force_mag = 10.0, tau = 0.02;
+  static constexpr double x_threshold = 2.4;
+};
+
+// qpos = (x, theta), qvel = (x_dot, theta_dot)
+struct CartPoleTask {
+  static constexpr int NQ = 2, NV = 2, O = 4, NA = 1;
+  static constexpr bool never_done = false;
+  using Model = LaneNoModel;
+  using State = LaneStateQV<2, 2>;
+
+  static __device__ __forceinline__ void write_obs(const State& s, float* dst) {
+    dst[0] = (float)s.q[0]; dst[1] = (float)s.v[0]; dst[2] = (float)s.q[1]; dst[3] = (float)s.v[1];
+  }
+  static __device__ __forceinline__ void obs_before(const State& s, const float*, float* dst) { write_obs(s, dst); }
+
+  // reset(): np_random.uniform(low=-0.05, high=0.05, size=(4,)) — component k of (x, x_dot, theta, theta_dot) from counter k of the env's
+  // Philox stream
+  static __device__ __forceinline__ void reset_state(const Model&, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, State& s) {
+    s.q[0] = -0.05 + 0.1 * env_uniform(seed, stream, step, env, 0);
+    s.v[0] = -0.05 + 0.1 * env_uniform(seed, stream, step, env, 1);
+    s.q[1] = -0.05 + 0.1 * env_uniform(seed, stream, step, env, 2);
+    s.v[1] = -0.05 + 0.1 * env_uniform(seed, stream, step, env, 3);
+  }
+
+  static __device__ __forceinline__ void advance(const Model&, State& s, const float (&act)[1], double& reward, bool& done, bool& finite) {
+    double x = s.q[0], th = s.q[1], xd = s.v[0], thd = s.v[1];
+    // cartpole.py step(): constants derived exactly as __init__ derives them
+    const double total_mass = CartPoleC::masspole + CartPoleC::masscart;
+    const double polemass_length = CartPoleC::masspole * CartPoleC::length;
+    const double theta_threshold = 12.0 * 2.0 * 3.141592653589793 / 360.0;
+    const double force = act[0] == 1.0f ? CartPoleC::force_mag : -CartPoleC::force_mag;
+    const double costheta = cos(th), sintheta = sin(th);
+    const double temp = (force + polemass_length * (thd * thd) * sintheta) / total_mass;
+    const double thetaacc = (CartPoleC::gravity * sintheta - costheta * temp) /
+                            (CartPoleC::length * (4.0 / 3.0 - CartPoleC::masspole * (costheta * costheta) / total_mass));
+    const double xacc = temp - polemass_length * thetaacc * costheta / total_mass;
+    x = x + CartPoleC::tau * xd;
+    xd = xd + CartPoleC::tau * xacc;
+    th = th + CartPoleC::tau * thd;
+    thd = thd + CartPoleC::tau * thetaacc;
+    done = x < -CartPoleC::x_threshold || x > CartPoleC::x_threshold || th < -theta_threshold || th > theta_threshold;
+    reward = 1.0;   // on every step including the one that ends the episode
+    finite = isfinite(x) && isfinite(xd) && isfinite(th) && isfinite(thd);
+    s.q[0] = x; s.q[1] = th; s.v[0] = xd; s.v[1] = thd;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_cartpole_step(const EnvStepArgs A) { lane_step_frame<CartPoleTask>(A, {}); }
+__global__ __launch_bounds__(256) void k_cartpole_reset(const LaneResetArgs R) { lane_reset_frame<CartPoleTask>(R, {}); }
 
 // env.action_space.sample() of a Discrete(n) space per env while the replay is short (base_algorithm.py:369-380): a uniform index in
 // [0, n) as a float, one Philox draw per env (floor(u * n) with u in (0, 1); u * n < n for every u the draw can take, n <= 2^20)
@@ -152,88 +251,44 @@ __device__ __forceinline__ double pendulum_angle_normalize(double x) {
   return r - PendulumC::pi;
 }
 
-__device__ __forceinline__ void pendulum_write_obs(double th, double thd, float* dst) {   // _get_obs(): float32 (cos, sin, theta_dot)
-  dst[0] = (float)cos(th); dst[1] = (float)sin(th); dst[2] = (float)thd;
-}
+// qpos = (theta), qvel = (theta_dot)
+struct PendulumTask {
+  static constexpr int NQ = 1, NV = 1, O = 3, NA = 1;
+  static constexpr bool never_done = true;
+  using Model = LaneNoModel;
+  using State = LaneStateQV<1, 1>;
 
-// reset(): np_random.uniform(low=-[pi, 1], high=[pi, 1]) = low + (high - low) * u — component k from counter k of the env's Philox stream
-__device__ __forceinline__ void pendulum_reset_state(uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, double& th,
-                                                     double& thd) {
-  th = -PendulumC::pi + PendulumC::two_pi * env_uniform(seed, stream, step, env, 0);
-  thd = -1.0 + 2.0 * env_uniform(seed, stream, step, env, 1);
-}
+  static __device__ __forceinline__ void write_obs(const State& s, float* dst) {   // _get_obs(): float32 (cos, sin, theta_dot)
+    dst[0] = (float)cos(s.q[0]); dst[1] = (float)sin(s.q[0]); dst[2] = (float)s.v[0];
+  }
+  static __device__ __forceinline__ void obs_before(const State& s, const float*, float* dst) { write_obs(s, dst); }
 
-__global__ __launch_bounds__(256) void k_pendulum_step(const EnvStepArgs A) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= A.n_ids) return;
-  const int env = A.ids ? A.ids[t] : t;
-  if (A.frozen && A.frozen[env]) return;
-  double th = A.qpos[env], thd = A.qvel[env];
-  float obs_before[3];
-  if (A.replay) pendulum_write_obs(th, thd, obs_before);
-  const float av = A.act[t];
-  const double u = (double)pendulum_torque(av);
-  // cost in float64 with u promoted exactly, summed left to right.  Had numpy rounded u**2 to float32 (a float32 scalar to an integer
-  // power), the cost would move by < 3e-10: below the resolution of the float32 reward that is stored.
-  const double an = pendulum_angle_normalize(th);
-  const double cost = an * an + 0.1 * (thd * thd) + 0.001 * (u * u);
-  const double reward = -cost;
-  // gym 0.22's order: the velocity is clipped BEFORE the position update (0.21 clipped afterwards and wrote -sin(theta + pi))
-  thd = thd + (PendulumC::k_sin * sin(th) + PendulumC::k_u * u) * PendulumC::dt;
-  thd = thd < -PendulumC::max_speed ? -PendulumC::max_speed : (thd > PendulumC::max_speed ? PendulumC::max_speed : thd);
-  th = th + thd * PendulumC::dt;
-  const bool done = false;
-  float ob[3];
-  pendulum_write_obs(th, thd, ob);
-  if (A.obs) for (int i = 0; i < 3; ++i) A.obs[(size_t)t * 3 + i] = ob[i];
-  if (A.rew) A.rew[t] = (float)reward;
-  if (A.done) A.done[t] = 0;
-  if (A.replay) {   // fused replay insert (k_env_step's record layout: obs | act | rew | done | next_obs | absorbing[2]); the unmapped action
-    long long slot = A.top + env;
-    if (slot >= A.cap) slot -= A.cap;
-    float* rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
-    for (int i = 0; i < 3; ++i) rec[i] = obs_before[i];
-    rec[3] = A.rec_act ? A.rec_act[t] : av;
-    rec[4] = (float)reward;
-    rec[5] = 0.0f;
-    for (int i = 0; i < 3; ++i) rec[6 + i] = ob[i];
-    rec[9] = 0.0f; rec[10] = 0.0f;   // absorbing = [0, 0]
+  // reset(): np_random.uniform(low=-[pi, 1], high=[pi, 1]) = low + (high - low) * u — component k from counter k of the env's Philox stream
+  static __device__ __forceinline__ void reset_state(const Model&, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, State& s) {
+    s.q[0] = -PendulumC::pi + PendulumC::two_pi * env_uniform(seed, stream, step, env, 0);
+    s.v[0] = -1.0 + 2.0 * env_uniform(seed, stream, step, env, 1);
   }
-  if (A.auto_reset) {
-    const int len = A.ep_len[env] + 1;
-    const double ret = A.ep_ret[env] + reward;
-    const bool finite = isfinite(th) && isfinite(thd);
-    const bool end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // as k_env_step
-    if (end) {
-      atomicAdd(&A.stats[0], 1.0);
-      atomicAdd(&A.stats[1], ret);
-      pendulum_reset_state(A.seed, A.stream, A.step, (uint32_t)env, th, thd);
-      pendulum_write_obs(th, thd, ob);
-    }
-    A.ep_len[env] = end ? 0 : len;
-    A.ep_ret[env] = end ? 0.0 : ret;
-    if (A.flush_len) A.flush_len[env] = end ? len : 0;   // never terminal
-  }
-  if (A.obs_cur) for (int i = 0; i < 3; ++i) A.obs_cur[(size_t)env * 3 + i] = ob[i];
-  A.qpos[env] = th; A.qvel[env] = thd;
-}
 
-__global__ __launch_bounds__(256) void k_pendulum_reset(double* qpos, double* qvel, const int* ids, int n_ids, float* obs, float* obs_cur,
-                                                        int* ep_len, double* ep_ret, uint64_t seed, uint32_t stream, unsigned long long step) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_ids) return;
-  const int env = ids ? ids[t] : t;
-  double th, thd;
-  pendulum_reset_state(seed, stream, step, (uint32_t)env, th, thd);
-  float ob[3];
-  pendulum_write_obs(th, thd, ob);
-  for (int i = 0; i < 3; ++i) {
-    if (obs) obs[(size_t)t * 3 + i] = ob[i];
-    if (obs_cur) obs_cur[(size_t)env * 3 + i] = ob[i];
+  static __device__ __forceinline__ void advance(const Model&, State& s, const float (&act)[1], double& reward, bool& done, bool& finite) {
+    double th = s.q[0], thd = s.v[0];
+    const double u = (double)pendulum_torque(act[0]);
+    // cost in float64 with u promoted exactly, summed left to right.  Had numpy rounded u**2 to float32 (a float32 scalar to an integer
+    // power), the cost would move by < 3e-10: below the resolution of the float32 reward that is stored.
+    const double an = pendulum_angle_normalize(th);
+    const double cost = an * an + 0.1 * (thd * thd) + 0.001 * (u * u);
+    reward = -cost;
+    // gym 0.22's order: the velocity is clipped BEFORE the position update (0.21 clipped afterwards and wrote -sin(theta + pi))
+    thd = thd + (PendulumC::k_sin * sin(th) + PendulumC::k_u * u) * PendulumC::dt;
+    thd = thd < -PendulumC::max_speed ? -PendulumC::max_speed : (thd > PendulumC::max_speed ? PendulumC::max_speed : thd);
+    th = th + thd * PendulumC::dt;
+    done = false;
+    finite = isfinite(th) && isfinite(thd);
+    s.q[0] = th; s.v[0] = thd;
   }
-  ep_len[env] = 0; ep_ret[env] = 0.0;
-  qpos[env] = th; qvel[env] = thd;
-}
+};
+
+__global__ __launch_bounds__(256) void k_pendulum_step(const EnvStepArgs A) { lane_step_frame<PendulumTask>(A, {}); }
+__global__ __launch_bounds__(256) void k_pendulum_reset(const LaneResetArgs R) { lane_reset_frame<PendulumTask>(R, {}); }
 
 // ------------------------------------------------------------------------------------------------ cart + chain of poles
 // InvertedPendulum (NP = 1) and InvertedDoublePendulum (NP = 2): gym 0.22's task rules on this repository's own rigid-body dynamics, in
@@ -422,142 +477,84 @@ __device__ __forceinline__ void cartchain_substep(const CartChainDev& m, double 
   }
 }
 
-template <int NP> struct CartChainDims { static constexpr int N = NP + 1, O = NP == 1 ? 4 : 11; };
-
 __device__ __forceinline__ float cartchain_clip10(double x) { return (float)(x < -10.0 ? -10.0 : (x > 10.0 ? 10.0 : x)); }   // np.clip: NaN stays
 
-// _get_obs(): InvertedPendulum (qpos | qvel); InvertedDoublePendulum (x, sin th, cos th, clip(qvel, +-10), clip(qfrc_constraint, +-10))
 template <int NP>
-__device__ __forceinline__ void cartchain_write_obs(const double (&q)[NP + 1], const double (&v)[NP + 1], const double (&qfrc)[NP + 1], float* dst) {
-  if constexpr (NP == 1) {
-    dst[0] = (float)q[0]; dst[1] = (float)q[1]; dst[2] = (float)v[0]; dst[3] = (float)v[1];
-  } else {
-    dst[0] = (float)q[0];
-    dst[1] = (float)sin(q[1]); dst[2] = (float)sin(q[2]);
-    dst[3] = (float)cos(q[1]); dst[4] = (float)cos(q[2]);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { dst[5 + i] = cartchain_clip10(v[i]); dst[8 + i] = cartchain_clip10(qfrc[i]); }
-  }
-}
+struct CartChainTask {
+  static constexpr int N = NP + 1, NQ = N, NV = N, O = NP == 1 ? 4 : 11, NA = 1;
+  static constexpr bool never_done = false;
+  using Model = CartChainDev;
+  struct State { double q[N], v[N], qfrc[N]; };   // qfrc: the constraint force of the step that produced the state (0 after a reset)
 
-// reset_model(): InvertedPendulum init + U(+-0.01) on qpos and qvel (counters 0..3 of the env's Philox stream); InvertedDoublePendulum
-// qpos = init + U(+-0.1) (counters 0..2), qvel = 0.1 * randn by env_reset_state's Box-Muller draw (counters 3 + 2 i, 4 + 2 i)
-template <int NP>
-__device__ __forceinline__ void cartchain_reset_state(uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, double (&q)[NP + 1],
-                                                      double (&v)[NP + 1]) {
-  constexpr int N = NP + 1;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
+  // _get_obs(): InvertedPendulum (qpos | qvel); InvertedDoublePendulum (x, sin th, cos th, clip(qvel, +-10), clip(qfrc_constraint, +-10))
+  static __device__ __forceinline__ void write_obs(const State& s, float* dst) {
     if constexpr (NP == 1) {
-      q[i] = -0.01 + 0.02 * env_uniform(seed, stream, step, env, i);
-      v[i] = -0.01 + 0.02 * env_uniform(seed, stream, step, env, N + i);
+      dst[0] = (float)s.q[0]; dst[1] = (float)s.q[1]; dst[2] = (float)s.v[0]; dst[3] = (float)s.v[1];
     } else {
-      q[i] = -0.1 + 0.2 * env_uniform(seed, stream, step, env, i);
-      const double u1 = env_uniform(seed, stream, step, env, N + 2 * i), u2 = env_uniform(seed, stream, step, env, N + 2 * i + 1);
-      v[i] = 0.1 * (sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+      dst[0] = (float)s.q[0];
+      dst[1] = (float)sin(s.q[1]); dst[2] = (float)sin(s.q[2]);
+      dst[3] = (float)cos(s.q[1]); dst[4] = (float)cos(s.q[2]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { dst[5 + i] = cartchain_clip10(s.v[i]); dst[8 + i] = cartchain_clip10(s.qfrc[i]); }
     }
   }
-}
-
-template <int NP>
-__global__ __launch_bounds__(256) void k_cartchain_step(const EnvStepArgs A, const CartChainDev m) {
-  constexpr int N = CartChainDims<NP>::N, O = CartChainDims<NP>::O;
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= A.n_ids) return;
-  const int env = A.ids ? A.ids[t] : t;
-  if (A.frozen && A.frozen[env]) return;
-  const size_t ne = (size_t)A.n_env;
-  double q[N], v[N], qfrc[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) { q[i] = A.qpos[i * ne + env]; v[i] = A.qvel[i * ne + env]; qfrc[i] = 0.0; }
-  float obs_before[O];
-  if (A.replay) {
-    cartchain_write_obs<NP>(q, v, qfrc, obs_before);
-    // the constraint force belongs to the step that produced the state: the columns the env showed for it (0 after a reset)
+  // the constraint force belongs to the step that produced the state, which (q, v) does not hold: the record opens with the columns the
+  // env showed for it (0 after a reset).  They are loaded BEFORE write_obs, whose trigonometry then hides the round trip: the record's
+  // first stores wait for them ahead of the dynamics.
+  static __device__ __forceinline__ void obs_before(const State& s, const float* obs_cur, float* dst) {
+    float shown[3] = {0.0f, 0.0f, 0.0f};
     if constexpr (NP == 2)
-      if (A.obs_cur)
-        for (int i = 0; i < 3; ++i) obs_before[8 + i] = A.obs_cur[(size_t)env * O + 8 + i];
+      if (obs_cur)
+        for (int i = 0; i < 3; ++i) shown[i] = obs_cur[8 + i];
+    write_obs(s, dst);
+    if constexpr (NP == 2)
+      if (obs_cur)
+        for (int i = 0; i < 3; ++i) dst[8 + i] = shown[i];
   }
-  const float av = A.act[t];
-  const double tau0 = m.gear * (double)cartchain_ctrl(av, m.ctrl_lo, m.ctrl_hi);
-#pragma unroll 1
-  for (int s = 0; s < m.frame_skip; ++s) cartchain_substep<NP>(m, q, v, tau0, qfrc);
-  bool finite = true;
+
+  // reset_model(): InvertedPendulum init + U(+-0.01) on qpos and qvel (counters 0..3 of the env's Philox stream); InvertedDoublePendulum
+  // qpos = init + U(+-0.1) (counters 0..2), qvel = 0.1 * randn by env_reset_state's Box-Muller draw (counters 3 + 2 i, 4 + 2 i)
+  static __device__ __forceinline__ void reset_state(const Model&, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, State& s) {
 #pragma unroll
-  for (int i = 0; i < N; ++i) finite = finite && isfinite(q[i]) && isfinite(v[i]);
-  bool done;
-  double reward;
-  if constexpr (NP == 1) {
-    reward = 1.0;
-    done = !finite || fabs(q[1]) > 0.2;
-  } else {
-    // tip site of pole 2: cart + hinge 2 (pole 1's frame) + site (pole 2's frame)
-    const double p1 = m.jsign * q[1], p2 = m.jsign * q[1] + m.jsign * q[2];
-    const double s1 = sin(p1), c1 = cos(p1), s2 = sin(p2), c2 = cos(p2);
-    const double xt = q[0] + (c1 * m.anchor[2][0] - s1 * m.anchor[2][1]) + (c2 * m.tip[0] - s2 * m.tip[1]);
-    const double yt = (s1 * m.anchor[2][0] + c1 * m.anchor[2][1]) + (s2 * m.tip[0] + c2 * m.tip[1]);
-    const double dist_penalty = 0.01 * (xt * xt) + (yt - 2.0) * (yt - 2.0);
-    const double vel_penalty = 1e-3 * (v[1] * v[1]) + 5e-3 * (v[2] * v[2]);
-    reward = 10.0 - dist_penalty - vel_penalty;
-    done = yt <= 1.0;
-  }
-  float ob[O];
-  cartchain_write_obs<NP>(q, v, qfrc, ob);
-  if (A.obs) for (int i = 0; i < O; ++i) A.obs[(size_t)t * O + i] = ob[i];
-  if (A.rew) A.rew[t] = (float)reward;
-  if (A.done) A.done[t] = done ? 1 : 0;
-  if (A.replay) {   // fused replay insert (k_env_step's record layout with a 1-wide action column); the unmapped action
-    long long slot = A.top + env;
-    if (slot >= A.cap) slot -= A.cap;
-    float* rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
-    for (int i = 0; i < O; ++i) rec[i] = obs_before[i];
-    rec[O] = A.rec_act ? A.rec_act[t] : av;
-    rec[O + 1] = (float)reward;
-    rec[O + 2] = (done && !A.no_terminal) ? 1.0f : 0.0f;
-    for (int i = 0; i < O; ++i) rec[O + 3 + i] = ob[i];
-    rec[2 * O + 3] = 0.0f; rec[2 * O + 4] = 0.0f;   // absorbing = [0, 0]
-  }
-  if (A.auto_reset) {
-    const int len = A.ep_len[env] + 1;
-    const double ret = A.ep_ret[env] + reward;
-    const bool end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // as k_env_step
-    if (end) {
-      atomicAdd(&A.stats[0], 1.0);
-      atomicAdd(&A.stats[1], ret);
-      cartchain_reset_state<NP>(A.seed, A.stream, A.step, (uint32_t)env, q, v);
-#pragma unroll
-      for (int i = 0; i < N; ++i) qfrc[i] = 0.0;
-      cartchain_write_obs<NP>(q, v, qfrc, ob);
+    for (int i = 0; i < N; ++i) {
+      if constexpr (NP == 1) {
+        s.q[i] = -0.01 + 0.02 * env_uniform(seed, stream, step, env, i);
+        s.v[i] = -0.01 + 0.02 * env_uniform(seed, stream, step, env, N + i);
+      } else {
+        s.q[i] = -0.1 + 0.2 * env_uniform(seed, stream, step, env, i);
+        const double u1 = env_uniform(seed, stream, step, env, N + 2 * i), u2 = env_uniform(seed, stream, step, env, N + 2 * i + 1);
+        s.v[i] = 0.1 * (sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+      }
+      s.qfrc[i] = 0.0;
     }
-    A.ep_len[env] = end ? 0 : len;
-    A.ep_ret[env] = end ? 0.0 : ret;
-    if (A.flush_len) A.flush_len[env] = end ? (len | ((done && !A.no_terminal) ? (1 << 30) : 0)) : 0;
   }
-  if (A.obs_cur) for (int i = 0; i < O; ++i) A.obs_cur[(size_t)env * O + i] = ob[i];
+
+  static __device__ __forceinline__ void advance(const Model& m, State& s, const float (&act)[1], double& reward, bool& done, bool& finite) {
+    double (&q)[N] = s.q, (&v)[N] = s.v;
+    const double tau0 = m.gear * (double)cartchain_ctrl(act[0], m.ctrl_lo, m.ctrl_hi);
+#pragma unroll 1
+    for (int k = 0; k < m.frame_skip; ++k) cartchain_substep<NP>(m, q, v, tau0, s.qfrc);
+    finite = true;
 #pragma unroll
-  for (int i = 0; i < N; ++i) { A.qpos[i * ne + env] = q[i]; A.qvel[i * ne + env] = v[i]; }
-}
+    for (int i = 0; i < N; ++i) finite = finite && isfinite(q[i]) && isfinite(v[i]);
+    if constexpr (NP == 1) {
+      reward = 1.0;
+      done = !finite || fabs(q[1]) > 0.2;
+    } else {
+      // tip site of pole 2: cart + hinge 2 (pole 1's frame) + site (pole 2's frame)
+      const double p1 = m.jsign * q[1], p2 = m.jsign * q[1] + m.jsign * q[2];
+      const double s1 = sin(p1), c1 = cos(p1), s2 = sin(p2), c2 = cos(p2);
+      const double xt = q[0] + (c1 * m.anchor[2][0] - s1 * m.anchor[2][1]) + (c2 * m.tip[0] - s2 * m.tip[1]);
+      const double yt = (s1 * m.anchor[2][0] + c1 * m.anchor[2][1]) + (s2 * m.tip[0] + c2 * m.tip[1]);
+      const double dist_penalty = 0.01 * (xt * xt) + (yt - 2.0) * (yt - 2.0);
+      const double vel_penalty = 1e-3 * (v[1] * v[1]) + 5e-3 * (v[2] * v[2]);
+      reward = 10.0 - dist_penalty - vel_penalty;
+      done = yt <= 1.0;
+    }
+  }
+};
 
 template <int NP>
-__global__ __launch_bounds__(256) void k_cartchain_reset(double* qpos, double* qvel, int n_env, const int* ids, int n_ids, float* obs,
-                                                         float* obs_cur, int* ep_len, double* ep_ret, uint64_t seed, uint32_t stream,
-                                                         unsigned long long step) {
-  constexpr int N = CartChainDims<NP>::N, O = CartChainDims<NP>::O;
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_ids) return;
-  const int env = ids ? ids[t] : t;
-  double q[N], v[N], qfrc[N];
-  cartchain_reset_state<NP>(seed, stream, step, (uint32_t)env, q, v);
-#pragma unroll
-  for (int i = 0; i < N; ++i) qfrc[i] = 0.0;
-  float ob[O];
-  cartchain_write_obs<NP>(q, v, qfrc, ob);
-  for (int i = 0; i < O; ++i) {
-    if (obs) obs[(size_t)t * O + i] = ob[i];
-    if (obs_cur) obs_cur[(size_t)env * O + i] = ob[i];
-  }
-  ep_len[env] = 0; ep_ret[env] = 0.0;
-  const size_t ne = (size_t)n_env;
-#pragma unroll
-  for (int i = 0; i < N; ++i) { qpos[i * ne + env] = q[i]; qvel[i * ne + env] = v[i]; }
-}
+__global__ __launch_bounds__(256) void k_cartchain_step(const EnvStepArgs A, const CartChainDev m) { lane_step_frame<CartChainTask<NP>>(A, m); }
+template <int NP>
+__global__ __launch_bounds__(256) void k_cartchain_reset(const LaneResetArgs R) { lane_reset_frame<CartChainTask<NP>>(R, CartChainDev{}); }

@@ -10,6 +10,7 @@
 // The model and its solver are stated in oracle/planar_env.py (the CPU oracle); physics parity with
 // MuJoCo is UNPINNED (no MuJoCo here) — see DESIGN.md.
 // Not a roofline kernel: ~160 B of HBM traffic and O(1e4) fp64 FLOP per env-step on a serial chain.
+#include <algorithm>
 #include <cmath>
 
 #include "host_common.h"
@@ -33,8 +34,13 @@ struct PlanarModelDev {
   double obs_shift[2 * (ENV_MAXB + 2)], obs_inv_scale[2 * (ENV_MAXB + 2)];
 };
 
+struct EnvStepArgs;
 struct ilsx_vecenv {
   ilsx_ctx* ctx = nullptr;
+  std::vector<void*> owned;   // every device allocation of this handle (env_alloc): ilsx_vecenv_destroy frees exactly these
+  // the step and reset kernels of this handle, chosen once at creation (env_select_planar / _spatial / _classic)
+  int (*step_fn)(ilsx_vecenv*, ProfScope&, const EnvStepArgs&) = nullptr;
+  int (*reset_fn)(ilsx_vecenv*, const int* ids_dev, int n_ids, float* obs, unsigned long long step) = nullptr;
   PlanarModelDev hm;
   PlanarModelDev* dm = nullptr;
   int n_env = 0, n = 0, o = 0, a = 0;
@@ -76,6 +82,18 @@ struct ilsx_vecenv {
   unsigned long long explore_calls = 0;   // Philox counter of k_explore (one draw per call)
   const float* policy_obs() const { return norm_obs ? obs_n : obs_cur; }
 };
+
+// Device memory of a vec-env, at creation or later: recorded in the handle, so that destroying the handle gives all of it back
+template <class T>
+static int env_alloc(ilsx_vecenv* e, size_t bytes, T** out) {
+  ILSX_TRY(ctx_alloc(e->ctx, bytes, (void**)out));
+  e->owned.push_back(*out);
+  return ILSX_OK;
+}
+static int env_free(ilsx_vecenv* e, void* p) {
+  e->owned.erase(std::remove(e->owned.begin(), e->owned.end(), p), e->owned.end());
+  return ctx_free(e->ctx, p);
+}
 
 // RunningMeanStd (normalizer.py:128-152): float64, one owner workgroup per observation dimension (count is kept per
 // dimension so that no workgroup depends on another's update).
@@ -717,8 +735,10 @@ __device__ __forceinline__ void e3w_reset_state(e3w_lds* S, const Spatial3Dev& m
 #undef E3K_TRUNC
 
 // ------------------------------------------------------------------------------------------------ host
+// One launcher per kernel; a handle's two (step_fn, reset_fn) are chosen once, when it is created, by its engine's env_select_* below.
+// launch_env_step / launch_env_reset own what is common: the empty call, the ProfScope, the step counter, the launch error.
 template <int NB, int MR, int BLOCK>
-static int launch_env_step_t(ilsx_vecenv* e, const EnvStepArgs& A) {
+static int step_planar_lane(ilsx_vecenv* e, ProfScope& ps, const EnvStepArgs& A) {
   using S = EnvScratch<NB, MR, BLOCK>;
   const size_t lds = (size_t)S::TOTAL * BLOCK * sizeof(double) + ((sizeof(PlanarModelDev) + 7) / 8) * sizeof(double);   // per-env scratch + the model record
   static bool attr_done = false;
@@ -726,130 +746,114 @@ static int launch_env_step_t(ilsx_vecenv* e, const EnvStepArgs& A) {
     HIPCHK(hipFuncSetAttribute((const void*)k_env_step<NB, MR, BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_done = true;
   }
-  ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
   ILSX_LAUNCH(ps, (k_env_step<NB, MR, BLOCK>), dim3((A.n_ids + BLOCK - 1) / BLOCK), dim3(BLOCK), lds, e->ctx->stream, A);
-  HIPCHK(hipGetLastError());
   return ILSX_OK;
 }
 // 16 lanes per env (env2d_group.h): one wavefront = one workgroup = 4 envs
 template <int NB, int MR>
-static int launch_envg_step_t(ilsx_vecenv* e, const EnvStepArgs& A) {
+static int step_planar_group(ilsx_vecenv* e, ProfScope& ps, const EnvStepArgs& A) {
   const size_t lds = (((sizeof(PlanarModelDev) + 7) / 8) + (size_t)EG_ENVS * EgOff<NB, MR>::TOTAL) * sizeof(double);
-  ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
   ILSX_LAUNCH(ps, (k_envg_step<NB, MR>), dim3((A.n_ids + EG_ENVS - 1) / EG_ENVS), dim3(64), lds, e->ctx->stream, A);
+  return ILSX_OK;
+}
+#define ENV_STEP_FN(fn, kernel, grid, block, lds, ...)                                  \
+  static int fn(ilsx_vecenv* e, ProfScope& ps, const EnvStepArgs& A) {                  \
+    ILSX_LAUNCH(ps, kernel, grid, dim3(block), lds, e->ctx->stream, A, ##__VA_ARGS__);  \
+    return ILSX_OK;                                                                     \
+  }
+#define ENV_RESET_FN(fn, kernel, grid, block, lds, ...)                                                      \
+  static int fn(ilsx_vecenv* e, const int* ids_dev, int n_ids, float* obs, unsigned long long step) {        \
+    hipLaunchKernelGGL(kernel, grid, dim3(block), lds, e->ctx->stream, __VA_ARGS__);                         \
+    return ILSX_OK;                                                                                          \
+  }
+#define ENV_RESET_TAIL obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step
+#define LANES(n, per) dim3(((n) + (per) - 1) / (per))
+// ---- planar engine
+ENV_RESET_FN(reset_planar4, k_env_reset<4>, LANES(n_ids, 256), 256, 0, e->dm, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL)
+ENV_RESET_FN(reset_planar7, k_env_reset<7>, LANES(n_ids, 256), 256, 0, e->dm, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL)
+static int env_select_planar(ilsx_vecenv* e) {
+  static const bool lane_form = getenv("ILSX_ENV2D_LANE") != nullptr;   // A/B: the first form, one lane per env
+  const int nb = e->hm.nb;
+  const bool wide = e->hm.max_rows > 12;
+  if (nb == 4) {
+    e->step_fn = lane_form ? step_planar_lane<4, 8, 64> : step_planar_group<4, 8>;
+    e->reset_fn = reset_planar4;
+  } else if (nb == 7) {
+    if (lane_form) e->step_fn = wide ? step_planar_lane<7, 16, 32> : step_planar_lane<7, 12, 64>;
+    else e->step_fn = wide ? step_planar_group<7, 16> : step_planar_group<7, 12>;
+    e->reset_fn = reset_planar7;
+  } else {
+    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "vec-env kernels are instantiated for 4 (Hopper) and 7 (Walker2d) bodies, got %d", nb);
+  }
+  return ILSX_OK;
+}
+// ---- 3-D engine: wave per env (env3d_wave.h), or the lane-per-env form (ILSX_ENV3D_LANE); *_trunc: the observation ends after qvel
+#define E3W_LDS ((size_t)E3WOff::TOTAL * 8)
+#define E3_DM (const Spatial3Dev*)e->dm3
+ENV_STEP_FN(step_3dw_23, k_env3dw_step<23>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)   // Humanoid
+ENV_STEP_FN(step_3dw_14, k_env3dw_step<14>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)   // Ant
+ENV_STEP_FN(step_3dw_any, k_env3dw_step<0>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)   // any other tree: run-time dof count
+ENV_STEP_FN(step_3d_lane, k_env3d_step, LANES(A.n_ids, 64), 64, 0, E3_DM, e->scr3)
+ENV_STEP_FN(step_3dw_23_trunc, k_env3dw_step_trunc<23>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)
+ENV_STEP_FN(step_3dw_14_trunc, k_env3dw_step_trunc<14>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)
+ENV_STEP_FN(step_3d_lane_trunc, k_env3d_step_trunc, LANES(A.n_ids, 64), 64, 0, E3_DM, e->scr3)
+ENV_RESET_FN(reset_3dw, k_env3dw_reset, dim3(n_ids), 64, E3W_LDS, E3_DM, e->qpos, e->qvel, e->n_env, ids_dev, ENV_RESET_TAIL)
+ENV_RESET_FN(reset_3dw_trunc, k_env3dw_reset_trunc, dim3(n_ids), 64, E3W_LDS, E3_DM, e->qpos, e->qvel, e->n_env, ids_dev, ENV_RESET_TAIL)
+ENV_RESET_FN(reset_3d_lane, k_env3d_reset, LANES(n_ids, 64), 64, 0, E3_DM, e->scr3, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL)
+ENV_RESET_FN(reset_3d_lane_trunc, k_env3d_reset_trunc, LANES(n_ids, 64), 64, 0, E3_DM, e->scr3, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL)
+static void env_select_spatial(ilsx_vecenv* e) {   // obs_trunc comes with 14 or 23 dofs only (ilsx_vecenv_create_spatial)
+  const bool trunc = e->hm3->obs_trunc != 0;
+  if (!e->wave3) {
+    e->step_fn = trunc ? step_3d_lane_trunc : step_3d_lane;
+    e->reset_fn = trunc ? reset_3d_lane_trunc : reset_3d_lane;
+    return;
+  }
+  if (e->nv == 23) e->step_fn = trunc ? step_3dw_23_trunc : step_3dw_23;
+  else if (e->nv == 14) e->step_fn = trunc ? step_3dw_14_trunc : step_3dw_14;
+  else e->step_fn = step_3dw_any;
+  e->reset_fn = trunc ? reset_3dw_trunc : reset_3dw;
+}
+// ---- classic control and Swimmer: the lane-per-env frame (classic_env.h), one row per task
+#define LANE_RESET_ARGS LaneResetArgs{e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL}
+ENV_STEP_FN(step_cartpole, k_cartpole_step, LANES(A.n_ids, 256), 256, 0)
+ENV_STEP_FN(step_pendulum, k_pendulum_step, LANES(A.n_ids, 256), 256, 0)
+ENV_STEP_FN(step_cartchain1, k_cartchain_step<1>, LANES(A.n_ids, 256), 256, 0, *e->cc)
+ENV_STEP_FN(step_cartchain2, k_cartchain_step<2>, LANES(A.n_ids, 256), 256, 0, *e->cc)
+ENV_STEP_FN(step_swimmer, k_swimmer_step<3>, LANES(A.n_ids, 256), 256, 0, *e->sw)
+ENV_RESET_FN(reset_cartpole, k_cartpole_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
+ENV_RESET_FN(reset_pendulum, k_pendulum_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
+ENV_RESET_FN(reset_cartchain1, k_cartchain_reset<1>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
+ENV_RESET_FN(reset_cartchain2, k_cartchain_reset<2>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
+ENV_RESET_FN(reset_swimmer, k_swimmer_reset<3>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS, *e->sw)
+static const struct ClassicTask {
+  int kind, n, o, a, discrete_n;   // n = nq = nv; discrete_n: the size of a Discrete action space, 0 = Box(-1, 1) actions
+  decltype(ilsx_vecenv::step_fn) step;
+  decltype(ilsx_vecenv::reset_fn) reset;
+} CLASSIC_TASKS[] = {
+    {ILSX_CLASSIC_CARTPOLE, 2, 4, 1, 2, step_cartpole, reset_cartpole},
+    {ILSX_CLASSIC_PENDULUM, 1, 3, 1, 0, step_pendulum, reset_pendulum},
+    {ILSX_CLASSIC_INVERTED_PENDULUM, 2, 4, 1, 0, step_cartchain1, reset_cartchain1},
+    {ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM, 3, 11, 1, 0, step_cartchain2, reset_cartchain2},
+    {ILSX_SWIMMER_TASK, 5, 8, 2, 0, step_swimmer, reset_swimmer},
+};
+#undef ENV_STEP_FN
+#undef ENV_RESET_FN
+#undef ENV_RESET_TAIL
+#undef LANE_RESET_ARGS
+#undef LANES
+#undef E3W_LDS
+#undef E3_DM
+
+static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
+  if (A.n_ids <= 0) return ILSX_OK;
+  ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
+  ILSX_TRY(e->step_fn(e, ps, A));
   HIPCHK(hipGetLastError());
   return ILSX_OK;
 }
-static int launch_env_step(ilsx_vecenv* e, const EnvStepArgs& A) {
-  if (A.n_ids <= 0) return ILSX_OK;
-  if (e->engine == 2) {
-    ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
-    if (e->classic == ILSX_CLASSIC_PENDULUM)
-      ILSX_LAUNCH(ps, k_pendulum_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
-    else if (e->classic == ILSX_CLASSIC_INVERTED_PENDULUM)
-      ILSX_LAUNCH(ps, k_cartchain_step<1>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->cc);
-    else if (e->classic == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM)
-      ILSX_LAUNCH(ps, k_cartchain_step<2>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->cc);
-    else if (e->classic == ILSX_SWIMMER_TASK)
-      ILSX_LAUNCH(ps, k_swimmer_step<3>, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A, *e->sw);
-    else
-      ILSX_LAUNCH(ps, k_cartpole_step, dim3((A.n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, A);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  if (e->engine == 1 && e->hm3->obs_trunc) {   // the *_trunc_obs tasks: the same steppers with the observation ending after qvel
-    ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
-    if (e->wave3 && e->nv == 23)
-      ILSX_LAUNCH(ps, k_env3dw_step_trunc<23>, dim3(A.n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, A, (const Spatial3Dev*)e->dm3);
-    else if (e->wave3 && e->nv == 14)
-      ILSX_LAUNCH(ps, k_env3dw_step_trunc<14>, dim3(A.n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, A, (const Spatial3Dev*)e->dm3);
-    else   // the lane-per-env form (ILSX_ENV3D_LANE)
-      ILSX_LAUNCH(ps, k_env3d_step_trunc, dim3((A.n_ids + 63) / 64), dim3(64), 0, e->ctx->stream, A, (const Spatial3Dev*)e->dm3, e->scr3);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  if (e->engine == 1) {
-    ProfScope ps(e->ctx, ILSX_K_ENV_STEP);
-    if (e->wave3 && e->nv == 23)        // Humanoid
-      ILSX_LAUNCH(ps, k_env3dw_step<23>, dim3(A.n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, A, (const Spatial3Dev*)e->dm3);
-    else if (e->wave3 && e->nv == 14)   // Ant
-      ILSX_LAUNCH(ps, k_env3dw_step<14>, dim3(A.n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, A, (const Spatial3Dev*)e->dm3);
-    else if (e->wave3)                  // any other tree: run-time dof count
-      ILSX_LAUNCH(ps, k_env3dw_step<0>, dim3(A.n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, A, (const Spatial3Dev*)e->dm3);
-    else
-      ILSX_LAUNCH(ps, k_env3d_step, dim3((A.n_ids + 63) / 64), dim3(64), 0, e->ctx->stream, A, (const Spatial3Dev*)e->dm3, e->scr3);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  static const bool lane_form = getenv("ILSX_ENV2D_LANE") != nullptr;   // A/B: the first form, one lane per env
-  if (!lane_form) {
-    if (e->hm.nb == 4) return launch_envg_step_t<4, 8>(e, A);
-    if (e->hm.nb == 7) return e->hm.max_rows > 12 ? launch_envg_step_t<7, 16>(e, A) : launch_envg_step_t<7, 12>(e, A);
-  }
-  if (e->hm.nb == 4) return launch_env_step_t<4, 8, 64>(e, A);
-  if (e->hm.nb == 7) return e->hm.max_rows > 12 ? launch_env_step_t<7, 16, 32>(e, A) : launch_env_step_t<7, 12, 64>(e, A);
-  ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "vec-env kernels are instantiated for 4 (Hopper) and 7 (Walker2d) bodies, got %d", e->hm.nb);
-}
 static int launch_env_reset(ilsx_vecenv* e, const int* ids_dev, int n_ids, float* obs) {
   if (n_ids <= 0) return ILSX_OK;
-  const unsigned long long step = ++e->step_ctr;
-  if (e->engine == 2 && e->classic == ILSX_CLASSIC_PENDULUM) {
-    hipLaunchKernelGGL(k_pendulum_reset, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, ids_dev, n_ids, obs,
-                       e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  if (e->engine == 2 && (e->classic == ILSX_CLASSIC_INVERTED_PENDULUM || e->classic == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM)) {
-    if (e->classic == ILSX_CLASSIC_INVERTED_PENDULUM)
-      hipLaunchKernelGGL(k_cartchain_reset<1>, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids,
-                         obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-    else
-      hipLaunchKernelGGL(k_cartchain_reset<2>, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids,
-                         obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  if (e->engine == 2 && e->classic == ILSX_SWIMMER_TASK) {
-    hipLaunchKernelGGL(k_swimmer_reset<3>, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, obs,
-                       e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step, *e->sw);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  if (e->engine == 2) {
-    hipLaunchKernelGGL(k_cartpole_reset, dim3((n_ids + 255) / 256), dim3(256), 0, e->ctx->stream, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, obs,
-                       e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  if (e->engine == 1 && e->hm3->obs_trunc) {
-    if (e->wave3)
-      hipLaunchKernelGGL(k_env3dw_reset_trunc, dim3(n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, (const Spatial3Dev*)e->dm3, e->qpos,
-                         e->qvel, e->n_env, ids_dev, obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-    else
-      hipLaunchKernelGGL(k_env3d_reset_trunc, dim3((n_ids + 63) / 64), dim3(64), 0, e->ctx->stream, (const Spatial3Dev*)e->dm3, e->scr3, e->qpos,
-                         e->qvel, e->n_env, ids_dev, n_ids, obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  if (e->engine == 1 && e->wave3) {
-    hipLaunchKernelGGL(k_env3dw_reset, dim3(n_ids), dim3(64), (size_t)E3WOff::TOTAL * 8, e->ctx->stream, (const Spatial3Dev*)e->dm3, e->qpos, e->qvel,
-                       e->n_env, ids_dev, obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  if (e->engine == 1) {
-    hipLaunchKernelGGL(k_env3d_reset, dim3((n_ids + 63) / 64), dim3(64), 0, e->ctx->stream, (const Spatial3Dev*)e->dm3, e->scr3, e->qpos, e->qvel,
-                       e->n_env, ids_dev, n_ids, obs, e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
-  const dim3 grid((n_ids + 255) / 256), block(256);
-  if (e->hm.nb == 4)
-    hipLaunchKernelGGL(k_env_reset<4>, grid, block, 0, e->ctx->stream, e->dm, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, obs,
-                       e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
-  else
-    hipLaunchKernelGGL(k_env_reset<7>, grid, block, 0, e->ctx->stream, e->dm, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, obs,
-                       e->obs_cur, e->ep_len, e->ep_ret, e->seed, e->rng_stream, step);
+  ILSX_TRY(e->reset_fn(e, ids_dev, n_ids, obs, ++e->step_ctr));
   HIPCHK(hipGetLastError());
   return ILSX_OK;
 }
@@ -867,19 +871,57 @@ static int env_obs_norm(ilsx_vecenv* e, const float* upd_src, int upd_rows, cons
   return ILSX_OK;
 }
 
+// A handle under construction: every early return of a creator gives back the handle, its host-side models and its device buffers
+struct EnvGuard {
+  ilsx_vecenv* e;
+  ~EnvGuard() { if (e) ilsx_vecenv_destroy(e); }
+};
+static ilsx_vecenv* env_new(ilsx_ctx* ctx, int engine, int n_env, uint64_t seed) {
+  ilsx_vecenv* e = new ilsx_vecenv();
+  e->ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++; e->engine = engine;
+  return e;
+}
+// What every creator does once nq / nv / o / a and the kernels of the handle are known: the buffers all engines share, RunningMeanStd() and
+// the first reset.  On success the handle is the caller's.
+static int env_create_finish(EnvGuard& guard, ilsx_vecenv** out) {
+  ilsx_vecenv* e = guard.e;
+  const size_t N = (size_t)e->n_env;
+  ILSX_TRY(env_alloc(e, N * e->nq * 8, &e->qpos));
+  ILSX_TRY(env_alloc(e, N * e->nv * 8, &e->qvel));
+  ILSX_TRY(env_alloc(e, N * e->o * 4, &e->obs_cur));
+  ILSX_TRY(env_alloc(e, N * e->a * 4, &e->act));
+  ILSX_TRY(env_alloc(e, N * e->o * 4, &e->nobs));
+  ILSX_TRY(env_alloc(e, N * 4, &e->rew));
+  ILSX_TRY(env_alloc(e, N, &e->done));
+  ILSX_TRY(env_alloc(e, N * 4, &e->ep_len));
+  ILSX_TRY(env_alloc(e, N * e->o * 4, &e->obs_n));
+  ILSX_TRY(env_alloc(e, sizeof(ObsRms), &e->rms));
+  ILSX_TRY(env_alloc(e, N * 8, &e->ep_ret));
+  ILSX_TRY(env_alloc(e, 4 * 8, &e->stats));
+  ILSX_TRY(env_alloc(e, N * 4, &e->ids));
+  ObsRms h;   // RunningMeanStd(): mean 0, var 1, count 0 (normalizer.py:133-136)
+  for (int i = 0; i < ENV_MAX_OBS; ++i) { h.mean[i] = 0.0; h.var[i] = 1.0; h.count[i] = 0.0; }
+  HIPCHK(hipMemcpyAsync(e->rms, &h, sizeof h, hipMemcpyHostToDevice, e->ctx->stream));
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));   // h, and a model record a creator is uploading, are read by now
+  ILSX_TRY(launch_env_reset(e, nullptr, e->n_env, nullptr));
+  guard.e = nullptr;
+  *out = e;
+  return ILSX_OK;
+}
+
 extern "C" int ilsx_vecenv_create(ilsx_ctx* ctx, const ilsx_planar_model* pm, int n_env, uint64_t seed, ilsx_vecenv** out) {
   if (!ctx || !pm || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create: bad argument");
   if (pm->n_body != 4 && pm->n_body != 7)
     ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "n_body=%d: kernels exist for 4 (Hopper) and 7 (Walker2d) bodies", pm->n_body);
   if (pm->n_geom < 1 || pm->n_geom > ENV_MAXG) ILSX_FAIL(ILSX_ERR_ARG, "n_geom=%d out of range", pm->n_geom);
   HIPCHK(hipSetDevice(ctx->device));
-  ilsx_vecenv* e = new ilsx_vecenv();
-  e->ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++;
+  ilsx_vecenv* e = env_new(ctx, 0, n_env, seed);
+  EnvGuard guard{e};
   PlanarModelDev& m = e->hm;
   memset(&m, 0, sizeof m);
   m.nb = pm->n_body; m.ng = pm->n_geom; m.task = pm->task; m.frame_skip = pm->frame_skip; m.pgs_iters = pm->pgs_iters;
   m.max_rows = pm->max_rows > 0 ? pm->max_rows : (pm->n_body == 4 ? 8 : 12);
-  if (m.max_rows > 16) { delete e; ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "max_rows=%d: the kernels keep at most 16 constraint rows per env", m.max_rows); }
+  if (m.max_rows > 16) { ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "max_rows=%d: the kernels keep at most 16 constraint rows per env", m.max_rows); }
   int na = 0;
   for (int b = 0; b < m.nb; ++b) {
     m.parent[b] = pm->parent[b]; m.limited[b] = pm->limited[b];
@@ -892,7 +934,7 @@ extern "C" int ilsx_vecenv_create(ilsx_ctx* ctx, const ilsx_planar_model* pm, in
     int mask = 0;
     for (int j = b; j >= 0; j = pm->parent[j]) mask |= 1 << j;
     m.ancmask[b] = mask;
-    if (b > 0 && (pm->parent[b] < 0 || pm->parent[b] >= b)) { delete e; ILSX_FAIL(ILSX_ERR_ARG, "parent[%d] must precede the body", b); }
+    if (b > 0 && (pm->parent[b] < 0 || pm->parent[b] >= b)) ILSX_FAIL(ILSX_ERR_ARG, "parent[%d] must precede the body", b);
   }
   m.n_act = na;
   for (int g = 0; g < m.ng; ++g) {
@@ -911,40 +953,18 @@ extern "C" int ilsx_vecenv_create(ilsx_ctx* ctx, const ilsx_planar_model* pm, in
   m.obs_dim = e->o;
   for (int i = 0; i < e->n; ++i) m.init_qpos[i] = pm->init_qpos[i];
   for (int i = 0; i < 2 * (ENV_MAXB + 2); ++i) { m.obs_shift[i] = 0.0; m.obs_inv_scale[i] = 1.0; }
-  const size_t N = (size_t)n_env;
-  int rc = ctx_alloc(ctx, sizeof m, (void**)&e->dm);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->n * 8, (void**)&e->qpos);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->n * 8, (void**)&e->qvel);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->obs_cur);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->a * 4, (void**)&e->act);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->nobs);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->rew);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N, (void**)&e->done);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ep_len);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->obs_n);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, sizeof(ObsRms), (void**)&e->rms);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 8, (void**)&e->ep_ret);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, 4 * 8, (void**)&e->stats);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ids);
-  if (rc != ILSX_OK) { delete e; return rc; }
+  ILSX_TRY(env_select_planar(e));
+  ILSX_TRY(env_alloc(e, sizeof m, &e->dm));
   HIPCHK(hipMemcpyAsync(e->dm, &m, sizeof m, hipMemcpyHostToDevice, ctx->stream));
-  {
-    ObsRms h;   // RunningMeanStd(): mean 0, var 1, count 0 (normalizer.py:133-136)
-    for (int i = 0; i < ENV_MAX_OBS; ++i) { h.mean[i] = 0.0; h.var[i] = 1.0; h.count[i] = 0.0; }
-    HIPCHK(hipMemcpyAsync(e->rms, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
-  }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ILSX_TRY(launch_env_reset(e, nullptr, n_env, nullptr));
-  *out = e;
-  return ILSX_OK;
+  return env_create_finish(guard, out);
 }
 
 // 3-D models (Ant / Humanoid): same handle type, same protocol entry points; the engine behind step / reset is env3d.h
 extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_model* sm, int n_env, uint64_t seed, ilsx_vecenv** out) {
   if (!ctx || !sm || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_spatial: bad argument");
   HIPCHK(hipSetDevice(ctx->device));
-  ilsx_vecenv* e = new ilsx_vecenv();
-  e->ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++; e->engine = 1;
+  ilsx_vecenv* e = env_new(ctx, 1, n_env, seed);
+  EnvGuard guard{e};
   e->wave3 = !(getenv("ILSX_ENV3D_LANE") && atoi(getenv("ILSX_ENV3D_LANE")) != 0);
   if (e->wave3) {
     HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<23>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
@@ -957,85 +977,33 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
   }
   e->hm3 = new Spatial3Dev();
   Spatial3Dev& m = *e->hm3;
-  if (const char* why = e3_build_model(sm, m)) { delete e->hm3; delete e; ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_spatial: %s", why); }
-  if (m.obs_trunc && m.nv != 23 && m.nv != 14) {   // the truncated wave kernel is built for the Humanoid's and the Ant's dof counts only
-    const int nv = m.nv;
-    delete e->hm3; delete e;
-    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_spatial: obs_trunc is available for the Ant (14 dofs) and the Humanoid (23), not for %d dofs", nv);
-  }
+  if (const char* why = e3_build_model(sm, m)) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_spatial: %s", why);
+  if (m.obs_trunc && m.nv != 23 && m.nv != 14)   // the truncated wave kernel is built for the Humanoid's and the Ant's dof counts only
+    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_spatial: obs_trunc is available for the Ant (14 dofs) and the Humanoid (23), not for %d dofs", m.nv);
   e->n = m.nq; e->nq = m.nq; e->nv = m.nv; e->o = m.obs_dim; e->a = m.n_act;
-  const size_t N = (size_t)n_env;
-  int rc = ctx_alloc(ctx, sizeof m, (void**)&e->dm3);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, (size_t)E3Off::TOTAL * N * 8, (void**)&e->scr3);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->nq * 8, (void**)&e->qpos);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->nv * 8, (void**)&e->qvel);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->obs_cur);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->a * 4, (void**)&e->act);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->nobs);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->rew);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N, (void**)&e->done);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ep_len);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->obs_n);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, sizeof(ObsRms), (void**)&e->rms);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 8, (void**)&e->ep_ret);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, 4 * 8, (void**)&e->stats);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ids);
-  if (rc != ILSX_OK) { delete e->hm3; delete e; return rc; }
+  env_select_spatial(e);
+  ILSX_TRY(env_alloc(e, sizeof m, &e->dm3));
+  ILSX_TRY(env_alloc(e, (size_t)E3Off::TOTAL * n_env * 8, &e->scr3));
   HIPCHK(hipMemcpyAsync(e->dm3, &m, sizeof m, hipMemcpyHostToDevice, ctx->stream));
-  {
-    std::vector<ObsRms> h(1);
-    for (int i = 0; i < ENV_MAX_OBS; ++i) { h[0].mean[i] = 0.0; h[0].var[i] = 1.0; h[0].count[i] = 0.0; }
-    HIPCHK(hipMemcpyAsync(e->rms, h.data(), sizeof(ObsRms), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  ILSX_TRY(launch_env_reset(e, nullptr, n_env, nullptr));
-  *out = e;
-  return ILSX_OK;
+  return env_create_finish(guard, out);
 }
 // Classic control (classic_env.h): CartPole, Pendulum and the cart-and-poles tasks, one lane per env, the same handle and protocol entry
 // points as the other engines.  cc != null: InvertedPendulum / InvertedDoublePendulum with these constants; sw != null: Swimmer with these.
 static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n_env, uint64_t seed, ilsx_vecenv** out,
                           const SwimmerDev* sw = nullptr) {
   HIPCHK(hipSetDevice(ctx->device));
-  ilsx_vecenv* e = new ilsx_vecenv();
-  struct Guard {   // every early return below gives back what was allocated so far (the handle, its buffers, the constants)
-    ilsx_vecenv* e;
-    ~Guard() { if (e) ilsx_vecenv_destroy(e); }
-  } guard{e};
-  e->ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++; e->engine = 2;
-  e->classic = kind;
-  if (kind == ILSX_CLASSIC_PENDULUM) { e->discrete_n = 0; e->n = 1; e->nq = 1; e->nv = 1; e->o = 3; e->a = 1; }   // Box(-1, 1) actions
-  else if (kind == ILSX_CLASSIC_INVERTED_PENDULUM) { e->discrete_n = 0; e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1; }
-  else if (kind == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM) { e->discrete_n = 0; e->n = 3; e->nq = 3; e->nv = 3; e->o = 11; e->a = 1; }
-  else if (kind == ILSX_SWIMMER_TASK) { e->discrete_n = 0; e->n = 5; e->nq = 5; e->nv = 5; e->o = 8; e->a = 2; }
-  else { e->discrete_n = 2; e->n = 2; e->nq = 2; e->nv = 2; e->o = 4; e->a = 1; }
+  ilsx_vecenv* e = env_new(ctx, 2, n_env, seed);
+  EnvGuard guard{e};
+  const ClassicTask* task = nullptr;
+  for (const ClassicTask& t : CLASSIC_TASKS)
+    if (t.kind == kind) task = &t;
+  if (!task) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "classic control: unknown kind %d", kind);
+  e->classic = kind; e->discrete_n = task->discrete_n;
+  e->n = e->nq = e->nv = task->n; e->o = task->o; e->a = task->a;
+  e->step_fn = task->step; e->reset_fn = task->reset;
   if (cc) e->cc = new CartChainDev(*cc);
   if (sw) e->sw = new SwimmerDev(*sw);
-  const size_t N = (size_t)n_env;
-  int rc = ctx_alloc(ctx, N * e->nq * 8, (void**)&e->qpos);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->nv * 8, (void**)&e->qvel);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->obs_cur);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->a * 4, (void**)&e->act);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->nobs);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->rew);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N, (void**)&e->done);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ep_len);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * e->o * 4, (void**)&e->obs_n);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, sizeof(ObsRms), (void**)&e->rms);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 8, (void**)&e->ep_ret);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, 4 * 8, (void**)&e->stats);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * 4, (void**)&e->ids);
-  if (rc != ILSX_OK) return rc;
-  {
-    ObsRms h;   // RunningMeanStd(): mean 0, var 1, count 0 (normalizer.py:133-136)
-    for (int i = 0; i < ENV_MAX_OBS; ++i) { h.mean[i] = 0.0; h.var[i] = 1.0; h.count[i] = 0.0; }
-    HIPCHK(hipMemcpyAsync(e->rms, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  ILSX_TRY(launch_env_reset(e, nullptr, n_env, nullptr));
-  guard.e = nullptr;
-  *out = e;
-  return ILSX_OK;
+  return env_create_finish(guard, out);
 }
 
 // MuJoCo's capsule rule as ilswiss_amd/envs/models.py states it (capsule_mass_inertia): m = rho pi r^2 (L + r), inertia about the COM
@@ -1200,11 +1168,9 @@ extern "C" int ilsx_vecenv_state_dims(const ilsx_vecenv* e, int* nq, int* nv) {
 
 extern "C" int ilsx_vecenv_destroy(ilsx_vecenv* e) {
   if (!e) return ILSX_OK;
-  void* ps[] = {e->dm, e->qpos, e->qvel, e->obs_cur, e->act, e->nobs, e->rew, e->done, e->ep_len, e->ep_ret, e->stats, e->ids, e->dm3, e->scr3, e->stage, e->flush_len, e->ou_state, e->ou_sigma};
-  for (void* p : ps) if (p) ctx_free(e->ctx, p);
+  for (void* p : e->owned) ctx_free(e->ctx, p);
   if (e->flush_host) hipHostFree(e->flush_host);
   if (e->grp_flush_host) hipHostFree(e->grp_flush_host);
-  if (e->grp_flush_dev) ctx_free(e->ctx, e->grp_flush_dev);
   delete e->hm3;
   delete e->cc;
   delete e->sw;
@@ -1408,7 +1374,6 @@ static int env_after_step_norm(ilsx_vecenv* e) {
 // The stepper's arguments for one fused rollout step of `e` (auto-reset, record into `rb`'s ring — or, with path mode on, into the per-env
 // episode staging area, allocated on first use).
 static int rollout_env_args(ilsx_vecenv* e, ilsx_replay* rb, int max_path_length, int no_terminal, unsigned long long step, EnvStepArgs* out) {
-  ilsx_ctx* ctx = e->ctx;
   EnvStepArgs& A = *out;
   memset(&A, 0, sizeof A);
   A.m = e->dm; A.qpos = e->qpos; A.qvel = e->qvel; A.n_env = e->n_env;
@@ -1424,8 +1389,8 @@ static int rollout_env_args(ilsx_vecenv* e, ilsx_replay* rb, int max_path_length
                 max_path_length, rb->rec);
     if (!e->stage) {
       if (max_path_length < 1 || max_path_length >= rb->cap) ILSX_FAIL(ILSX_ERR_ARG, "path mode needs 1 <= max_path_length < replay capacity");
-      ILSX_TRY(ctx_alloc(ctx, (size_t)e->n_env * max_path_length * rb->rec * 4, (void**)&e->stage));
-      ILSX_TRY(ctx_alloc(ctx, (size_t)e->n_env * 4, (void**)&e->flush_len));
+      ILSX_TRY(env_alloc(e, (size_t)e->n_env * max_path_length * rb->rec * 4, &e->stage));
+      ILSX_TRY(env_alloc(e, (size_t)e->n_env * 4, &e->flush_len));
       e->stage_len = max_path_length; e->stage_rec = rb->rec;
       HIPCHK(hipHostMalloc((void**)&e->flush_host, (size_t)e->n_env * sizeof(int), hipHostMallocDefault));
     }
@@ -1468,7 +1433,7 @@ extern "C" int ilsx_vecenv_set_exploration(ilsx_vecenv* e, const ilsx_explore_cf
   e->explore = *cfg;
   if (!cfg->kind) return ILSX_OK;
   const size_t n = (size_t)e->n_env * e->a;
-  if (!e->ou_state) { ILSX_TRY(ctx_alloc(e->ctx, n * 8, (void**)&e->ou_state)); ILSX_TRY(ctx_alloc(e->ctx, n * 8, (void**)&e->ou_sigma)); }
+  if (!e->ou_state) { ILSX_TRY(env_alloc(e, n * 8, &e->ou_state)); ILSX_TRY(env_alloc(e, n * 8, &e->ou_sigma)); }
   std::vector<double> h(n, cfg->mu);   // OUStrategy.__init__: state = mu, sigma = max_sigma
   HIPCHK(hipMemcpyAsync(e->ou_state, h.data(), n * 8, hipMemcpyHostToDevice, e->ctx->stream));
   HIPCHK(hipStreamSynchronize(e->ctx->stream));
@@ -1530,7 +1495,7 @@ static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, i
   EnvStepArgs A;
   ILSX_TRY(rollout_env_args(e, rb, max_path_length, no_terminal, step, &A));
   if (label_pi) {   // DAgger._handle_step (dagger.py:45-71): the stored action is the expert's for the observation acted on
-    if (!e->act_label) ILSX_TRY(ctx_alloc(ctx, (size_t)e->n_env * e->a * 4, (void**)&e->act_label));
+    if (!e->act_label) ILSX_TRY(env_alloc(e, (size_t)e->n_env * e->a * 4, &e->act_label));
     ILSX_TRY(ilsx_policy_act(label_pi, e->policy_obs(), e->n_env, label_deterministic, nullptr, e->act_label, nullptr));
     A.rec_act = e->act_label;
   }
@@ -1641,10 +1606,10 @@ static int rollout_lockstep_grouped(ilsx_vecenv* const* envs, ilsx_net* const* p
   for (int k = 0; k < n_runs; ++k) all_paths = all_paths && envs[k]->path_mode;
   const int ne = e0m->n_env;
   if (all_paths && e0m->grp_flush_n < n_runs * ne) {   // the group's flag array (owned by run 0's env, freed with it)
-    if (e0m->grp_flush_dev) ILSX_TRY(ctx_free(gctx, e0m->grp_flush_dev));
+    if (e0m->grp_flush_dev) ILSX_TRY(env_free(e0m, e0m->grp_flush_dev));
     if (e0m->grp_flush_host) HIPCHK(hipHostFree(e0m->grp_flush_host));
     e0m->grp_flush_dev = nullptr; e0m->grp_flush_host = nullptr; e0m->grp_flush_n = 0;
-    ILSX_TRY(ctx_alloc(gctx, (size_t)n_runs * ne * sizeof(int), (void**)&e0m->grp_flush_dev));
+    ILSX_TRY(env_alloc(e0m, (size_t)n_runs * ne * sizeof(int), &e0m->grp_flush_dev));
     HIPCHK(hipHostMalloc((void**)&e0m->grp_flush_host, (size_t)n_runs * ne * sizeof(int), hipHostMallocDefault));
     e0m->grp_flush_n = n_runs * ne;
   }
@@ -1824,6 +1789,15 @@ __global__ void k_eval_accum(const float* __restrict__ rew, const unsigned char*
   }
 }
 
+static int eval_buffers(ilsx_vecenv* e) {   // allocated by the env's first evaluation rollout
+  if (e->ev_frozen) return ILSX_OK;
+  const int n = e->n_env;
+  ILSX_TRY(env_alloc(e, n, &e->ev_frozen)); ILSX_TRY(env_alloc(e, (size_t)n * 8, &e->ev_ret));
+  ILSX_TRY(env_alloc(e, (size_t)n * 4, &e->ev_len)); ILSX_TRY(env_alloc(e, EV_N * 8, &e->ev_stats));
+  ILSX_TRY(env_alloc(e, 4, &e->ev_alive));
+  return ILSX_OK;
+}
+
 extern "C" int ilsx_eval_rollout(ilsx_vecenv* e, ilsx_net* pi, ilsx_ppo* ppo, int max_path_length, int deterministic, int reset_stats,
                                  double* stats_host) {
   if (!e || (!pi && !ppo) || max_path_length < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_eval_rollout: bad argument");
@@ -1833,9 +1807,7 @@ extern "C" int ilsx_eval_rollout(ilsx_vecenv* e, ilsx_net* pi, ilsx_ppo* ppo, in
   HIPCHK(hipSetDevice(ctx->device));
   const int n = e->n_env;
   if (!e->ev_frozen) {
-    ILSX_TRY(ctx_alloc(ctx, n, (void**)&e->ev_frozen)); ILSX_TRY(ctx_alloc(ctx, (size_t)n * 8, (void**)&e->ev_ret));
-    ILSX_TRY(ctx_alloc(ctx, (size_t)n * 4, (void**)&e->ev_len)); ILSX_TRY(ctx_alloc(ctx, EV_N * 8, (void**)&e->ev_stats));
-    ILSX_TRY(ctx_alloc(ctx, 4, (void**)&e->ev_alive));
+    ILSX_TRY(eval_buffers(e));
     reset_stats = 1;
   }
   hipStream_t st = ctx->stream;
@@ -1908,15 +1880,6 @@ __global__ void k_eval_accum_runs(const EvalAccumRuns G) {   // blockIdx.y = run
     atomicSub(R.alive, 1);
   }
 }
-static int eval_buffers(ilsx_vecenv* e) {
-  if (e->ev_frozen) return ILSX_OK;
-  ilsx_ctx* ctx = e->ctx;
-  const int n = e->n_env;
-  ILSX_TRY(ctx_alloc(ctx, n, (void**)&e->ev_frozen)); ILSX_TRY(ctx_alloc(ctx, (size_t)n * 8, (void**)&e->ev_ret));
-  ILSX_TRY(ctx_alloc(ctx, (size_t)n * 4, (void**)&e->ev_len)); ILSX_TRY(ctx_alloc(ctx, EV_N * 8, (void**)&e->ev_stats));
-  ILSX_TRY(ctx_alloc(ctx, 4, (void**)&e->ev_alive));
-  return ILSX_OK;
-}
 // VecPathSampler.obtain_samples (vec_sampler.py:126-146) of K runs at once: every run rolls whole rounds (one episode per env, frozen at its
 // end) until ITS statistics hold >= num_steps steps; the runs of one shape step in lock-step as one launch per stage on run 0's stream — a run
 // leaves a round at the very check (every 32 vec steps) at which its own ilsx_eval_rollout would, so its policy-call counter, env step counter
@@ -1938,11 +1901,11 @@ extern "C" int ilsx_eval_rollouts_lockstep(ilsx_vecenv* const* envs, ilsx_net* c
     if (envs[k]->ctx->stream != gs) HIPCHK(hipStreamSynchronize(envs[k]->ctx->stream));
   }
   if (e0->grp_flush_n < n_runs) {   // the group's small int array (alive counters here, episode-end flags in the training rollouts)
-    if (e0->grp_flush_dev) ILSX_TRY(ctx_free(gctx, e0->grp_flush_dev));
+    if (e0->grp_flush_dev) ILSX_TRY(env_free(e0, e0->grp_flush_dev));
     if (e0->grp_flush_host) HIPCHK(hipHostFree(e0->grp_flush_host));
     e0->grp_flush_dev = nullptr; e0->grp_flush_host = nullptr; e0->grp_flush_n = 0;
     const int cnt = std::max(n_runs, n_runs * ne);
-    ILSX_TRY(ctx_alloc(gctx, (size_t)cnt * sizeof(int), (void**)&e0->grp_flush_dev));
+    ILSX_TRY(env_alloc(e0, (size_t)cnt * sizeof(int), &e0->grp_flush_dev));
     HIPCHK(hipHostMalloc((void**)&e0->grp_flush_host, (size_t)cnt * sizeof(int), hipHostMallocDefault));
     e0->grp_flush_n = cnt;
   }
@@ -2035,5 +1998,11 @@ extern "C" int ilsx_rollout_stats(ilsx_vecenv* e, double* episodes, double* retu
   if (episodes) *episodes = h[0];
   if (return_sum) *return_sum = h[1];
   if (reset) HIPCHK(hipMemsetAsync(e->stats, 0, sizeof h, e->ctx->stream));
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_debug_ctx_allocs(ilsx_ctx* ctx, size_t* count) {
+  if (!ctx || !count) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_debug_ctx_allocs: NULL argument");
+  *count = ctx->allocs.size();
   return ILSX_OK;
 }

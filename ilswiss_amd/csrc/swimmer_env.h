@@ -1,5 +1,5 @@
-// swimmer_env.h — Swimmer stepper of ilsx_vecenv, included by ilsx_env.hip after classic_env.h (it uses EnvStepArgs, env_uniform,
-// impedance_d, cartchain_ctrl and cartchain_chol_solve).
+// swimmer_env.h — Swimmer stepper of ilsx_vecenv: a task of the lane-per-env frame.  It uses, by name, env_uniform and impedance_d
+// (ilsx_env.hip) and lane_step_frame / lane_reset_frame, LaneStateQV, cartchain_ctrl and cartchain_chol_solve (classic_env.h).
 //
 // gym 0.22's SwimmerEnv task rules (rlkit/envs/envs_dict.py `swimmer`) behind the reference's NormalizedBoxEnv, on this repository's own
 // dynamics of a free planar chain in a viscous medium (the constants are ilswiss_amd/envs/models_swimmer.py,
@@ -190,161 +190,61 @@ __device__ __forceinline__ void swimmer_substep(const SwimmerDev& m, double (&q)
   }
 }
 
-// _get_obs(): float32 (qpos[2:] | qvel)
+// The task of the lane-per-env frame (classic_env.h).  The frame turns the arguments its tail needs into per-lane values before the RK4
+// loop: read after the loop they cost this kernel a private segment (a dead scalar spill slot).
 template <int NL>
-__device__ __forceinline__ void swimmer_write_obs(const double (&q)[NL + 2], const double (&v)[NL + 2], float* dst) {
-#pragma unroll
-  for (int i = 0; i < NL; ++i) dst[i] = (float)q[2 + i];
-#pragma unroll
-  for (int i = 0; i < NL + 2; ++i) dst[NL + i] = (float)v[i];
-}
+struct SwimmerTask {
+  static constexpr int N = NL + 2, NQ = N, NV = N, O = 2 * NL + 2, NA = NL - 1;
+  static constexpr bool never_done = true;
+  using Model = SwimmerDev;
+  using State = LaneStateQV<N, N>;
 
-// reset_model(): qpos = init + U(+-0.1) (counters 0 .. N-1 of the env's Philox stream), qvel = U(+-0.1) (counters N .. 2N-1)
-template <int NL>
-__device__ __forceinline__ void swimmer_reset_state(const SwimmerDev& m, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env,
-                                                    double (&q)[NL + 2], double (&v)[NL + 2]) {
-  static_assert(NL == 3, "the draws are written out for five degrees of freedom");
+  // _get_obs(): float32 (qpos[2:] | qvel)
+  static __device__ __forceinline__ void write_obs(const State& s, float* dst) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) dst[i] = (float)s.q[2 + i];
+#pragma unroll
+    for (int i = 0; i < NL + 2; ++i) dst[NL + i] = (float)s.v[i];
+  }
+  static __device__ __forceinline__ void obs_before(const State& s, const float*, float* dst) { write_obs(s, dst); }
+
+  // reset_model(): qpos = init + U(+-0.1) (counters 0 .. N-1 of the env's Philox stream), qvel = U(+-0.1) (counters N .. 2N-1)
+  static __device__ __forceinline__ void reset_state(const Model& m, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, State& s) {
+    static_assert(NL == 3, "the draws are written out for five degrees of freedom");
 #define SWIMMER_DRAW(k) env_uniform(seed, stream, step, env, k)
-  q[0] = m.init_qpos[0] + (-0.1 + 0.2 * SWIMMER_DRAW(0));
-  q[1] = m.init_qpos[1] + (-0.1 + 0.2 * SWIMMER_DRAW(1));
-  q[2] = m.init_qpos[2] + (-0.1 + 0.2 * SWIMMER_DRAW(2));
-  q[3] = m.init_qpos[3] + (-0.1 + 0.2 * SWIMMER_DRAW(3));
-  q[4] = m.init_qpos[4] + (-0.1 + 0.2 * SWIMMER_DRAW(4));
-  v[0] = -0.1 + 0.2 * SWIMMER_DRAW(5);
-  v[1] = -0.1 + 0.2 * SWIMMER_DRAW(6);
-  v[2] = -0.1 + 0.2 * SWIMMER_DRAW(7);
-  v[3] = -0.1 + 0.2 * SWIMMER_DRAW(8);
-  v[4] = -0.1 + 0.2 * SWIMMER_DRAW(9);
+    s.q[0] = m.init_qpos[0] + (-0.1 + 0.2 * SWIMMER_DRAW(0));
+    s.q[1] = m.init_qpos[1] + (-0.1 + 0.2 * SWIMMER_DRAW(1));
+    s.q[2] = m.init_qpos[2] + (-0.1 + 0.2 * SWIMMER_DRAW(2));
+    s.q[3] = m.init_qpos[3] + (-0.1 + 0.2 * SWIMMER_DRAW(3));
+    s.q[4] = m.init_qpos[4] + (-0.1 + 0.2 * SWIMMER_DRAW(4));
+    s.v[0] = -0.1 + 0.2 * SWIMMER_DRAW(5);
+    s.v[1] = -0.1 + 0.2 * SWIMMER_DRAW(6);
+    s.v[2] = -0.1 + 0.2 * SWIMMER_DRAW(7);
+    s.v[3] = -0.1 + 0.2 * SWIMMER_DRAW(8);
+    s.v[4] = -0.1 + 0.2 * SWIMMER_DRAW(9);
 #undef SWIMMER_DRAW
-}
+  }
 
-// Everything the tail needs from the arguments is turned into per-lane values BEFORE the RK4 loop (the addresses it stores to, the reset
-// state it may select): the loop then carries them in vector registers, of which there are plenty, instead of keeping forty-odd scalar
-// registers of arguments alive across the dynamics.  With the arguments read after the loop the scalar allocator spilled an 8-dword
-// tuple it later rematerialised, and the dead spill slot left the kernel a private segment.
-template <int NL>
-__global__ __launch_bounds__(256) void k_swimmer_step(const EnvStepArgs A, const SwimmerDev m) {
-  constexpr int N = NL + 2, O = 2 * NL + 2, NA = NL - 1;
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= A.n_ids) return;
-  const int env = A.ids ? A.ids[t] : t;
-  if (A.frozen && A.frozen[env]) return;
-  const size_t ne = (size_t)A.n_env;
-  double* const qp = A.qpos + env;
-  double* const vp = A.qvel + env;
-  double q[N], v[N];
+  static __device__ __forceinline__ void advance(const Model& m, State& s, const float (&act)[NA], double& reward, bool& done, bool& finite) {
+    double tau[NA], ctrl2 = 0.0;
 #pragma unroll
-  for (int i = 0; i < N; ++i) { q[i] = qp[i * ne]; v[i] = vp[i * ne]; }
-  float* const obs_p = A.obs ? A.obs + (size_t)t * O : nullptr;
-  float* const rew_p = A.rew ? A.rew + t : nullptr;
-  unsigned char* const done_p = A.done ? A.done + t : nullptr;
-  float* const cur_p = A.obs_cur ? A.obs_cur + (size_t)env * O : nullptr;
-  float* rec = nullptr;   // fused replay insert (k_env_step's record layout: obs | act | rew | done | next_obs | absorbing[2])
-  if (A.replay) {
-    long long slot = A.top + env;
-    if (slot >= A.cap) slot -= A.cap;
-    rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
-  }
-  float av[NA], rav[NA];
-  double tau[NA], ctrl2 = 0.0;
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {
-    av[j] = A.act[(size_t)t * NA + j];
-    rav[j] = A.rec_act ? A.rec_act[(size_t)t * NA + j] : av[j];   // the record holds the unmapped action
-    const double c = (double)cartchain_ctrl(av[j], m.ctrl_lo, m.ctrl_hi);
-    tau[j] = m.gear[j] * c;
-    ctrl2 += c * c;
-  }
-  if (rec) {
-    float obs_before[O];
-    swimmer_write_obs<NL>(q, v, obs_before);
-#pragma unroll
-    for (int i = 0; i < O; ++i) rec[i] = obs_before[i];
-#pragma unroll
-    for (int j = 0; j < NA; ++j) rec[O + j] = rav[j];
-  }
-  // auto-reset bookkeeping that does not depend on the step: the episode's length and whether it ends at the path limit, the return so
-  // far, and the state a reset would give (ten Philox blocks: nothing beside the dynamics)
-  int len = 0;
-  bool limit = false;
-  double ret0 = 0.0, rq[N], rv[N];
-  int* const len_p = A.ep_len + env;
-  double* const ret_p = A.ep_ret + env;
-  int* const flush_p = (A.auto_reset && A.flush_len) ? A.flush_len + env : nullptr;
-  double* const stats_p = A.stats;
-  const bool auto_reset = A.auto_reset != 0;
-  if (auto_reset) {
-    len = *len_p + 1;
-    ret0 = *ret_p;
-    limit = len >= A.max_path_length;
-    swimmer_reset_state<NL>(m, A.seed, A.stream, A.step, (uint32_t)env, rq, rv);
-  } else {
-#pragma unroll
-    for (int i = 0; i < N; ++i) { rq[i] = 0.0; rv[i] = 0.0; }
-  }
-  const double x_before = q[0];
-#pragma unroll 1
-  for (int s = 0; s < m.frame_skip; ++s) swimmer_substep<NL>(m, q, v, tau);
-  bool finite = true;
-#pragma unroll
-  for (int i = 0; i < N; ++i) finite = finite && isfinite(q[i]) && isfinite(v[i]);
-  const double reward = (q[0] - x_before) / ((double)m.frame_skip * m.timestep) - 1e-4 * ctrl2;
-  float ob[O];
-  swimmer_write_obs<NL>(q, v, ob);
-  if (obs_p) {
-#pragma unroll
-    for (int i = 0; i < O; ++i) obs_p[i] = ob[i];
-  }
-  if (rew_p) *rew_p = (float)reward;
-  if (done_p) *done_p = 0;   // never done
-  if (rec) {
-    rec[O + NA] = (float)reward;
-    rec[O + NA + 1] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < O; ++i) rec[O + NA + 2 + i] = ob[i];
-    rec[2 * O + NA + 2] = 0.0f; rec[2 * O + NA + 3] = 0.0f;   // absorbing = [0, 0]
-  }
-  if (auto_reset) {
-    const double ret = ret0 + reward;
-    const bool end = limit || !finite;   // never done: the path limit or a non-finite state ends the episode
-    if (end) {
-      atomicAdd(&stats_p[0], 1.0);
-      atomicAdd(&stats_p[1], ret);
+    for (int j = 0; j < NA; ++j) {
+      const double c = (double)cartchain_ctrl(act[j], m.ctrl_lo, m.ctrl_hi);
+      tau[j] = m.gear[j] * c;
+      ctrl2 += c * c;
     }
+    const double x_before = s.q[0];
+#pragma unroll 1
+    for (int k = 0; k < m.frame_skip; ++k) swimmer_substep<NL>(m, s.q, s.v, tau);
+    finite = true;
 #pragma unroll
-    for (int i = 0; i < N; ++i) { q[i] = end ? rq[i] : q[i]; v[i] = end ? rv[i] : v[i]; }
-    swimmer_write_obs<NL>(q, v, ob);
-    *len_p = end ? 0 : len;
-    *ret_p = end ? 0.0 : ret;
-    if (flush_p) *flush_p = end ? len : 0;   // never terminal
+    for (int i = 0; i < N; ++i) finite = finite && isfinite(s.q[i]) && isfinite(s.v[i]);
+    reward = (s.q[0] - x_before) / ((double)m.frame_skip * m.timestep) - 1e-4 * ctrl2;
+    done = false;
   }
-  if (cur_p) {
-#pragma unroll
-    for (int i = 0; i < O; ++i) cur_p[i] = ob[i];
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) { qp[i * ne] = q[i]; vp[i * ne] = v[i]; }
-}
+};
 
 template <int NL>
-__global__ __launch_bounds__(256) void k_swimmer_reset(double* qpos, double* qvel, int n_env, const int* ids, int n_ids, float* obs,
-                                                       float* obs_cur, int* ep_len, double* ep_ret, uint64_t seed, uint32_t stream,
-                                                       unsigned long long step, const SwimmerDev m) {
-  constexpr int N = NL + 2, O = 2 * NL + 2;
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_ids) return;
-  const int env = ids ? ids[t] : t;
-  double q[N], v[N];
-  swimmer_reset_state<NL>(m, seed, stream, step, (uint32_t)env, q, v);
-  float ob[O];
-  swimmer_write_obs<NL>(q, v, ob);
-#pragma unroll
-  for (int i = 0; i < O; ++i) {
-    if (obs) obs[(size_t)t * O + i] = ob[i];
-    if (obs_cur) obs_cur[(size_t)env * O + i] = ob[i];
-  }
-  ep_len[env] = 0; ep_ret[env] = 0.0;
-  const size_t ne = (size_t)n_env;
-#pragma unroll
-  for (int i = 0; i < N; ++i) { qpos[i * ne + env] = q[i]; qvel[i * ne + env] = v[i]; }
-}
+__global__ __launch_bounds__(256) void k_swimmer_step(const EnvStepArgs A, const SwimmerDev m) { lane_step_frame<SwimmerTask<NL>>(A, m); }
+template <int NL>
+__global__ __launch_bounds__(256) void k_swimmer_reset(const LaneResetArgs R, const SwimmerDev m) { lane_reset_frame<SwimmerTask<NL>>(R, m); }

@@ -306,6 +306,8 @@ int ilsx_sac_debug_last_batch(ilsx_sac* sac, int B, float* obs, float* act, floa
  * object was given at creation (ids are handed out per ctx in creation order) and the seed its draws are keyed by. */
 int ilsx_debug_rng_stream(const void* object, int kind, uint32_t* stream, uint64_t* seed);
 int ilsx_debug_philox(ilsx_ctx* ctx, uint64_t seed, uint64_t step, uint32_t stream, int n_rows, int a, uint32_t* raw, float* normals);
+/* Leak check aid (tests only): the number of device allocations the context holds right now. */
+int ilsx_debug_ctx_allocs(ilsx_ctx* ctx, size_t* count);
 
 /* ---------------------------------------------------------------- adversarial-IRL discriminator
  * Replaces rlkit/torch/algorithms/adv_irl/disc_models/simple_disc_models.py:8-48 (MLPDisc, with and without batch norm),
