@@ -85,6 +85,17 @@ class SwimmerModel(C.Structure):  # ilsx_swimmer_model
                 ("limit_solref", C.c_double * 2), ("limit_solimp", C.c_double * 3)]
 
 
+class LunarModel(C.Structure):  # ilsx_lunar_model
+    _fields_ = [("frame_skip", C.c_int32), ("pgs_iters", C.c_int32),
+                ("fps", C.c_double), ("scale", C.c_double), ("w", C.c_double), ("h", C.c_double), ("gravity", C.c_double),
+                ("main_engine_power", C.c_double), ("side_engine_power", C.c_double), ("initial_random", C.c_double),
+                ("side_engine_height", C.c_double), ("side_engine_away", C.c_double), ("leg_down", C.c_double), ("helipad_y", C.c_double),
+                ("mass", C.c_double), ("inertia", C.c_double), ("com", C.c_double * 2), ("foot", (C.c_double * 2) * 2),
+                ("hull", (C.c_double * 2) * 6),
+                ("friction", C.c_double), ("contact_solref", C.c_double * 2), ("contact_solimp", C.c_double * 3),
+                ("sleep_lin_tol", C.c_double), ("sleep_ang_tol", C.c_double), ("sleep_time", C.c_double)]
+
+
 class SpatialModel(C.Structure):  # ilsx_spatial_model
     _fields_ = [("task", C.c_int32), ("n_link", C.c_int32), ("n_act", C.c_int32), ("n_contact", C.c_int32),
                 ("n_body", C.c_int32), ("frame_skip", C.c_int32), ("pgs_iters", C.c_int32), ("max_rows", C.c_int32),
@@ -383,6 +394,7 @@ PROTOTYPES = {
     "ilsx_vecenv_create_classic": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]),
     "ilsx_vecenv_create_cartchain": (C.c_int, [vp, C.POINTER(CartChainModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
     "ilsx_vecenv_create_swimmer": (C.c_int, [vp, C.POINTER(SwimmerModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "ilsx_vecenv_create_lunar": (C.c_int, [vp, C.POINTER(LunarModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
     "ilsx_vecenv_action_space": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "ilsx_dsac_create": (C.c_int, [vp, C.POINTER(DsacCfg), vp, vp, vp, C.POINTER(vp)]),
     "ilsx_dsac_destroy": (C.c_int, [vp]),

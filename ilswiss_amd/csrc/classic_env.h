@@ -25,9 +25,10 @@ enum { CLASSIC_CARTPOLE = 0, CLASSIC_PENDULUM = 1, CLASSIC_INVERTED_PENDULUM = 2
 //   Model              constants passed to the kernel by value (empty for CartPole and Pendulum)
 //   State              q[NQ], v[NV] and whatever else the task carries from the dynamics to the observation
 //   reset_state        the draws of reset_model() from the env's Philox stream
-//   write_obs          _get_obs()
+//   write_obs          _get_obs(): a function of the state (and the model's constants)
 //   obs_before         the observation the record opens with: write_obs, unless the env showed something the state does not hold
 //   advance            one env step: the new state, its reward, done and whether the state is finite
+//   step_draws         optional: advance also takes the step's stream coordinates (LaneCoords below), for tasks that draw on every step
 //   never_done         the task never reports done: done and the terminal bit of flush_len are constants
 // Everything the tail needs from the arguments is turned into per-lane values BEFORE advance (the addresses it stores to, the action the
 // record holds, the episode's length): a long dynamics loop then carries them in vector registers, of which there are plenty, instead of
@@ -41,6 +42,15 @@ struct LaneResetArgs {
   int* ep_len; double* ep_ret;
   uint64_t seed; uint32_t stream; unsigned long long step;
 };
+
+// Where a step stands in the env's Philox stream: what env_uniform takes.  A task that draws random numbers on every step declares
+// `static constexpr bool step_draws = true` and takes a LaneCoords in advance (before reward); its draws must use counters reset_state
+// does not, since an episode that ends is reset at the same coordinates.  Every other task's advance is called as before.
+struct LaneCoords { uint64_t seed; uint32_t stream; unsigned long long step; uint32_t env; };
+template <class T, class = void>
+struct lane_step_draws { static constexpr bool value = false; };
+template <class T>
+struct lane_step_draws<T, decltype((void)T::step_draws)> { static constexpr bool value = T::step_draws; };
 
 template <class T>
 __device__ __forceinline__ void lane_step_frame(const EnvStepArgs& A, const typename T::Model& m) {
@@ -72,7 +82,7 @@ __device__ __forceinline__ void lane_step_frame(const EnvStepArgs& A, const type
   for (int j = 0; j < NA; ++j) av[j] = A.act[(size_t)t * NA + j];
   if (rec) {
     float obs_before[O];
-    T::obs_before(s, cur_p, obs_before);
+    T::obs_before(m, s, cur_p, obs_before);
 #pragma unroll
     for (int i = 0; i < O; ++i) rec[i] = obs_before[i];
 #pragma unroll
@@ -94,10 +104,11 @@ __device__ __forceinline__ void lane_step_frame(const EnvStepArgs& A, const type
   }
   double reward;
   bool done, finite;
-  T::advance(m, s, av, reward, done, finite);
+  if constexpr (lane_step_draws<T>::value) T::advance(m, s, av, LaneCoords{A.seed, A.stream, A.step, (uint32_t)env}, reward, done, finite);
+  else T::advance(m, s, av, reward, done, finite);
   const bool terminal = !T::never_done && done && !no_terminal;
   float ob[O];
-  T::write_obs(s, ob);
+  T::write_obs(m, s, ob);
   if (obs_p) {
 #pragma unroll
     for (int i = 0; i < O; ++i) obs_p[i] = ob[i];
@@ -118,7 +129,7 @@ __device__ __forceinline__ void lane_step_frame(const EnvStepArgs& A, const type
       atomicAdd(&stats_p[0], 1.0);
       atomicAdd(&stats_p[1], ret);
       T::reset_state(m, A.seed, A.stream, A.step, (uint32_t)env, s);   // drawn when an episode ends, not on every step
-      T::write_obs(s, ob);
+      T::write_obs(m, s, ob);
     }
     *len_p = end ? 0 : len;
     *ret_p = end ? 0.0 : ret;
@@ -143,7 +154,7 @@ __device__ __forceinline__ void lane_reset_frame(const LaneResetArgs& R, const t
   typename T::State s{};
   T::reset_state(m, R.seed, R.stream, R.step, (uint32_t)env, s);
   float ob[O];
-  T::write_obs(s, ob);
+  T::write_obs(m, s, ob);
 #pragma unroll
   for (int i = 0; i < O; ++i) {
     if (R.obs) R.obs[(size_t)t * O + i] = ob[i];
@@ -176,10 +187,10 @@ struct CartPoleTask {
   using Model = LaneNoModel;
   using State = LaneStateQV<2, 2>;
 
-  static __device__ __forceinline__ void write_obs(const State& s, float* dst) {
+  static __device__ __forceinline__ void write_obs(const Model&, const State& s, float* dst) {
     dst[0] = (float)s.q[0]; dst[1] = (float)s.v[0]; dst[2] = (float)s.q[1]; dst[3] = (float)s.v[1];
   }
-  static __device__ __forceinline__ void obs_before(const State& s, const float*, float* dst) { write_obs(s, dst); }
+  static __device__ __forceinline__ void obs_before(const Model& m, const State& s, const float*, float* dst) { write_obs(m, s, dst); }
 
   // reset(): np_random.uniform(low=-0.05, high=0.05, size=(4,)) — component k of (x, x_dot, theta, theta_dot) from counter k of the env's
   // Philox stream
@@ -258,10 +269,10 @@ struct PendulumTask {
   using Model = LaneNoModel;
   using State = LaneStateQV<1, 1>;
 
-  static __device__ __forceinline__ void write_obs(const State& s, float* dst) {   // _get_obs(): float32 (cos, sin, theta_dot)
+  static __device__ __forceinline__ void write_obs(const Model&, const State& s, float* dst) {   // _get_obs(): float32 (cos, sin, theta_dot)
     dst[0] = (float)cos(s.q[0]); dst[1] = (float)sin(s.q[0]); dst[2] = (float)s.v[0];
   }
-  static __device__ __forceinline__ void obs_before(const State& s, const float*, float* dst) { write_obs(s, dst); }
+  static __device__ __forceinline__ void obs_before(const Model& m, const State& s, const float*, float* dst) { write_obs(m, s, dst); }
 
   // reset(): np_random.uniform(low=-[pi, 1], high=[pi, 1]) = low + (high - low) * u — component k from counter k of the env's Philox stream
   static __device__ __forceinline__ void reset_state(const Model&, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, State& s) {
@@ -487,7 +498,7 @@ struct CartChainTask {
   struct State { double q[N], v[N], qfrc[N]; };   // qfrc: the constraint force of the step that produced the state (0 after a reset)
 
   // _get_obs(): InvertedPendulum (qpos | qvel); InvertedDoublePendulum (x, sin th, cos th, clip(qvel, +-10), clip(qfrc_constraint, +-10))
-  static __device__ __forceinline__ void write_obs(const State& s, float* dst) {
+  static __device__ __forceinline__ void write_obs(const Model&, const State& s, float* dst) {
     if constexpr (NP == 1) {
       dst[0] = (float)s.q[0]; dst[1] = (float)s.q[1]; dst[2] = (float)s.v[0]; dst[3] = (float)s.v[1];
     } else {
@@ -501,12 +512,12 @@ struct CartChainTask {
   // the constraint force belongs to the step that produced the state, which (q, v) does not hold: the record opens with the columns the
   // env showed for it (0 after a reset).  They are loaded BEFORE write_obs, whose trigonometry then hides the round trip: the record's
   // first stores wait for them ahead of the dynamics.
-  static __device__ __forceinline__ void obs_before(const State& s, const float* obs_cur, float* dst) {
+  static __device__ __forceinline__ void obs_before(const Model& m, const State& s, const float* obs_cur, float* dst) {
     float shown[3] = {0.0f, 0.0f, 0.0f};
     if constexpr (NP == 2)
       if (obs_cur)
         for (int i = 0; i < 3; ++i) shown[i] = obs_cur[8 + i];
-    write_obs(s, dst);
+    write_obs(m, s, dst);
     if constexpr (NP == 2)
       if (obs_cur)
         for (int i = 0; i < 3; ++i) dst[8 + i] = shown[i];

@@ -73,6 +73,8 @@ struct ilsx_vecenv {
   int classic = -1, discrete_n = 0;  // engine 2: ILSX_CLASSIC_* task and the size of its Discrete action space (0 = Box actions)
   struct CartChainDev* cc = nullptr; // engine 2, InvertedPendulum / InvertedDoublePendulum: the constants k_cartchain_step takes by value
   struct SwimmerDev* sw = nullptr;   // engine 2, classic == ILSX_SWIMMER_TASK: the constants k_swimmer_step takes by value (swimmer_env.h)
+  struct LunarDev* ln = nullptr;     // engine 2, classic == ILSX_LUNAR_TASK: the constants k_lunar_step takes by value (lunar_env.h)
+  bool step_draws = false;           // the task draws random numbers on every step: ilsx_vecenv_step gives each step stream coordinates of its own
   bool wave3 = true;   // wave-per-env kernels (env3d_wave.h); ILSX_ENV3D_LANE=1 selects the lane-per-env form (env3d.h) for A/B runs
   Spatial3Dev* hm3 = nullptr; Spatial3Dev* dm3 = nullptr; double* scr3 = nullptr;
   // exploration strategy of a deterministic policy (ilsx_vecenv_set_exploration): one process per env, float64
@@ -508,6 +510,7 @@ __device__ __forceinline__ void env_reset_state(const PlanarModelDev& m, uint64_
 #include "env2d_group.h"
 #include "classic_env.h"
 #include "swimmer_env.h"
+#include "lunar_env.h"
 #ifdef ILSX_EG_PROFILE
 extern "C" int ilsx_debug_eg_prof(unsigned long long* out16, int reset) {   // measurement build only
   if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_eg_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
@@ -813,28 +816,32 @@ static void env_select_spatial(ilsx_vecenv* e) {   // obs_trunc comes with 14 or
   else e->step_fn = step_3dw_any;
   e->reset_fn = trunc ? reset_3dw_trunc : reset_3dw;
 }
-// ---- classic control and Swimmer: the lane-per-env frame (classic_env.h), one row per task
+// ---- classic control, Swimmer and the lander: the lane-per-env frame (classic_env.h), one row per task
 #define LANE_RESET_ARGS LaneResetArgs{e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL}
 ENV_STEP_FN(step_cartpole, k_cartpole_step, LANES(A.n_ids, 256), 256, 0)
 ENV_STEP_FN(step_pendulum, k_pendulum_step, LANES(A.n_ids, 256), 256, 0)
 ENV_STEP_FN(step_cartchain1, k_cartchain_step<1>, LANES(A.n_ids, 256), 256, 0, *e->cc)
 ENV_STEP_FN(step_cartchain2, k_cartchain_step<2>, LANES(A.n_ids, 256), 256, 0, *e->cc)
 ENV_STEP_FN(step_swimmer, k_swimmer_step<3>, LANES(A.n_ids, 256), 256, 0, *e->sw)
+ENV_STEP_FN(step_lunar, k_lunar_step, LANES(A.n_ids, 256), 256, 0, *e->ln)
 ENV_RESET_FN(reset_cartpole, k_cartpole_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_pendulum, k_pendulum_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_cartchain1, k_cartchain_reset<1>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_cartchain2, k_cartchain_reset<2>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_swimmer, k_swimmer_reset<3>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS, *e->sw)
+ENV_RESET_FN(reset_lunar, k_lunar_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS, *e->ln)
 static const struct ClassicTask {
-  int kind, n, o, a, discrete_n;   // n = nq = nv; discrete_n: the size of a Discrete action space, 0 = Box(-1, 1) actions
+  int kind, n, o, a, discrete_n;   // n = degrees of freedom; discrete_n: the size of a Discrete action space, 0 = Box(-1, 1) actions
   decltype(ilsx_vecenv::step_fn) step;
   decltype(ilsx_vecenv::reset_fn) reset;
+  int nq, nv;                      // widths of the state rows where they are not n (0: n)
 } CLASSIC_TASKS[] = {
     {ILSX_CLASSIC_CARTPOLE, 2, 4, 1, 2, step_cartpole, reset_cartpole},
     {ILSX_CLASSIC_PENDULUM, 1, 3, 1, 0, step_pendulum, reset_pendulum},
     {ILSX_CLASSIC_INVERTED_PENDULUM, 2, 4, 1, 0, step_cartchain1, reset_cartchain1},
     {ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM, 3, 11, 1, 0, step_cartchain2, reset_cartchain2},
     {ILSX_SWIMMER_TASK, 5, 8, 2, 0, step_swimmer, reset_swimmer},
+    {ILSX_LUNAR_TASK, 3, 8, 2, 0, step_lunar, reset_lunar, 14, 4},   // qpos carries the terrain, qvel the sleep clock
 };
 #undef ENV_STEP_FN
 #undef ENV_RESET_FN
@@ -988,9 +995,10 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
   return env_create_finish(guard, out);
 }
 // Classic control (classic_env.h): CartPole, Pendulum and the cart-and-poles tasks, one lane per env, the same handle and protocol entry
-// points as the other engines.  cc != null: InvertedPendulum / InvertedDoublePendulum with these constants; sw != null: Swimmer with these.
+// points as the other engines.  cc != null: InvertedPendulum / InvertedDoublePendulum with these constants; sw != null: Swimmer with these;
+// ln != null: the lander with these.
 static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n_env, uint64_t seed, ilsx_vecenv** out,
-                          const SwimmerDev* sw = nullptr) {
+                          const SwimmerDev* sw = nullptr, const LunarDev* ln = nullptr) {
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_vecenv* e = env_new(ctx, 2, n_env, seed);
   EnvGuard guard{e};
@@ -999,10 +1007,11 @@ static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n
     if (t.kind == kind) task = &t;
   if (!task) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "classic control: unknown kind %d", kind);
   e->classic = kind; e->discrete_n = task->discrete_n;
-  e->n = e->nq = e->nv = task->n; e->o = task->o; e->a = task->a;
+  e->n = task->n; e->nq = task->nq ? task->nq : task->n; e->nv = task->nv ? task->nv : task->n; e->o = task->o; e->a = task->a;
   e->step_fn = task->step; e->reset_fn = task->reset;
   if (cc) e->cc = new CartChainDev(*cc);
   if (sw) e->sw = new SwimmerDev(*sw);
+  if (ln) { e->ln = new LunarDev(*ln); e->step_draws = true; }
   return env_create_finish(guard, out);
 }
 
@@ -1138,6 +1147,49 @@ extern "C" int ilsx_vecenv_create_swimmer(ilsx_ctx* ctx, const ilsx_swimmer_mode
   return create_classic(ctx, ILSX_SWIMMER_TASK, nullptr, n_env, seed, out, &d);
 }
 
+// The lander (lunar_env.h): the caller's model is the one source of the constants.  Every field is checked before anything is allocated;
+// create_classic gives back whatever it allocated when it fails.
+extern "C" int ilsx_vecenv_create_lunar(ilsx_ctx* ctx, const ilsx_lunar_model* pm, int n_env, uint64_t seed, ilsx_vecenv** out) {
+  if (!ctx || !pm || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_lunar: bad argument");
+  if (pm->frame_skip < 1 || pm->pgs_iters < 1) ILSX_FAIL(ILSX_ERR_ARG, "lunar: frame_skip and pgs_iters must be positive");
+  const double all[] = {pm->fps, pm->scale, pm->w, pm->h, pm->gravity, pm->main_engine_power, pm->side_engine_power, pm->initial_random,
+                        pm->side_engine_height, pm->side_engine_away, pm->leg_down, pm->helipad_y, pm->mass, pm->inertia, pm->com[0], pm->com[1],
+                        pm->foot[0][0], pm->foot[0][1], pm->foot[1][0], pm->foot[1][1], pm->friction, pm->contact_solref[0], pm->contact_solref[1],
+                        pm->contact_solimp[0], pm->contact_solimp[1], pm->contact_solimp[2], pm->sleep_lin_tol, pm->sleep_ang_tol, pm->sleep_time};
+  for (double x : all)
+    if (!std::isfinite(x)) ILSX_FAIL(ILSX_ERR_ARG, "lunar: every constant must be finite");
+  if (!(pm->mass > 0.0) || !(pm->inertia > 0.0)) ILSX_FAIL(ILSX_ERR_ARG, "lunar: mass and inertia must be positive");
+  if (!(pm->fps > 0.0) || !(pm->scale > 0.0) || !(pm->w > 0.0) || !(pm->h > 0.0)) ILSX_FAIL(ILSX_ERR_ARG, "lunar: fps, scale, w and h must be positive");
+  if (!(pm->contact_solref[0] > 0.0) || !(pm->contact_solref[1] > 0.0) || !(pm->contact_solimp[0] > 0.0) || !(pm->contact_solimp[1] > 0.0))
+    ILSX_FAIL(ILSX_ERR_ARG, "lunar: contact_solref and the impedances of contact_solimp must be positive");
+  if (pm->contact_solimp[2] < 0.0 || pm->friction < 0.0) ILSX_FAIL(ILSX_ERR_ARG, "lunar: the impedance width and the friction must not be negative");
+  if (!(pm->sleep_lin_tol > 0.0) || !(pm->sleep_ang_tol > 0.0) || !(pm->sleep_time > 0.0)) ILSX_FAIL(ILSX_ERR_ARG, "lunar: the sleep tolerances must be positive");
+  double bottom = pm->hull[0][1];
+  for (int k = 0; k < 6; ++k) {
+    if (!std::isfinite(pm->hull[k][0]) || !std::isfinite(pm->hull[k][1])) ILSX_FAIL(ILSX_ERR_ARG, "lunar: every constant must be finite");
+    bottom = std::fmin(bottom, pm->hull[k][1]);
+  }
+  for (int i = 0; i < 2; ++i)
+    if (!(pm->foot[i][1] < bottom)) ILSX_FAIL(ILSX_ERR_ARG, "lunar: foot %d must lie below the hull's bottom (the hull has no contact response)", i);
+  LunarDev d;
+  memset(&d, 0, sizeof d);
+  d.frame_skip = pm->frame_skip; d.pgs_iters = pm->pgs_iters;
+  d.fps = pm->fps; d.scale = pm->scale; d.w = pm->w; d.h = pm->h; d.gravity = pm->gravity;
+  d.main_power = pm->main_engine_power; d.side_power = pm->side_engine_power; d.initial_random = pm->initial_random;
+  d.side_height = pm->side_engine_height; d.side_away = pm->side_engine_away; d.leg_down = pm->leg_down; d.helipad_y = pm->helipad_y;
+  d.mass = pm->mass; d.inertia = pm->inertia;
+  for (int k = 0; k < 2; ++k) { d.com[k] = pm->com[k]; d.foot[0][k] = pm->foot[0][k]; d.foot[1][k] = pm->foot[1][k]; }
+  for (int k = 0; k < 6; ++k) { d.hull[k][0] = pm->hull[k][0]; d.hull[k][1] = pm->hull[k][1]; }
+  d.friction = pm->friction;
+  for (int k = 0; k < 3; ++k) d.solimp[k] = pm->contact_solimp[k];
+  const double tc = pm->contact_solref[0], dr = pm->contact_solref[1], dmax = pm->contact_solimp[1];
+  d.con_b = 2.0 / (dmax * tc);
+  d.con_k = 1.0 / (dmax * dmax * tc * tc * dr * dr);
+  d.sleep_lin2 = pm->sleep_lin_tol * pm->sleep_lin_tol; d.sleep_ang2 = pm->sleep_ang_tol * pm->sleep_ang_tol; d.sleep_time = pm->sleep_time;
+  d.chunk_dx = pm->w / 10.0;
+  return create_classic(ctx, ILSX_LUNAR_TASK, nullptr, n_env, seed, out, nullptr, &d);
+}
+
 extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out) {
   if (!ctx || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_classic: bad argument");
   if (kind == ILSX_CLASSIC_INVERTED_PENDULUM || kind == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM) {
@@ -1174,6 +1226,7 @@ extern "C" int ilsx_vecenv_destroy(ilsx_vecenv* e) {
   delete e->hm3;
   delete e->cc;
   delete e->sw;
+  delete e->ln;
   delete e;
   return ILSX_OK;
 }
@@ -1226,6 +1279,7 @@ extern "C" int ilsx_vecenv_step(ilsx_vecenv* e, const float* act, const int32_t*
   A.m = e->dm; A.qpos = e->qpos; A.qvel = e->qvel; A.n_env = e->n_env;
   A.ids = dev; A.n_ids = n_ids; A.act = act; A.obs = obs; A.rew = rew; A.done = done;
   A.obs_cur = e->obs_cur;
+  if (e->step_draws) { A.seed = e->seed; A.stream = e->rng_stream; A.step = ++e->step_ctr; }   // no auto-reset here: only advance draws
   if (!e->norm_obs) return launch_env_step(e, A);
   if (!obs) A.obs = e->nobs;
   ILSX_TRY(launch_env_step(e, A));   // step() returns normalised observations (vecenvs.py:251-257)

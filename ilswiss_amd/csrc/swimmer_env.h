@@ -200,13 +200,13 @@ struct SwimmerTask {
   using State = LaneStateQV<N, N>;
 
   // _get_obs(): float32 (qpos[2:] | qvel)
-  static __device__ __forceinline__ void write_obs(const State& s, float* dst) {
+  static __device__ __forceinline__ void write_obs(const Model&, const State& s, float* dst) {
 #pragma unroll
     for (int i = 0; i < NL; ++i) dst[i] = (float)s.q[2 + i];
 #pragma unroll
     for (int i = 0; i < NL + 2; ++i) dst[NL + i] = (float)s.v[i];
   }
-  static __device__ __forceinline__ void obs_before(const State& s, const float*, float* dst) { write_obs(s, dst); }
+  static __device__ __forceinline__ void obs_before(const Model& m, const State& s, const float*, float* dst) { write_obs(m, s, dst); }
 
   // reset_model(): qpos = init + U(+-0.1) (counters 0 .. N-1 of the env's Philox stream), qvel = U(+-0.1) (counters N .. 2N-1)
   static __device__ __forceinline__ void reset_state(const Model& m, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, State& s) {

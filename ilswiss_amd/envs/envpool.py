@@ -9,9 +9,11 @@ import numpy as np
 
 from .vecenv import HipVectorEnv
 
-# every MuJoCo task the steppers model: planar (csrc/env2d_group.h), 3-D (csrc/env3d_wave.h) and cart-and-poles (csrc/classic_env.h)
+# every MuJoCo task the steppers model: planar (csrc/env2d_group.h), 3-D (csrc/env3d_wave.h) and cart-and-poles (csrc/classic_env.h);
+# and the Box2D lander (csrc/lunar_env.h)
 ENVPOOL_NAMES = {"Hopper": "hopper", "Walker2d": "walker2d", "HalfCheetah": "halfcheetah", "Ant": "ant", "Humanoid": "humanoid",
-                 "InvertedPendulum": "invertedpendulum", "InvertedDoublePendulum": "inverteddoublependulum"}
+                 "InvertedPendulum": "invertedpendulum", "InvertedDoublePendulum": "inverteddoublependulum",
+                 "LunarLanderContinuous": "lunarlandercont"}
 
 
 def _model_name(envpool_name):

@@ -14,6 +14,7 @@ from ..device import as_dev, get_context, host_ptr
 from .models import MODELS
 from .models3d import MODELS3D
 from .models_cartchain import MODELS_CARTCHAIN
+from .models_lunar import MODELS_LUNAR
 from .models_swimmer import MODELS_SWIMMER
 
 
@@ -54,6 +55,9 @@ CLASSIC_KINDS = {**CLASSIC, **CARTCHAIN}
 # stepper of its own beside the classic-control kinds: its task id is outside theirs and ilsx_vecenv_create_classic does not build it; the
 # constants always come from the model description (models_swimmer.py) through ilsx_vecenv_create_swimmer.
 SWIMMER = {"swimmer": 16}
+# gym 0.22's LunarLanderContinuous on this repository's one-body dynamics (k_lunar_step of csrc/lunar_env.h; ILSX_LUNAR_TASK), under the
+# envs_dict spelling.  As for the Swimmer, the constants always come from the model description (models_lunar.py).
+LUNAR = {"lunarlandercont": 17}
 
 
 def model_struct(m):
@@ -124,6 +128,35 @@ def swimmer_struct(m):
     for k in (0, 1, 2):
         s.limit_solimp[k] = m["limit_solimp"][k]
     s.timestep, s.density, s.viscosity = m["timestep"], m["density"], m["viscosity"]
+    return s
+
+
+_LUNAR_SCALARS = ("frame_skip", "pgs_iters", "fps", "scale", "w", "h", "gravity", "main_engine_power", "side_engine_power", "initial_random",
+                  "side_engine_height", "side_engine_away", "leg_down", "helipad_y", "mass", "inertia", "friction",
+                  "sleep_lin_tol", "sleep_ang_tol", "sleep_time")
+
+
+def lunar_struct(m):
+    """models_lunar dict -> ilsx_lunar_model (include/ilsx.h).  Raises ValueError for a model the struct cannot hold or that can be seen
+    to be wrong without the library: a hull that is not six vertices, two feet that are not two points, a foot above the hull's bottom."""
+    if len(m["hull_poly"]) != 6 or any(len(p) != 2 for p in m["hull_poly"]):
+        raise ValueError(f"lunarlandercont: the hull polygon has {len(m['hull_poly'])} vertices, ilsx_lunar_model holds 6")
+    if len(m["foot"]) != 2 or any(len(p) != 2 for p in m["foot"]):
+        raise ValueError("lunarlandercont: the model needs two foot points")
+    bottom = min(p[1] for p in m["hull_poly"])
+    if not all(p[1] < bottom for p in m["foot"]):
+        raise ValueError("lunarlandercont: a foot lies above the hull's bottom (the hull has no contact response)")
+    s = _lib.LunarModel()
+    for k in _LUNAR_SCALARS:
+        setattr(s, k, m[k])
+    for k in (0, 1):
+        s.com[k], s.contact_solref[k] = m["com"][k], m["contact_solref"][k]
+        for i in (0, 1):
+            s.foot[i][k] = m["foot"][i][k]
+        for i in range(6):
+            s.hull[i][k] = m["hull_poly"][i][k]
+    for k in (0, 1, 2):
+        s.contact_solimp[k] = m["contact_solimp"][k]
     return s
 
 
@@ -234,6 +267,13 @@ class HipVectorEnv:
             self.model = None
             ms = swimmer_struct(self.swimmer_model)
             _lib.check(self.ctx.lib.ilsx_vecenv_create_swimmer(self.ctx.h, C.byref(ms), self.env_num, C.c_uint64(seed), C.byref(self.h)))
+        elif env_name in LUNAR:         # the lander: the model description is the one source of the constants
+            if obs_shift is not None:
+                raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for this task")
+            self.lunar_model = model or MODELS_LUNAR[env_name]()
+            self.model = None
+            ms = lunar_struct(self.lunar_model)
+            _lib.check(self.ctx.lib.ilsx_vecenv_create_lunar(self.ctx.h, C.byref(ms), self.env_num, C.c_uint64(seed), C.byref(self.h)))
         elif env_name in CARTCHAIN:     # classic-control engine, cart and poles: the constants always come from the model description
             if obs_shift is not None:
                 raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for classic-control tasks")

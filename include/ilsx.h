@@ -709,6 +709,30 @@ typedef struct {
   double ctrl_range[2], timestep, density, viscosity, limit_solref[2], limit_solimp[3];
 } ilsx_swimmer_model;
 int ilsx_vecenv_create_swimmer(ilsx_ctx* ctx, const ilsx_swimmer_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
+/* LunarLanderContinuous — gym 0.22's LunarLander rules, continuous branch (envs_dict `lunarlandercont`; NormalizedBoxEnv over Box(-1, 1)
+ * is the identity), on this library's own dynamics (csrc/lunar_env.h; no Box2D): ONE rigid body of three degrees
+ * of freedom (hull and legs as one, the legs at their rest angle), soft contacts at the two foot points, semi-implicit Euler with
+ * frame_skip substeps per 1 / fps.  float64 state, nq = 14: qpos = (x, y, theta of the hull origin, smooth_y[0..10] of the episode's
+ * terrain); nv = 4: qvel = (vx, vy, omega, sleep_time); ilsx_vecenv_dims reports 3 degrees of freedom.  Lengths in metres (pixels /
+ * scale); com, foot (0 = left, 1 = right) and hull (the polygon's six vertices) are in the hull frame; mass and inertia (about com) are
+ * the composite body's.  Box(-1, 1) actions of width 2 (main engine, side engines), clipped to +-1; the engines' dispersion is drawn on
+ * every step.  Observation float32, 8 wide, gym's `state`, the two contact flags set when a foot is at or below the terrain; reward =
+ * shaping(after) - shaping(before) - 0.30 m_power - 0.03 s_power; done with reward -100 when a hull vertex touches the terrain or
+ * |obs[0]| >= 1, with +100 once the body has been below both sleep tolerances for sleep_time; no time limit of its own.  Contacts are soft
+ * rows (contact_solref = (timeconst, dampratio), contact_solimp = (d0, dmax, width)) with Coulomb friction.  The handle is an ordinary
+ * ilsx_vecenv of the classic-control kind (ilsx_vecenv_set_obs_affine is not available); ilsx_vecenv_create_classic does not build it:
+ * the caller is the one source of the constants (ilswiss_amd/envs/models_lunar.py).  Refused: non-finite constants; non-positive mass,
+ * inertia, fps, scale, w, h, frame_skip, pgs_iters, solref, impedances or sleep tolerances; a foot that is not below the hull's bottom. */
+enum { ILSX_LUNAR_TASK = 17 };   /* the task id of the handle, outside ILSX_CLASSIC_* */
+typedef struct {
+  int frame_skip, pgs_iters;
+  double fps, scale, w, h, gravity, main_engine_power, side_engine_power, initial_random;
+  double side_engine_height, side_engine_away, leg_down, helipad_y;
+  double mass, inertia, com[2], foot[2][2], hull[6][2];
+  double friction, contact_solref[2], contact_solimp[3];
+  double sleep_lin_tol, sleep_ang_tol, sleep_time;
+} ilsx_lunar_model;
+int ilsx_vecenv_create_lunar(ilsx_ctx* ctx, const ilsx_lunar_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
 /* discrete_n = n of a Discrete(n) action space, 0 for Box actions */
 int ilsx_vecenv_action_space(const ilsx_vecenv* env, int* discrete_n);
 /* Path mode of the fused rollout (ilsx_rollout_step with a replay ring): 0 (default) = every transition enters the ring when it
