@@ -13,10 +13,15 @@
 // Never done (the reference builds PendulumEnv directly, with no TimeLimit): max_path_length ends episodes.
 //
 // InvertedPendulum / InvertedDoublePendulum: gym 0.22's task rules (envs_dict.py `invertedpendulum` / `inverteddoublependulum`) on this
-// repository's own cart-and-poles dynamics (k_cartchain_step at the end of this file).
+// repository's own cart-and-poles dynamics (k_cartchain_step below).
+//
+// MountainCarContinuous / MountainCar / Acrobot: gym 0.22's closed-form Continuous_MountainCarEnv, MountainCarEnv and AcrobotEnv
+// (envs_dict.py `mountaincarcont`; gym's other two closed-form Discrete(3) tasks), operation for operation in float64 as CartPole and
+// Pendulum are; at the end of this file, DESIGN.md section 24.
 #pragma once
 
-enum { CLASSIC_CARTPOLE = 0, CLASSIC_PENDULUM = 1, CLASSIC_INVERTED_PENDULUM = 2, CLASSIC_INVERTED_DOUBLE_PENDULUM = 3 };
+enum { CLASSIC_CARTPOLE = 0, CLASSIC_PENDULUM = 1, CLASSIC_INVERTED_PENDULUM = 2, CLASSIC_INVERTED_DOUBLE_PENDULUM = 3,
+       CLASSIC_MOUNTAINCAR_CONT = 4, CLASSIC_MOUNTAINCAR = 5, CLASSIC_ACROBOT = 6 };
 
 // ------------------------------------------------------------------------------------------------ the lane-per-env frame
 // One lane per env, one frame for every task of this engine (and for swimmer_env.h): the rollout protocol is written once here and a task
@@ -569,3 +574,170 @@ template <int NP>
 __global__ __launch_bounds__(256) void k_cartchain_step(const EnvStepArgs A, const CartChainDev m) { lane_step_frame<CartChainTask<NP>>(A, m); }
 template <int NP>
 __global__ __launch_bounds__(256) void k_cartchain_reset(const LaneResetArgs R) { lane_reset_frame<CartChainTask<NP>>(R, CartChainDev{}); }
+
+// ------------------------------------------------------------------------------------------------ the two mountain cars
+// gym 0.22's Continuous_MountainCarEnv (continuous_mountain_car.py, behind NormalizedBoxEnv) and MountainCarEnv (mountain_car.py): a point
+// on the curve sin(3 x) pushed by `force`; qpos = (x), qvel = (v).  Both share the clamps and the wall; they differ in the push, the goal,
+// the reward and in what the env keeps between steps.
+struct MountainCarC {
+  static constexpr double min_position = -1.2, max_position = 0.6, max_speed = 0.07;
+  static constexpr double power = 0.0015, goal_cont = 0.45;      // Continuous_MountainCarEnv
+  static constexpr double force = 0.001, gravity = 0.0025, goal = 0.5;   // MountainCarEnv
+};
+
+// NormalizedBoxEnv.step on float32 arrays over Box(-1, 1): lb + (a + 1.0) * 0.5 * (ub - lb), one rounding per operation, then np.clip (which
+// is also the env's own min(max(action, -1), 1)).  The comparisons keep a NaN a NaN.
+__device__ __forceinline__ float mountaincar_force(float a) {
+  const float t = ((a + 1.0f) * 0.5f) * 2.0f;
+  const float s = -1.0f + t;
+  return s < -1.0f ? -1.0f : (s > 1.0f ? 1.0f : s);
+}
+
+// the clamps, the move and the inelastic left wall, as both envs have them (a NaN passes through every comparison)
+__device__ __forceinline__ void mountaincar_move(double& x, double& v) {
+  v = v < -MountainCarC::max_speed ? -MountainCarC::max_speed : (v > MountainCarC::max_speed ? MountainCarC::max_speed : v);
+  x = x + v;
+  x = x < MountainCarC::min_position ? MountainCarC::min_position : (x > MountainCarC::max_position ? MountainCarC::max_position : x);
+  if (x == MountainCarC::min_position && v < 0.0) v = 0.0;
+}
+
+template <bool CONT>
+struct MountainCarTask {
+  static constexpr int NQ = 1, NV = 1, O = 2, NA = 1;
+  static constexpr bool never_done = false;
+  using Model = LaneNoModel;
+  using State = LaneStateQV<1, 1>;
+
+  static __device__ __forceinline__ void write_obs(const Model&, const State& s, float* dst) { dst[0] = (float)s.q[0]; dst[1] = (float)s.v[0]; }
+  static __device__ __forceinline__ void obs_before(const Model& m, const State& s, const float*, float* dst) { write_obs(m, s, dst); }
+
+  // reset(): (np_random.uniform(low=-0.6, high=-0.4), 0) from counter 0 of the env's Philox stream.  The continuous env keeps a float32 array
+  static __device__ __forceinline__ void reset_state(const Model&, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, State& s) {
+    const double x = -0.6 + 0.2 * env_uniform(seed, stream, step, env, 0);
+    s.q[0] = CONT ? (double)(float)x : x;
+    s.v[0] = 0.0;
+  }
+
+  static __device__ __forceinline__ void advance(const Model&, State& s, const float (&act)[1], double& reward, bool& done, bool& finite) {
+    double x = s.q[0], v = s.v[0];
+    if constexpr (CONT) {
+      const double force = (double)mountaincar_force(act[0]);
+      v = v + (force * MountainCarC::power - MountainCarC::gravity * cos(3.0 * x));
+      mountaincar_move(x, v);
+      done = x >= MountainCarC::goal_cont && v >= 0.0;
+      reward = (done ? 100.0 : 0.0) - (force * force) * 0.1;
+      // self.state = np.array([position, velocity], dtype=np.float32): the env carries float32 values from step to step
+      x = (double)(float)x; v = (double)(float)v;
+    } else {
+      // the action is the index held as a float, used as it is: 0, 1, 2 push left, not at all, right
+      v = v + (((double)act[0] - 1.0) * MountainCarC::force + cos(3.0 * x) * (-MountainCarC::gravity));
+      mountaincar_move(x, v);
+      done = x >= MountainCarC::goal && v >= 0.0;
+      reward = -1.0;
+    }
+    finite = isfinite(x) && isfinite(v);
+    s.q[0] = x; s.v[0] = v;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_mountaincar_cont_step(const EnvStepArgs A) { lane_step_frame<MountainCarTask<true>>(A, {}); }
+__global__ __launch_bounds__(256) void k_mountaincar_cont_reset(const LaneResetArgs R) { lane_reset_frame<MountainCarTask<true>>(R, {}); }
+__global__ __launch_bounds__(256) void k_mountaincar_step(const EnvStepArgs A) { lane_step_frame<MountainCarTask<false>>(A, {}); }
+__global__ __launch_bounds__(256) void k_mountaincar_reset(const LaneResetArgs R) { lane_reset_frame<MountainCarTask<false>>(R, {}); }
+
+// ------------------------------------------------------------------------------------------------ Acrobot
+// gym 0.22's AcrobotEnv (acrobot.py), book_or_nips = "book", no torque noise: qpos = (theta1, theta2), qvel = (dtheta1, dtheta2).  Every
+// constant is written as gym's expression of LINK_MASS = LINK_LENGTH = LINK_MOI = 1, LINK_COM_POS = 0.5, g = 9.8 and folds, in float64, to
+// what Python computes.
+struct AcrobotC {
+  static constexpr double m1 = 1.0, m2 = 1.0, l1 = 1.0, lc1 = 0.5, lc2 = 0.5, I1 = 1.0, I2 = 1.0, g = 9.8, dt = 0.2;
+  static constexpr double pi = 3.141592653589793, max_vel_1 = 4.0 * pi, max_vel_2 = 9.0 * pi;
+  static constexpr int wrap_trips = 16;   // wrap()'s loops end after this many turns: an angle further out is not finite for the frame
+};
+
+// _dsdt, the "book" branch, in Python's order of evaluation (x ** 2 as x * x)
+__device__ __forceinline__ void acrobot_dsdt(const double (&q)[2], const double (&v)[2], double a, double (&acc)[2]) {
+  using C = AcrobotC;
+  const double c2 = cos(q[1]), s2 = sin(q[1]);
+  const double d1 = C::m1 * (C::lc1 * C::lc1) + C::m2 * (((C::l1 * C::l1) + (C::lc2 * C::lc2)) + ((2.0 * C::l1) * C::lc2) * c2) + C::I1 + C::I2;
+  const double d2 = C::m2 * ((C::lc2 * C::lc2) + (C::l1 * C::lc2) * c2) + C::I2;
+  const double phi2 = ((C::m2 * C::lc2) * C::g) * cos((q[0] + q[1]) - C::pi / 2.0);
+  const double phi1 = ((((-C::m2 * C::l1) * C::lc2) * (v[1] * v[1])) * s2 - (((((2.0 * C::m2) * C::l1) * C::lc2) * v[1]) * v[0]) * s2 +
+                       ((C::m1 * C::lc1 + C::m2 * C::l1) * C::g) * cos(q[0] - C::pi / 2.0)) + phi2;
+  const double dd2 = (((a + (d2 / d1) * phi1) - (((C::m2 * C::l1) * C::lc2) * (v[0] * v[0])) * s2) - phi2) /
+                     ((C::m2 * (C::lc2 * C::lc2) + C::I2) - (d2 * d2) / d1);
+  acc[0] = -(d2 * dd2 + phi1) / d1;
+  acc[1] = dd2;
+}
+
+// wrap(x, -pi, pi): gym's subtract / add 2 pi loops, ended after wrap_trips turns (gym's would not end on an infinite angle)
+__device__ __forceinline__ double acrobot_wrap(double x) {
+  const double diff = AcrobotC::pi - (-AcrobotC::pi);
+#pragma unroll 1
+  for (int i = 0; i < AcrobotC::wrap_trips && x > AcrobotC::pi; ++i) x = x - diff;
+#pragma unroll 1
+  for (int i = 0; i < AcrobotC::wrap_trips && x < -AcrobotC::pi; ++i) x = x + diff;
+  return x;
+}
+__device__ __forceinline__ double acrobot_bound(double x, double m, double M) { return x < m ? m : (x > M ? M : x); }   // min(max(x, m), M): NaN stays
+
+struct AcrobotTask {
+  static constexpr int NQ = 2, NV = 2, O = 6, NA = 1;
+  static constexpr bool never_done = false;
+  using Model = LaneNoModel;
+  using State = LaneStateQV<2, 2>;
+
+  // _get_ob(): float32 (cos theta1, sin theta1, cos theta2, sin theta2, dtheta1, dtheta2)
+  static __device__ __forceinline__ void write_obs(const Model&, const State& s, float* dst) {
+    dst[0] = (float)cos(s.q[0]); dst[1] = (float)sin(s.q[0]); dst[2] = (float)cos(s.q[1]); dst[3] = (float)sin(s.q[1]);
+    dst[4] = (float)s.v[0]; dst[5] = (float)s.v[1];
+  }
+  static __device__ __forceinline__ void obs_before(const Model& m, const State& s, const float*, float* dst) { write_obs(m, s, dst); }
+
+  // reset(): np_random.uniform(low=-0.1, high=0.1, size=(4,)).astype(np.float32) — component k of (theta1, theta2, dtheta1, dtheta2) from
+  // counter k of the env's Philox stream, rounded to float32
+  static __device__ __forceinline__ void reset_state(const Model&, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t env, State& s) {
+    s.q[0] = (double)(float)(-0.1 + 0.2 * env_uniform(seed, stream, step, env, 0));
+    s.q[1] = (double)(float)(-0.1 + 0.2 * env_uniform(seed, stream, step, env, 1));
+    s.v[0] = (double)(float)(-0.1 + 0.2 * env_uniform(seed, stream, step, env, 2));
+    s.v[1] = (double)(float)(-0.1 + 0.2 * env_uniform(seed, stream, step, env, 3));
+  }
+
+  static __device__ __forceinline__ void advance(const Model&, State& s, const float (&act)[1], double& reward, bool& done, bool& finite) {
+    // AVAIL_TORQUE[a] = a - 1: the index held as a float, used as it is.  rk4() carries it as a fifth component whose derivative is 0:
+    // y0[4] + dt * 0.0 is the torque itself in every stage
+    const double torque = (double)act[0] - 1.0;
+    const double h = AcrobotC::dt;
+    double qs[2], vs[2], qsum[2], vsum[2], a[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { qs[i] = s.q[i]; vs[i] = s.v[i]; qsum[i] = 0.0; vsum[i] = 0.0; }
+    // rk4(): ONE dynamics call site in a 4-trip loop, cartchain_substep's form; y0 + dt / 6 * (k1 + 2 k2 + 2 k3 + k4), dt2 = dt / 2
+#pragma unroll 1
+    for (int stage = 0; stage < 4; ++stage) {
+      acrobot_dsdt(qs, vs, torque, a);
+      const double w = (stage == 1 || stage == 2) ? 2.0 : 1.0;
+      const double ch = (stage == 2) ? h : h / 2.0;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        qsum[i] = stage == 0 ? vs[i] : qsum[i] + w * vs[i];
+        vsum[i] = stage == 0 ? a[i] : vsum[i] + w * a[i];
+        const double vn = s.v[i] + ch * a[i];
+        qs[i] = s.q[i] + ch * vs[i];
+        vs[i] = vn;
+      }
+    }
+    double th1 = s.q[0] + h / 6.0 * qsum[0], th2 = s.q[1] + h / 6.0 * qsum[1];
+    double w1 = s.v[0] + h / 6.0 * vsum[0], w2 = s.v[1] + h / 6.0 * vsum[1];
+    th1 = acrobot_wrap(th1); th2 = acrobot_wrap(th2);
+    w1 = acrobot_bound(w1, -AcrobotC::max_vel_1, AcrobotC::max_vel_1);
+    w2 = acrobot_bound(w2, -AcrobotC::max_vel_2, AcrobotC::max_vel_2);
+    done = -cos(th1) - cos(th2 + th1) > 1.0;
+    reward = done ? 0.0 : -1.0;
+    // an angle the capped wrap left outside [-pi, pi] counts as not finite: the episode ends there
+    finite = isfinite(w1) && isfinite(w2) && fabs(th1) <= AcrobotC::pi && fabs(th2) <= AcrobotC::pi;
+    s.q[0] = th1; s.q[1] = th2; s.v[0] = w1; s.v[1] = w2;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_acrobot_step(const EnvStepArgs A) { lane_step_frame<AcrobotTask>(A, {}); }
+__global__ __launch_bounds__(256) void k_acrobot_reset(const LaneResetArgs R) { lane_reset_frame<AcrobotTask>(R, {}); }

@@ -824,12 +824,18 @@ ENV_STEP_FN(step_cartchain1, k_cartchain_step<1>, LANES(A.n_ids, 256), 256, 0, *
 ENV_STEP_FN(step_cartchain2, k_cartchain_step<2>, LANES(A.n_ids, 256), 256, 0, *e->cc)
 ENV_STEP_FN(step_swimmer, k_swimmer_step<3>, LANES(A.n_ids, 256), 256, 0, *e->sw)
 ENV_STEP_FN(step_lunar, k_lunar_step, LANES(A.n_ids, 256), 256, 0, *e->ln)
+ENV_STEP_FN(step_mountaincar_cont, k_mountaincar_cont_step, LANES(A.n_ids, 256), 256, 0)
+ENV_STEP_FN(step_mountaincar, k_mountaincar_step, LANES(A.n_ids, 256), 256, 0)
+ENV_STEP_FN(step_acrobot, k_acrobot_step, LANES(A.n_ids, 256), 256, 0)
 ENV_RESET_FN(reset_cartpole, k_cartpole_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_pendulum, k_pendulum_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_cartchain1, k_cartchain_reset<1>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_cartchain2, k_cartchain_reset<2>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_swimmer, k_swimmer_reset<3>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS, *e->sw)
 ENV_RESET_FN(reset_lunar, k_lunar_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS, *e->ln)
+ENV_RESET_FN(reset_mountaincar_cont, k_mountaincar_cont_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
+ENV_RESET_FN(reset_mountaincar, k_mountaincar_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
+ENV_RESET_FN(reset_acrobot, k_acrobot_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 static const struct ClassicTask {
   int kind, n, o, a, discrete_n;   // n = degrees of freedom; discrete_n: the size of a Discrete action space, 0 = Box(-1, 1) actions
   decltype(ilsx_vecenv::step_fn) step;
@@ -840,6 +846,9 @@ static const struct ClassicTask {
     {ILSX_CLASSIC_PENDULUM, 1, 3, 1, 0, step_pendulum, reset_pendulum},
     {ILSX_CLASSIC_INVERTED_PENDULUM, 2, 4, 1, 0, step_cartchain1, reset_cartchain1},
     {ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM, 3, 11, 1, 0, step_cartchain2, reset_cartchain2},
+    {ILSX_CLASSIC_MOUNTAINCAR_CONT, 1, 2, 1, 0, step_mountaincar_cont, reset_mountaincar_cont},
+    {ILSX_CLASSIC_MOUNTAINCAR, 1, 2, 1, 3, step_mountaincar, reset_mountaincar},
+    {ILSX_CLASSIC_ACROBOT, 2, 6, 1, 3, step_acrobot, reset_acrobot},
     {ILSX_SWIMMER_TASK, 5, 8, 2, 0, step_swimmer, reset_swimmer},
     {ILSX_LUNAR_TASK, 3, 8, 2, 0, step_lunar, reset_lunar, 14, 4},   // qpos carries the terrain, qvel the sleep clock
 };
@@ -1197,7 +1206,8 @@ extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, ui
     cartchain_defaults(kind == ILSX_CLASSIC_INVERTED_PENDULUM ? 1 : 2, &m);
     return ilsx_vecenv_create_cartchain(ctx, &m, n_env, seed, out);
   }
-  if (kind != ILSX_CLASSIC_CARTPOLE && kind != ILSX_CLASSIC_PENDULUM)
+  if (kind != ILSX_CLASSIC_CARTPOLE && kind != ILSX_CLASSIC_PENDULUM && kind != ILSX_CLASSIC_MOUNTAINCAR_CONT &&
+      kind != ILSX_CLASSIC_MOUNTAINCAR && kind != ILSX_CLASSIC_ACROBOT)
     ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_classic: unknown kind %d", kind);
   return create_classic(ctx, kind, nullptr, n_env, seed, out);
 }

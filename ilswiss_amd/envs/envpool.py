@@ -10,10 +10,11 @@ import numpy as np
 from .vecenv import HipVectorEnv
 
 # every MuJoCo task the steppers model: planar (csrc/env2d_group.h), 3-D (csrc/env3d_wave.h) and cart-and-poles (csrc/classic_env.h);
-# and the Box2D lander (csrc/lunar_env.h)
+# the Box2D lander (csrc/lunar_env.h); and gym's closed-form mountain cars and Acrobot (csrc/classic_env.h)
 ENVPOOL_NAMES = {"Hopper": "hopper", "Walker2d": "walker2d", "HalfCheetah": "halfcheetah", "Ant": "ant", "Humanoid": "humanoid",
                  "InvertedPendulum": "invertedpendulum", "InvertedDoublePendulum": "inverteddoublependulum",
-                 "LunarLanderContinuous": "lunarlandercont"}
+                 "LunarLanderContinuous": "lunarlandercont",
+                 "MountainCarContinuous": "mountaincarcont", "MountainCar": "mountaincar", "Acrobot": "acrobot"}
 
 
 def _model_name(envpool_name):

@@ -58,6 +58,11 @@ SWIMMER = {"swimmer": 16}
 # gym 0.22's LunarLanderContinuous on this repository's one-body dynamics (k_lunar_step of csrc/lunar_env.h; ILSX_LUNAR_TASK), under the
 # envs_dict spelling.  As for the Swimmer, the constants always come from the model description (models_lunar.py).
 LUNAR = {"lunarlandercont": 17}
+# gym 0.22's closed-form tasks of the classic-control engine beyond CartPole and Pendulum (ILSX_CLASSIC_MOUNTAINCAR_CONT / _MOUNTAINCAR /
+# _ACROBOT): `mountaincarcont` is the envs_dict spelling of Continuous_MountainCarEnv behind NormalizedBoxEnv,
+# `mountaincar` and `acrobot` are MountainCar-v0's and Acrobot-v1's classes, both Discrete(3).  No model description, as for CLASSIC; a
+# dict of their own beside it.
+GYM_CLASSIC = {"mountaincarcont": 4, "mountaincar": 5, "acrobot": 6}
 
 
 def model_struct(m):
@@ -290,6 +295,13 @@ class HipVectorEnv:
                 raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for classic-control tasks")
             self.model = None
             _lib.check(self.ctx.lib.ilsx_vecenv_create_classic(self.ctx.h, CLASSIC[env_name], self.env_num, C.c_uint64(seed), C.byref(self.h)))
+        elif env_name in GYM_CLASSIC:   # classic-control engine (the mountain cars, Acrobot)
+            if model is not None:
+                raise ValueError(f"{env_name}: a classic-control task has no model description")
+            if obs_shift is not None:
+                raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for classic-control tasks")
+            self.model = None
+            _lib.check(self.ctx.lib.ilsx_vecenv_create_classic(self.ctx.h, GYM_CLASSIC[env_name], self.env_num, C.c_uint64(seed), C.byref(self.h)))
         else:
             self.model = model or (MODELS3D[env_name]() if env_name in MODELS3D else MODELS[env_name]())
         if self.model is not None and "n_link" in self.model:      # 3-D engine (Ant / Humanoid)

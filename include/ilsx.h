@@ -664,8 +664,23 @@ int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_model* model, i
  * reward = 10 - (0.01 x_tip^2 + (y_tip - 2)^2) - (1e-3 qvel_1^2 + 5e-3 qvel_2^2) of the state after the step, done = y_tip <= 1, reset
  * qpos = U(+-0.1), qvel = 0.1 N(0, 1).  ilsx_vecenv_create_classic builds them from the built-in constants (the values of
  * ilswiss_amd/envs/models_cartchain.py); ilsx_vecenv_create_cartchain takes the constants from the caller.
+ * ILSX_CLASSIC_MOUNTAINCAR_CONT — gym 0.22's Continuous_MountainCarEnv (envs_dict `mountaincarcont`) behind NormalizedBoxEnv: Box(-1, 1)
+ * actions of width 1 (discrete_n 0), force = clip(-1 + (a + 1) * 0.5 * 2, +-1) in float32; state qpos = (x), qvel = (v) (nq = nv = 1),
+ * doubles holding float32 values (the env keeps a float32 array between steps), the arithmetic of a step float64: v' = clip(v + force *
+ * 0.0015 - 0.0025 cos(3 x), +-0.07), x' = clip(x + v', -1.2, 0.6), v' = 0 where x' = -1.2 and v' < 0; done = x' >= 0.45 and v' >= 0;
+ * reward = (done ? 100 : 0) - 0.1 force^2; observation = the two floats; reset: x = float32(-0.6 + 0.2 u), v = 0.
+ * ILSX_CLASSIC_MOUNTAINCAR — gym 0.22's MountainCarEnv: Discrete(3) (the index as a float in a 1-wide action column, used as it is: 0 left,
+ * 1 none, 2 right); float64 state qpos = (x), qvel = (v); v' = clip(v + (a - 1) * 0.001 + cos(3 x) * (-0.0025), +-0.07), x' and the wall
+ * as above; done = x' >= 0.5 and v' >= 0; reward -1 on every step; observation = float32 (x, v); reset: x = -0.6 + 0.2 u, v = 0.
+ * ILSX_CLASSIC_ACROBOT — gym 0.22's AcrobotEnv ("book" dynamics, no torque noise): Discrete(3), torque = a - 1; float64 state qpos =
+ * (theta_1, theta_2), qvel = (dtheta_1, dtheta_2) (nq = nv = 2); one classic RK4 step of 0.2 s, then wrap() of both angles into [-pi, pi]
+ * (its loops end after 16 turns; an angle still outside ends the episode as a non-finite state does) and bound() of the velocities to
+ * +-4 pi / +-9 pi; done = -cos theta_1 - cos(theta_2 + theta_1) > 1; reward = done ? 0 : -1; observation = float32 (cos theta_1,
+ * sin theta_1, cos theta_2, sin theta_2, dtheta_1, dtheta_2) (6 wide); reset: four draws U(-0.1, 0.1) rounded to float32.
+ * None of the three carries a TimeLimit (the reference builds the classes directly): max_path_length ends episodes.
  * Reset / step / rollout / evaluation entry points are the ordinary ones; ilsx_vecenv_set_obs_affine is not available. */
 enum { ILSX_CLASSIC_CARTPOLE = 0, ILSX_CLASSIC_PENDULUM = 1, ILSX_CLASSIC_INVERTED_PENDULUM = 2, ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM = 3 };
+enum { ILSX_CLASSIC_MOUNTAINCAR_CONT = 4, ILSX_CLASSIC_MOUNTAINCAR = 5, ILSX_CLASSIC_ACROBOT = 6 };   /* gym's closed-form tasks, no model */
 int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out);
 /* A cart on a rail (DoF 0, slide along x) carrying n_pole poles in a chain (DoF k = hinge of pole k, angle relative to its parent).
  * Body 0 is the cart, body k pole k; a pole's absolute angle is jsign * (q_1 + ... + q_k), counter-clockwise in (x, z).  anchor[k] =
