@@ -14,3 +14,4 @@ from .trainer import DeviceTrainer, Trainer  # noqa: F401
 from .mbpo import BNN, MBPO, BNNTrainer, FakeEnv  # noqa: F401
 from .discrete_sac import DiscreteSoftActorCritic  # noqa: F401
 from .ddpg import DDPG, GaussianStrategy, MlpPolicy, OUStrategy, PolicyWrappedWithExplorationStrategy  # noqa: F401
+from .dqn import DQN, ArgmaxDiscretePolicy, DoubleDQN  # noqa: F401

@@ -157,6 +157,15 @@ class DsacStats(C.Structure):  # ilsx_dsac_stats
                 ("q1_pred", C.c_float * 4), ("q2_pred", C.c_float * 4)]
 
 
+class DqnCfg(C.Structure):  # ilsx_dqn_cfg
+    _fields_ = [("discount", C.c_float), ("learning_rate", C.c_float), ("tau", C.c_float), ("use_hard_updates", C.c_int32),
+                ("hard_update_period", C.c_int32), ("double_q", C.c_int32), ("max_batch", C.c_int32)]
+
+
+class DqnStats(C.Structure):  # ilsx_dqn_stats
+    _fields_ = [("qf_loss", C.c_float), ("y_pred", C.c_float * 4)]
+
+
 class SacvCfg(C.Structure):  # ilsx_sacv_cfg
     _fields_ = [("reward_scale", C.c_float), ("discount", C.c_float), ("alpha", C.c_float), ("policy_lr", C.c_float),
                 ("qf_lr", C.c_float), ("vf_lr", C.c_float), ("soft_target_tau", C.c_float),
@@ -404,6 +413,15 @@ PROTOTYPES = {
     "ilsx_dsac_set_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
     "ilsx_dsac_get_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
     "ilsx_dsac_set_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
+    "ilsx_net_set_epsilon_greedy": (C.c_int, [vp, C.c_int, C.c_float]),
+    "ilsx_dqn_create": (C.c_int, [vp, C.POINTER(DqnCfg), vp, C.POINTER(vp)]),
+    "ilsx_dqn_destroy": (C.c_int, [vp]),
+    "ilsx_dqn_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(DqnStats)]),
+    "ilsx_dqn_train_from_replay": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(DqnStats)]),
+    "ilsx_dqn_get_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_dqn_set_params": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+    "ilsx_dqn_get_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
+    "ilsx_dqn_set_opt": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(OptMeta)]),
     "ilsx_mbpo_model_step": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                        C.POINTER(C.c_int)]),
     "ilsx_her_horizon_gather": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

@@ -146,9 +146,14 @@ struct ilsx_net {
   float noise = 0.f, noise_clip = 0.f, max_act = 1.f;
   bool out_linear = false;   // output activation: identity (Mlp's default) instead of tanh (ilsx_net_set_output_linear)
   bool categorical = false;  // DiscretePolicy (policies.py:39-101): LogSoftmax head, ilsx_policy_act writes an index (ilsx_net_set_categorical)
+  bool egreedy = false;      // ArgmaxDiscretePolicy under EpsilonGreedy (policies/argmax.py, exploration_strategies/epsilon_greedy.py): ilsx_policy_act writes
+  float epsilon = 0.f;       // the first maximal output's index, or with probability epsilon a uniform one (ilsx_net_set_epsilon_greedy)
+  bool discrete() const { return categorical || egreedy; }   // acts in a Discrete space: writes an index
 };
 // DiscretePolicy's action draw from raw logits z[rows][n] (dsac.h k_categorical_act; ilsx_ac.hip)
 int launch_categorical_act(ilsx_ctx* ctx, const float* z, int rows, int n, int deterministic, unsigned long long step, float* act, float* logp);
+// the epsilon-greedy argmax over raw head outputs z[rows][n] (dqn.h k_egreedy_act; ilsx_ac.hip)
+int launch_egreedy_act(ilsx_ctx* ctx, const float* z, int rows, int n, int deterministic, float epsilon, unsigned long long step, float* act);
 
 int net_upload_flat(ilsx_ctx* ctx, const NetLayout& L, float* dev_base, const float* src, size_t n, int src_is_device);
 int net_download_flat(ilsx_ctx* ctx, const NetLayout& L, const float* dev_base, float* dst, size_t n, int dst_is_device);

@@ -2,6 +2,7 @@
 //   TD3    rlkit/torch/algorithms/td3/td3.py:21-124,180-183 + MlpGaussianNoisePolicy (common/policies.py:130-188)
 //   SAC-V  rlkit/torch/algorithms/sac/sac.py:23-179,242-243 (state-value variant, fixed temperature)
 //   DDPG   rlkit/torch/algorithms/ddpg/ddpg.py:21-235 + MlpPolicy (common/policies.py:106-127); step structure at its section below
+//   discrete SAC (dsac.h) and DQN / Double DQN (dqn.h, rlkit/torch/algorithms/dqn/): step structures at their sections below
 //
 // One agent = one trainable arena P = [Q1 | Q2 | (V |) pi] with gradient / Adam-moment arenas of the same layout and a
 // target arena T of the same layout (only the slices the algorithm has targets for are ever read).  Adam runs in the
@@ -308,6 +309,7 @@ extern "C" int ilsx_td3_create(ilsx_ctx* ctx, const ilsx_td3_cfg* cfg, ilsx_net*
   const ilsx_mlp_cfg &cp = pi->lay.cfg, &c1 = q1->lay.cfg, &c2 = q2->lay.cfg;
   if (cp.n_heads != 1) ILSX_FAIL(ILSX_ERR_ARG, "TD3 policy is a single-head Mlp with tanh output (policies.py:130-188)");
   if (pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "TD3 trains a continuous policy; this one is categorical (use ilsx_dsac_create)");
+  if (pi->egreedy) ILSX_FAIL(ILSX_ERR_ARG, "TD3 trains a continuous policy; this one is epsilon-greedy (use ilsx_dqn_create)");
   if (c1.n_heads != 1 || c1.out_dim != 1 || memcmp(&c1, &c2, sizeof c1) != 0) ILSX_FAIL(ILSX_ERR_ARG, "qf1/qf2 must be identical single-output FlattenMlp's");
   if (c1.in_dim != cp.in_dim + cp.out_dim) ILSX_FAIL(ILSX_ERR_ARG, "qf input %d != obs %d + act %d", c1.in_dim, cp.in_dim, cp.out_dim);
   if (cfg->max_batch < 1 || cfg->max_batch > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "max_batch=%d out of range", cfg->max_batch);
@@ -612,7 +614,7 @@ __global__ __launch_bounds__(256) void k_ddpg_adam_decay(float* __restrict__ G, 
   }
 }
 // ptu.copy_model_params_from_to (pytorch_util.py) over the whole arena; n is a multiple of 4
-__global__ __launch_bounds__(256) void k_ddpg_hard_copy(const float4* __restrict__ p, float4* __restrict__ t, int n4) {
+__global__ __launch_bounds__(256) void k_ac_hard_copy(const float4* __restrict__ p, float4* __restrict__ t, int n4) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) t[i] = p[i];
 }
 
@@ -632,6 +634,7 @@ extern "C" int ilsx_ddpg_create(ilsx_ctx* ctx, const ilsx_ddpg_cfg* cfg, ilsx_ne
   const ilsx_mlp_cfg &cp = pi->lay.cfg, &cq = qf->lay.cfg;
   if (cp.n_heads != 1) ILSX_FAIL(ILSX_ERR_ARG, "DDPG policy is a single-head Mlp (policies.py:106-127)");
   if (pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "DDPG trains a continuous policy; this one is categorical");
+  if (pi->egreedy) ILSX_FAIL(ILSX_ERR_ARG, "DDPG trains a continuous policy; this one is epsilon-greedy (use ilsx_dqn_create)");
   if (cq.n_heads != 1 || cq.out_dim != 1) ILSX_FAIL(ILSX_ERR_ARG, "qf must be a single-output FlattenMlp");
   if (cq.in_dim != cp.in_dim + cp.out_dim) ILSX_FAIL(ILSX_ERR_ARG, "qf input %d != obs %d + act %d", cq.in_dim, cp.in_dim, cp.out_dim);
   if (cfg->max_batch < 1 || cfg->max_batch > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "max_batch=%d out of range", cfg->max_batch);
@@ -778,7 +781,7 @@ static int ddpg_step(ilsx_ddpg* t, ilsx_ddpg_stats* stats) {
     HIPCHK(hipGetLastError());
   } else if (t->n_steps % c.target_update_period == 0) {   // decided on the host from the step counter: no device read, no sync
     const int n4 = (int)(g->off[2] / 4);
-    hipLaunchKernelGGL(k_ddpg_hard_copy, dim3(std::min(1024, (n4 + 255) / 256)), dim3(256), 0, st, (const float4*)g->P, (float4*)g->T, n4);
+    hipLaunchKernelGGL(k_ac_hard_copy, dim3(std::min(1024, (n4 + 255) / 256)), dim3(256), 0, st, (const float4*)g->P, (float4*)g->T, n4);
     HIPCHK(hipGetLastError());
   }
   ILSX_TRY(ac_tick(g, 3, 1));
@@ -1197,6 +1200,8 @@ struct ilsx_dsac {
 extern "C" int ilsx_dsac_create(ilsx_ctx* ctx, const ilsx_dsac_cfg* cfg, ilsx_net* pi, ilsx_net* q1, ilsx_net* q2, ilsx_dsac** out) {
   if (!ctx || !cfg || !pi || !q1 || !q2 || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dsac_create: NULL argument");
   const ilsx_mlp_cfg &cp = pi->lay.cfg, &c1 = q1->lay.cfg, &c2 = q2->lay.cfg;
+  if (pi->egreedy || q1->egreedy || q2->egreedy)
+    ILSX_FAIL(ILSX_ERR_ARG, "discrete SAC trains a categorical policy and plain critics; one of these networks is epsilon-greedy (use ilsx_dqn_create)");
   if (!pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "discrete SAC needs a categorical policy (ilsx_net_set_categorical)");
   if (q1->categorical || q2->categorical) ILSX_FAIL(ILSX_ERR_ARG, "qf1 / qf2 must be plain FlattenMlp's, not policies");
   if (c1.n_heads != 1 || memcmp(&c1, &c2, sizeof c1) != 0) ILSX_FAIL(ILSX_ERR_ARG, "qf1/qf2 must be identical single-head FlattenMlp's");
@@ -1346,4 +1351,153 @@ extern "C" int ilsx_dsac_set_opt(ilsx_dsac* d, int which, const float* m_host, c
   if (!d) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
   ilsx_opt_meta m2; if (meta) m2 = *meta;
   return ac_opt(&d->g, which, true, const_cast<float*>(m_host), const_cast<float*>(v_host), n, meta ? &m2 : nullptr);
+}
+
+// ================================================================================================ DQN / Double DQN
+// rlkit/torch/algorithms/dqn/dqn.py:67-112 and double_dqn.py:12-38 on the trunk kernels above plus the loss kernel of dqn.h.  Arena P = [Q]:
+//   fwd{TQ(s') ; Q(s) saved (; Q(s'): Double DQN)} ; k_dqn_grad ; bwd{Q: given} ; dW+Adam(+Polyak){Q} | hard copy on the counter's multiples ; tick
+// The soft update rides in the Adam epilogue (target <- (1 - tau) target + tau Q on the stepped weights, dqn.py:91-92,112); the hard copy is
+// DDPG's kernel, decided on the host from a counter that is tested before its increment (:109).
+#include "dqn.h"
+
+int launch_egreedy_act(ilsx_ctx* ctx, const float* z, int rows, int n, int deterministic, float epsilon, unsigned long long step, float* act) {
+  if (rows <= 0) return ILSX_OK;
+  hipLaunchKernelGGL(k_egreedy_act, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, z, rows, n, deterministic, epsilon, ctx->seed,
+                     0x45475200u /* 'EGR' */, step, act);
+  HIPCHK(hipGetLastError());
+  return ILSX_OK;
+}
+
+struct ilsx_dqn {
+  AcAgent g;
+  ilsx_dqn_cfg cfg;
+  int n = 0;               // actions
+  long long n_steps = 0;   // dqn.py's _n_train_steps_total as _update_target_network reads it: one per train step, tested before its increment
+  float *tq = nullptr, *qn = nullptr, *q = nullptr;   // [cs][B][n]
+  float* gq = nullptr;                                // loss gradient [B][n]
+  float *y = nullptr, *qa = nullptr;                  // per-row statistics [B]
+  HeadSlabs slab(const float* p) const { return HeadSlabs{p, g.cs, g.max_batch}; }
+};
+
+extern "C" int ilsx_dqn_create(ilsx_ctx* ctx, const ilsx_dqn_cfg* cfg, ilsx_net* qf, ilsx_dqn** out) {
+  if (!ctx || !cfg || !qf || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dqn_create: NULL argument");
+  const ilsx_mlp_cfg& cq = qf->lay.cfg;
+  if (cq.n_heads != 1 || qf->categorical || qf->noise_policy) ILSX_FAIL(ILSX_ERR_ARG, "DQN's qf is a plain single-head FlattenMlp obs -> n actions");
+  if (cq.out_dim < 2 || cq.out_dim > ILSX_MAX_NO) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "DQN's qf has 2..%d outputs, got %d", ILSX_MAX_NO, cq.out_dim);
+  if (cfg->max_batch < 1 || cfg->max_batch > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "max_batch=%d out of range", cfg->max_batch);
+  if (cfg->use_hard_updates && cfg->hard_update_period < 1) ILSX_FAIL(ILSX_ERR_ARG, "hard_update_period must be >= 1");
+  HIPCHK(hipSetDevice(ctx->device));
+  ilsx_dqn* t = new ilsx_dqn();
+  t->cfg = *cfg;
+  t->n = cq.out_dim;
+  ilsx_net* nets[1] = {qf};
+  const int opt_of[1] = {0};
+  AcAgent* g = &t->g;
+  g->lr[0] = cfg->learning_rate; g->beta_1 = 0.9f;   // optim.Adam(lr=learning_rate), dqn.py:59-62
+  int rc = ac_init(g, ctx, nets, 1, opt_of, cfg->max_batch, cq.in_dim, 1);
+  const size_t B = (size_t)cfg->max_batch, n = (size_t)t->n, CS = (size_t)g->cs;
+  float** heads[] = {&t->tq, &t->qn, &t->q};
+  for (float** b : heads) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B * n);
+  if (rc == ILSX_OK) rc = ac_alloc(g, &t->gq, B * n);
+  float** rows[] = {&t->y, &t->qa};
+  for (float** b : rows) if (rc == ILSX_OK) rc = ac_alloc(g, b, B);
+  if (rc == ILSX_OK) rc = ac_tick(g, 0, 0);
+  if (rc != ILSX_OK) { delete t; return rc; }
+  *out = t;
+  return ILSX_OK;
+}
+extern "C" int ilsx_dqn_destroy(ilsx_dqn* t) {
+  if (!t) return ILSX_OK;
+  ac_release(&t->g);
+  delete t;
+  return ILSX_OK;
+}
+
+static int dqn_step(ilsx_dqn* t, ilsx_dqn_stats* stats) {
+  AcAgent* g = &t->g;
+  const ilsx_dqn_cfg& c = t->cfg;
+  hipStream_t st = g->ctx->stream;
+  {  // target net at s' ; online net at s (saved: its backward) ; Double DQN: online net at s'
+    FwdArgs A = ac_fwd_args(g, c.double_q ? 3 : 2);
+    ac_fwd(g, A.t[0], 0, true, g->s2, g->o, nullptr, 0, false); ac_out(g, A.t[0], t->tq);
+    ac_fwd(g, A.t[1], 0, false, g->s, g->o, nullptr, 0, true); ac_out(g, A.t[1], t->q);
+    if (c.double_q) { ac_fwd(g, A.t[2], 0, false, g->s2, g->o, nullptr, 0, false); ac_out(g, A.t[2], t->qn); }
+    ILSX_TRY(ac_launch_fwd(g, A, g->L[0].KP));
+  }
+  {
+    DqnGradArgs A;
+    memset(&A, 0, sizeof A);
+    A.tq = t->slab(t->tq); A.qn = t->slab(t->qn); A.q = t->slab(t->q);
+    A.act = g->ac; A.rew = g->r; A.done = g->d; A.g = t->gq; A.y = t->y; A.qa = t->qa;
+    A.B = g->B; A.n = t->n; A.double_q = c.double_q ? 1 : 0; A.gamma = c.discount; A.inv_B = 1.0f / (float)g->B;
+    hipLaunchKernelGGL(k_dqn_grad, dim3((g->B + 255) / 256), dim3(256), 0, st, A);
+    HIPCHK(hipGetLastError());
+  }
+  {
+    BwdArgs A = ac_bwd_args(g, 1, 0.f, 0.f);
+    ac_bwd(g, A.t[0], 0, true);
+    A.t[0].loss = LOSS_GIVEN; A.t[0].given = t->gq;
+    ILSX_TRY(ac_launch_bwd(g, A));
+  }
+  ILSX_TRY(ac_dw_adam(g, 0, 1, !c.use_hard_updates, c.tau));   // dqn.py:89-92 (+ :112 in the epilogue)
+  if (c.use_hard_updates && t->n_steps % c.hard_update_period == 0) {   // :108-110, decided on the host: no device read, no sync
+    const int n4 = (int)(g->off[1] / 4);
+    hipLaunchKernelGGL(k_ac_hard_copy, dim3(std::min(1024, (n4 + 255) / 256)), dim3(256), 0, st, (const float4*)g->P, (float4*)g->T, n4);
+    HIPCHK(hipGetLastError());
+  }
+  ILSX_TRY(ac_tick(g, 1, 1));
+  t->n_steps += 1;
+  if (stats) {  // dqn.py:97-105; the device buffers still hold this step's predictions
+    const size_t B = (size_t)g->B;
+    std::vector<float> y, qa;
+    ILSX_TRY(ac_fetch(g, t->y, B, y)); ILSX_TRY(ac_fetch(g, t->qa, B, qa));
+    HIPCHK(hipStreamSynchronize(st));
+    stats->qf_loss = mean_sq_diff(qa, y);
+    msmm(qa.data(), B, stats->y_pred);
+  }
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_dqn_train_step(ilsx_dqn* t, const float* obs, const float* act, const float* rew, const float* done, const float* nobs,
+                                   int B, ilsx_dqn_stats* stats) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dqn_train_step: NULL handle");
+  ILSX_TRY(ac_stage(&t->g, obs, act, rew, done, nobs, B, nullptr));
+  std::vector<float> a;   // the one-hot action as an index: refuse what is none
+  ILSX_TRY(ac_fetch(&t->g, t->g.ac, (size_t)B, a));
+  HIPCHK(hipStreamSynchronize(t->g.ctx->stream));
+  for (int i = 0; i < B; ++i)
+    if (!(a[i] >= 0.0f && a[i] < (float)t->n && a[i] == std::floor(a[i])))
+      ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dqn_train_step: action %g of row %d is not an index in [0, %d)", (double)a[i], i, t->n);
+  return dqn_step(t, stats);
+}
+extern "C" int ilsx_dqn_train_from_replay(ilsx_dqn* t, ilsx_replay* rb, int n_steps, int B, ilsx_dqn_stats* stats) {
+  if (!t || n_steps < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_dqn_train_from_replay: bad argument");
+  HIPCHK(hipSetDevice(t->g.ctx->device));
+  for (int i = 0; i < n_steps; ++i) {
+    ILSX_TRY(ac_sample(&t->g, rb, B));
+    ILSX_TRY(dqn_step(t, i == 0 ? stats : nullptr));   // statistics of the first batch only (dqn.py:97)
+  }
+  return ILSX_OK;
+}
+// which: 0 qf, 1 target_qf
+extern "C" int ilsx_dqn_get_params(ilsx_dqn* t, int which, float* dst_host, size_t n) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  return ac_params(&t->g, which, false, dst_host, n);
+}
+extern "C" int ilsx_dqn_set_params(ilsx_dqn* t, int which, const float* src_host, size_t n) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  return ac_params(&t->g, which, true, const_cast<float*>(src_host), n);
+}
+extern "C" int ilsx_dqn_get_opt(ilsx_dqn* t, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  ILSX_TRY(ac_opt(&t->g, which, false, m_host, v_host, n, meta));
+  if (meta) meta->n_train_steps = t->n_steps;
+  return ILSX_OK;
+}
+extern "C" int ilsx_dqn_set_opt(ilsx_dqn* t, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta) {
+  if (!t) ILSX_FAIL(ILSX_ERR_ARG, "NULL handle");
+  ilsx_opt_meta m2; if (meta) m2 = *meta;
+  ILSX_TRY(ac_opt(&t->g, which, true, const_cast<float*>(m_host), const_cast<float*>(v_host), n, meta ? &m2 : nullptr));
+  if (meta) t->n_steps = meta->n_train_steps;
+  return ILSX_OK;
 }

@@ -996,8 +996,9 @@ extern "C" int ilsx_mlp_forward(ilsx_net* n, const float* x, int rows, float* y)
 extern "C" int ilsx_policy_act(ilsx_net* pi, const float* obs, int nrows, int deterministic, const float* eps,
                                float* act, float* logp) {
   if (!pi || !obs || !act || nrows < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: bad argument");
-  if (pi->categorical) {   // DiscretePolicy: raw logits through the trunk, then the categorical head's own launch
-    if (eps) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: a categorical policy takes no explicit noise");
+  if (pi->discrete()) {   // DiscretePolicy / epsilon-greedy argmax: raw head outputs through the trunk, then the head's own launch
+    if (eps) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: a %s policy takes no explicit noise", pi->categorical ? "categorical" : "epsilon-greedy");
+    if (pi->egreedy && logp) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: an epsilon-greedy policy has no log-probability");
     HIPCHK(hipSetDevice(pi->ctx->device));
     const int n = pi->lay.cfg.out_dim;
     if (nrows == 0) return ILSX_OK;
@@ -1008,6 +1009,7 @@ extern "C" int ilsx_policy_act(ilsx_net* pi, const float* obs, int nrows, int de
       pi->ws_rows = nrows;
     }
     ILSX_TRY(ilsx_mlp_forward(pi, obs, nrows, pi->ws_out));
+    if (pi->egreedy) return launch_egreedy_act(pi->ctx, pi->ws_out, nrows, n, deterministic, pi->epsilon, ++pi->ctx->act_calls, act);
     return launch_categorical_act(pi->ctx, pi->ws_out, nrows, n, deterministic, ++pi->ctx->act_calls, act, logp);
   }
   if (pi->lay.cfg.n_heads != 2 && !pi->noise_policy)
@@ -1038,6 +1040,7 @@ extern "C" int ilsx_net_set_noise_policy(ilsx_net* pi, float policy_noise, float
   if (!pi) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_net_set_noise_policy: NULL network");
   if (pi->lay.cfg.n_heads != 1) ILSX_FAIL(ILSX_ERR_ARG, "a noise policy is a single-head Mlp (policies.py:130-188)");
   if (pi->categorical) ILSX_FAIL(ILSX_ERR_ARG, "a categorical policy cannot be a noise policy");
+  if (pi->egreedy) ILSX_FAIL(ILSX_ERR_ARG, "an epsilon-greedy policy cannot be a noise policy");
   pi->noise_policy = true; pi->noise = policy_noise; pi->noise_clip = policy_noise_clip; pi->max_act = max_act;
   return ILSX_OK;
 }
@@ -1046,10 +1049,25 @@ extern "C" int ilsx_net_set_categorical(ilsx_net* pi, int on) {
   if (!pi) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_net_set_categorical: NULL network");
   if (on) {
     if (pi->lay.cfg.n_heads != 1 || pi->noise_policy) ILSX_FAIL(ILSX_ERR_ARG, "a categorical policy is a single-head Mlp (policies.py:39-101)");
+    if (pi->egreedy) ILSX_FAIL(ILSX_ERR_ARG, "an epsilon-greedy policy cannot be categorical");
     if (pi->lay.cfg.out_dim < 2 || pi->lay.cfg.out_dim > ILSX_MAX_NO)
       ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "a categorical policy has 2..%d actions, got %d", ILSX_MAX_NO, pi->lay.cfg.out_dim);
   }
   pi->categorical = on != 0;
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_net_set_epsilon_greedy(ilsx_net* qf, int on, float epsilon) {
+  if (!qf) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_net_set_epsilon_greedy: NULL network");
+  if (on) {
+    if (qf->lay.cfg.n_heads != 1 || qf->noise_policy || qf->categorical)
+      ILSX_FAIL(ILSX_ERR_ARG, "an epsilon-greedy policy is a single-head Mlp that is neither categorical nor a noise policy (policies/argmax.py)");
+    if (qf->lay.cfg.out_dim < 2 || qf->lay.cfg.out_dim > ILSX_MAX_NO)
+      ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "an epsilon-greedy policy has 2..%d actions, got %d", ILSX_MAX_NO, qf->lay.cfg.out_dim);
+    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_net_set_epsilon_greedy: epsilon %g is not in [0, 1]", (double)epsilon);
+  }
+  qf->egreedy = on != 0;
+  qf->epsilon = on ? epsilon : 0.0f;
   return ILSX_OK;
 }
 

@@ -1518,11 +1518,12 @@ extern "C" int ilsx_vecenv_explore(ilsx_vecenv* e, float* act, const double* eps
   return env_explore(e, act, eps, (long long)t);
 }
 
-// A policy acts in the env's kind of action space: a categorical policy writes indices (Discrete envs), every other policy writes
+// A policy acts in the env's kind of action space: a categorical or epsilon-greedy policy writes indices (Discrete envs), every other policy writes
 // continuous actions (Box envs).  Crossed, either the stepper reads an index as a force or an index lands in a continuous column.
 static int env_policy_kind_check(const ilsx_vecenv* e, const ilsx_net* pi, const char* who) {
-  if (pi && pi->categorical != (e->discrete_n > 0))
-    ILSX_FAIL(ILSX_ERR_ARG, "%s: a %s policy on an env with a %s action space", who, pi->categorical ? "categorical" : "continuous",
+  if (pi && pi->discrete() != (e->discrete_n > 0))
+    ILSX_FAIL(ILSX_ERR_ARG, "%s: a %s policy on an env with a %s action space", who,
+              pi->categorical ? "categorical" : pi->egreedy ? "epsilon-greedy" : "continuous",
               e->discrete_n > 0 ? "Discrete" : "Box");
   return ILSX_OK;
 }
@@ -1612,7 +1613,7 @@ static bool rollout_runs_groupable(ilsx_vecenv* const* envs, ilsx_net* const* pi
         e->o != e0->o || e->a != e0->a || e->ctx->device != e0->ctx->device)
       return false;
     if (memcmp(&p->lay.cfg, &p0->lay.cfg, sizeof p->lay.cfg) || p->noise_policy != p0->noise_policy || p->out_linear != p0->out_linear ||
-        (p->lay.cfg.n_heads != 2 && !p->noise_policy) || p->categorical)   // the grouped forward has no categorical head
+        (p->lay.cfg.n_heads != 2 && !p->noise_policy) || p->discrete())   // the grouped forward has no categorical / argmax head
       return false;
   }
   return true;

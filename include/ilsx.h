@@ -52,6 +52,7 @@ typedef struct ilsx_ddpg ilsx_ddpg;
 typedef struct ilsx_sacv ilsx_sacv;
 typedef struct ilsx_bc ilsx_bc;
 typedef struct ilsx_dsac ilsx_dsac;
+typedef struct ilsx_dqn ilsx_dqn;
 
 enum { ILSX_ACT_RELU = 0, ILSX_ACT_TANH = 1 };
 
@@ -164,6 +165,14 @@ int ilsx_net_set_output_linear(ilsx_net* pi, int linear);
  * from Philox on the 'ACT' stream; deterministic: the first maximal log-probability — and logp (nullable) = log pi(a|s).  eps must be NULL.
  * on = 0 clears the mark.  Set it before a trainer adopts the network; continuous trainers refuse a categorical policy. */
 int ilsx_net_set_categorical(ilsx_net* pi, int on);
+/* Marks a single-head Mlp with n = out_dim outputs (2 <= n <= 64), neither categorical nor a noise policy, as ArgmaxDiscretePolicy(qf)
+ * under EpsilonGreedy (rlkit/policies/argmax.py, rlkit/exploration_strategies/epsilon_greedy.py:21-24).  ilsx_policy_act then writes the
+ * action INDEX as a float to act[n_rows][1] — deterministic: the first maximal output (numpy argmax); otherwise one Philox call per row on
+ * the 'EGR' stream, keyed by (row, the ctx's act-call counter): u0 <= epsilon takes min(n - 1, floor(u1 * n)), a uniform action that may
+ * coincide with the greedy one, anything else the argmax.  eps and logp must be NULL.  epsilon lies in [0, 1]; calling it again changes
+ * epsilon; on = 0 clears the mark.  A marked network counts as a policy over a Discrete space (ilsx_rollout_step, ilsx_eval_rollout);
+ * ilsx_dqn_create takes it marked or not, every other trainer refuses it. */
+int ilsx_net_set_epsilon_greedy(ilsx_net* qf, int on, float epsilon);
 /* DiscretePolicy.get_log_pis (policies.py:99-100) of a categorical policy: obs[n_rows,o] -> log_pis[n_rows,n] = log_softmax of the last
  * linear layer (max-shifted; device pointers). */
 int ilsx_policy_log_pis(ilsx_net* pi, const float* obs, int n_rows, float* log_pis);
@@ -467,6 +476,33 @@ int ilsx_dsac_train_from_replay(ilsx_dsac* d, ilsx_replay* rb, int n_steps, int 
 int ilsx_dsac_get_params(ilsx_dsac* d, int which, float* dst_host, size_t n);
 int ilsx_dsac_set_params(ilsx_dsac* d, int which, const float* src_host, size_t n);
 
+/* ---------------------------------------------------------------- DQN / Double DQN
+ * Replaces rlkit/torch/algorithms/dqn/dqn.py:17-65 (ctor), :67-105 (_do_training), :107-112 (_update_target_network) and
+ * double_dqn.py:12-51.  qf: one FlattenMlp obs -> n action values, with or without the epsilon-greedy mark (the env acts with this very
+ * network).  Batches carry the action INDEX as a float in a 1-wide action column (the reference's one-hot row, as its index).
+ * v = max_j TQ(s')_j, or with double_q TQ(s')_{j*}, j* the first maximal Q(s')_j; y = r + (1 - d) * discount * v (no reward scale);
+ * loss nn.MSELoss()(Q(s)_a, y); Adam(lr = learning_rate), torch's default betas.  Targets: Polyak with tau after the Adam step, or with
+ * use_hard_updates a hard copy on the steps whose counter (tested before its increment, one per train step) is a multiple of
+ * hard_update_period — the first step copies.  Statistics are those of the first batch of a call (dqn.py:97). */
+typedef struct {
+  float discount, learning_rate, tau;
+  int32_t use_hard_updates, hard_update_period, double_q, max_batch;
+} ilsx_dqn_cfg;
+typedef struct {
+  float qf_loss;     /* mean((Q(s)_a - y)^2) */
+  float y_pred[4];   /* {Mean, Std, Max, Min} of Q(s)_a */
+} ilsx_dqn_stats;
+int ilsx_dqn_create(ilsx_ctx* ctx, const ilsx_dqn_cfg* cfg, ilsx_net* qf, ilsx_dqn** out);
+int ilsx_dqn_destroy(ilsx_dqn* dqn);
+/* device batch rows: obs[B,o], act[B,1] (indices), rew[B], done[B], nobs[B,o]; an index outside [0, n) or not integral = ILSX_ERR_ARG
+ * (the check reads the action column back to the host).  stats nullable (host). */
+int ilsx_dqn_train_step(ilsx_dqn* dqn, const float* obs, const float* act, const float* rew, const float* done, const float* nobs, int B,
+                        ilsx_dqn_stats* stats);
+int ilsx_dqn_train_from_replay(ilsx_dqn* dqn, ilsx_replay* rb, int n_steps, int B, ilsx_dqn_stats* stats);
+/* which: 0 qf, 1 target_qf; HOST flat arrays */
+int ilsx_dqn_get_params(ilsx_dqn* dqn, int which, float* dst_host, size_t n);
+int ilsx_dqn_set_params(ilsx_dqn* dqn, int which, const float* src_host, size_t n);
+
 /* ---------------------------------------------------------------- SAC with a state-value function
  * Replaces rlkit/torch/algorithms/sac/sac.py:23-68 (ctor), :70-179 (train_step), :242-243 (soft update of V).
  * cfg fields == the YAML `sac_params` keys (exp_specs/sac/sac_hopper.yaml:36-47 with run_scripts/sac_exp_script.py). */
@@ -505,6 +541,8 @@ int ilsx_ddpg_get_opt(ilsx_ddpg* ddpg, int which, float* m_host, float* v_host, 
 int ilsx_ddpg_set_opt(ilsx_ddpg* ddpg, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
 int ilsx_dsac_get_opt(ilsx_dsac* d, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);     /* 0 qf1, 1 qf2, 2 policy */
 int ilsx_dsac_set_opt(ilsx_dsac* d, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
+int ilsx_dqn_get_opt(ilsx_dqn* dqn, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);      /* 0 qf; n_train_steps = the hard-update counter */
+int ilsx_dqn_set_opt(ilsx_dqn* dqn, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
 int ilsx_sacv_get_opt(ilsx_sacv* sac, int which, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);  /* 0 qf1, 1 qf2, 2 vf, 3 policy */
 int ilsx_sacv_set_opt(ilsx_sacv* sac, int which, const float* m_host, const float* v_host, size_t n, const ilsx_opt_meta* meta);
 int ilsx_bc_get_opt(ilsx_bc* bc, float* m_host, float* v_host, size_t n, ilsx_opt_meta* meta);

@@ -1653,6 +1653,122 @@ def gen_ddpg():
     save("g31_ddpg", **rec)
 
 
+DQN_CASES = (   # (double_q, use_hard_updates, H, B, n, o, seed) — the smallest shapes that reach each path of the device step
+    (False, False, 128, 128, 2, 4, 3200),
+    (True, False, 256, 37, 5, 4, 3201),    # a ragged row tile; n is no multiple of the Philox quad
+    (False, True, 128, 64, 3, 6, 3202),
+    (True, True, 256, 64, 3, 6, 3203),
+)
+DQN_KW = dict(discount=0.99, learning_rate=1e-3, tau=0.001, hard_update_period=2)
+DQN_GAP = 1e-3   # every vector that feeds a max / argmax keeps its top two entries further apart than this: fp32 summation order cannot flip an index
+
+
+def dqn_init(seed, o, Hw, na):
+    """G32's initial parameters (regenerated by the tests from the seed: the fixture stays under the size limit).  The target net has a
+    vector of its own, not a copy of qf: a step that read the wrong net would show."""
+    rng = np.random.default_rng(seed)
+    q0, tq0 = omlp.init_mlp(rng, o, [Hw, Hw], na), omlp.init_mlp(rng, o, [Hw, Hw], na)
+    for p in (q0, tq0):
+        p[-(Hw * na + na):] *= 100.0       # head up: action values of the rewards' size, entries well apart
+    return rng, q0, tq0
+
+
+def _dqn_top2_gap(v):
+    s = np.sort(v, axis=1)
+    return s[:, -1] - s[:, -2]
+
+
+def _dqn_rows(rng, nets, rows, o):
+    """N(0,1) observation rows at which every net of `nets` has its top two outputs more than DQN_GAP apart (offending rows are redrawn)."""
+    x = rng.normal(0, 1, (rows, o)).astype(np.float32)
+    while True:
+        with torch.no_grad():
+            bad = np.zeros(rows, bool)
+            for net in nets:
+                bad |= _dqn_top2_gap(n(net(t(x)))) <= 2 * DQN_GAP   # drawn at twice the margin that is asserted
+        if not bad.any():
+            return x
+        x[bad] = rng.normal(0, 1, (int(bad.sum()), o)).astype(np.float32)
+
+
+def gen_dqn():
+    """G32: DQN._do_training (dqn/dqn.py:67-112) and DoubleDQN._do_training (double_dqn.py:12-51) with the reference's own FlattenMlp, three
+    chained steps per case of DQN_CASES.  dqn.py:13 imports rlkit.torch.torch_rl_algorithm, a module the reference no longer has (the class
+    lives in rlkit.torch.algorithms.torch_rl_algorithm): a stub module under the old name, exposing the real TorchRLAlgorithm and a
+    placeholder MetaTorchRLAlgorithm, lets the file import; the two methods then run unbound on a SimpleNamespace that carries what they
+    read (the constructor would want an env and the whole loop).  The reference takes one-hot action rows; the fixture stores their indices.
+    Recorded: batches, per-step QF Loss and Y Predictions statistics, the first step's gradient, the final qf and target_qf, the argmax
+    actions of the initial net on 64 observations, and per step the fraction of rows whose online and target argmax at s' differ.
+    Initial parameters come from dqn_init(seed); vectors of the H = 256 cases are kept at `idx` only (a fixed random subset)."""
+    import types
+    import rlkit.torch.algorithms.torch_rl_algorithm as real
+    if "rlkit.torch.torch_rl_algorithm" not in sys.modules:
+        stub = types.ModuleType("rlkit.torch.torch_rl_algorithm")
+        stub.TorchRLAlgorithm, stub.MetaTorchRLAlgorithm = real.TorchRLAlgorithm, type("MetaTorchRLAlgorithm", (), {})
+        sys.modules["rlkit.torch.torch_rl_algorithm"] = stub
+    from rlkit.torch.algorithms.dqn.dqn import DQN
+    from rlkit.torch.algorithms.dqn.double_dqn import DoubleDQN
+    from rlkit.torch.common.networks import FlattenMlp
+    steps = 3
+    rec = dict(steps=np.array(steps), kw_keys=np.array(sorted(DQN_KW)), kw_vals=np.array([DQN_KW[k] for k in sorted(DQN_KW)], np.float64))
+    for c, (double_q, hard, Hw, B, na, o, seed) in enumerate(DQN_CASES):
+        rng, q0, tq0 = dqn_init(seed, o, Hw, na)
+        assert not np.array_equal(q0, tq0)
+        qf, tqf = (FlattenMlp(hidden_sizes=[Hw, Hw], input_size=o, output_size=na) for _ in range(2))
+        set_flat(qf, q0), set_flat(tqf, tq0)
+        cur = {}
+        ns = types.SimpleNamespace(qf=qf, target_qf=tqf, qf_optimizer=torch.optim.Adam(qf.parameters(), lr=DQN_KW["learning_rate"]),
+                                   qf_criterion=torch.nn.MSELoss(), discount=DQN_KW["discount"], tau=DQN_KW["tau"], use_hard_updates=hard,
+                                   hard_update_period=DQN_KW["hard_update_period"], _n_train_steps_total=0, eval_statistics=None,
+                                   get_batch=lambda **kk: cur["batch"])
+        ns._update_target_network = types.MethodType(DQN._update_target_network, ns)
+        grads = {}
+        _hook_grads(grads, ns.qf_optimizer, "q", qf)
+        pre = f"c{c}_"
+        idx = np.arange(q0.size) if Hw == 128 else np.sort(rng.choice(q0.size, 4096, replace=False))
+        rec.update({pre + "shape": np.array([int(double_q), int(hard), Hw, B, na, o, seed]), pre + "idx": idx.astype(np.int64)})
+        am_obs = _dqn_rows(rng, (qf,), 64, o)
+        with torch.no_grad():
+            rec[pre + "am_obs"], rec[pre + "argmax"] = am_obs, n(qf(t(am_obs))).argmax(1).astype(np.int64)
+        differ = []
+        for s in range(steps):
+            s2 = _dqn_rows(rng, (qf, tqf), B, o)
+            batch = dict(observations=rng.normal(0, 1, (B, o)).astype(np.float32), actions=rng.integers(0, na, (B, 1)).astype(np.float32),
+                         rewards=rng.normal(0, 1, (B, 1)).astype(np.float32), terminals=(rng.random((B, 1)) < 0.1).astype(np.float32),
+                         next_observations=s2)
+            assert set(np.unique(batch["terminals"])) == {0.0, 1.0}, (c, s)    # both values: the (1 - d) factor is exercised both ways
+            with torch.no_grad():
+                qn, tq = n(qf(t(s2))), n(tqf(t(s2)))
+            assert min(_dqn_top2_gap(qn).min(), _dqn_top2_gap(tq).min()) > DQN_GAP, (c, s)
+            differ.append(float((qn.argmax(1) != tq.argmax(1)).mean()))
+            onehot = np.eye(na, dtype=np.float32)[batch["actions"][:, 0].astype(np.int64)]
+            cur["batch"] = {k: t(v) for k, v in dict(batch, actions=onehot).items()}
+            before = get_flat(tqf)
+            ns.eval_statistics = None
+            (DoubleDQN if double_q else DQN)._do_training(ns)
+            if hard:   # counters 0, 1, 2 at period 2: steps 0 and 2 copy the stepped net, step 1 leaves the target alone
+                assert ns._n_train_steps_total == s
+                if s == 1:
+                    assert np.array_equal(get_flat(tqf), before) and np.abs(get_flat(tqf) - get_flat(qf)).max() > 1e-4
+                else:
+                    assert np.array_equal(get_flat(tqf), get_flat(qf))
+            ns._n_train_steps_total += 1   # base_algorithm.py:296-298: after the training call
+            st = ns.eval_statistics
+            rec.update({f"{pre}s{s}_{k}": v for k, v in batch.items()})
+            rec[f"{pre}s{s}_qf_loss"] = np.float32(st["QF Loss"])
+            rec[f"{pre}s{s}_y_pred"] = np.array([st["Y Predictions " + k] for k in ("Mean", "Std", "Max", "Min")], np.float32)
+            if s == 0:
+                rec[pre + "grad_q"] = grads["q"][idx]
+        # Double DQN must not pass for DQN: the two nets pick different actions at s' in at least a quarter of the rows — of every batch with
+        # soft targets, of the first batch with hard ones (after the copy of step 0 the target IS the online net of step 1 and one Adam
+        # step behind the one of step 2: there the two rules agree by construction, whatever the inputs)
+        if double_q:
+            assert min(differ if not hard else differ[:1]) >= 0.25, (c, differ)
+        rec[pre + "argmax_differ"] = np.array(differ)
+        rec.update({pre + "q": get_flat(qf)[idx], pre + "tq": get_flat(tqf)[idx]})
+    save("g32_dqn", **rec)
+
+
 def gen_gcsl():
     """G29: GCSL (gcsl/gcsl.py, relabel_horizon_replay_buffer.py) with the reference's own trainer, buffer, policies and DiscretEnv.
     buf_*: HindsightHorizonReplayBuffer.random_batch on point-reach-shaped paths in a 40-slot ring (the last path wraps it): the indices it
@@ -1814,7 +1930,7 @@ GROUPS = dict(mlp=gen_mlp, mlp_unequal=gen_mlp_unequal, head=gen_head, sac_alpha
               disc=gen_disc, disc_bn=gen_disc_bn, disc_blocks=gen_disc_blocks, disc_branches=gen_disc_branches, replay=gen_replay,
               replay_trajs=gen_replay_trajs, her=gen_her, absorbing=gen_absorbing, bc=gen_bc, rms=gen_rms_actionmap, terminals=gen_terminals,
               eval_stats=gen_eval_stats, variants=gen_variants, logger_csv=gen_logger_csv, logdir=gen_logdir, mbpo=gen_mbpo,
-              discrete_sac=gen_discrete_sac, gcsl=gen_gcsl, ddpg=gen_ddpg)
+              discrete_sac=gen_discrete_sac, gcsl=gen_gcsl, ddpg=gen_ddpg, dqn=gen_dqn)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GROUPS)
