@@ -382,6 +382,7 @@ PROTOTYPES = {
     "ilsx_sac_debug_last_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "ilsx_sac_phase_state": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ilsx_sac_debug_break_phase": (C.c_int, [vp]),
+    "ilsx_debug_phase_static_ok": (C.c_int, [C.c_int] * 10),
     "ilsx_sac_set_alpha_opt": (C.c_int, [vp, C.c_double, C.c_double, C.c_int64, C.c_uint64]),
     "ilsx_bnn_create": (C.c_int, [vp, C.POINTER(BnnCfg), C.POINTER(vp)]),
     "ilsx_bnn_destroy": (C.c_int, [vp]),

@@ -10,6 +10,14 @@
 // `T` (FwdTask), `GP` (const FwdGroup*, GRP only), `bx` (tile index in grid units), `cs` (column slice), `first_task` (this task's lead
 // slice publishes the finished policy head), `smem` (dynamic LDS); the macros XCH_HOOK_STAGE (before the input rows are staged) and
 // XCH_HOOK_FIN (before the producing policy's head is finished): empty in an ordinary launch, the wait for the previous stage in a phase kernel.
+// `constexpr int FIN_CT`: 0 = everything about the input rows and the policy epilogue is decided at run time (the wrappers).  -1 = a stage of
+// a phase kernel whose inputs carry no policy epilogue (the first stages: A.fin_on is 0 there, launch_phase_a / _c refuse anything else).
+// 1 = phase A's target critics: rows read from T.x0 (no replay draw), every task's action columns the tanh-Gaussian policy's output in CS
+// slabs, 16 a <= NTH, noise drawn in the kernel (launch_phase_a refuses anything else).  Then everything that does not depend on the
+// awaited policy slices comes BEFORE XCH_HOOK_STAGE: the descriptor fields (held in scalar registers), the noise of pi(s') — the same
+// philox_normal4 call and arguments — and the staging loop's index arithmetic; behind the wait: the rows' loads, the head partials
+// (requested back to back), the squash.  Same expressions, same order.
+  constexpr bool FINS = FIN_CT > 0;
   constexpr int NTH = 4 * H / CS, NWV = NTH / 64, NC = H / 16, SLW = H / CS, NCS = SLW / 16;
   constexpr int NT0 = PH == 1 ? 1 : CS;   // layer-0 column tiles per wave
   constexpr int LDH = H + ILSX_LDS_PAD, LDSL = SLW + ILSX_LDS_PAD;
@@ -18,7 +26,9 @@
   static_assert(MT == 1 || MT == 2 || MT == 4, "macro tile = 1, 2 or 4 row tiles");
   const DevScalars* scal = GRP ? GP->scal : A.scal;
   const NetView& N = T.net;
-  const int KP = N.KP, LDX = KP + ILSX_LDS_PAD, NO = N.NO, NCH0 = KP >> 4, NOT = (NO + 15) >> 4;
+  int KP = N.KP;
+  if constexpr (FINS) XCH_PIN(KP);
+  const int LDX = KP + ILSX_LDS_PAD, NO = N.NO, NCH0 = KP >> 4, NOT = (NO + 15) >> 4;
   float* xs = smem;                 // [MR][LDX]
   float* h0 = xs + (PH == 2 && MT > 1 ? 0 : MR * LDX);        // [MR][LDH]   layer-0 activations, all H columns   (macro tiles: the regions a phase
   float* hs = h0 + (PH == 1 && MT > 1 ? 0 : MR * LDH);        // [MR][LDSL]  this slice of the layer-1 activations  does not touch take no LDS, see fwd_split_lds_bytes)
@@ -75,16 +85,104 @@
 #ifdef XCH_FINE_DBG
   ILSX_STAMP_SYNC(XCH_FINE_DBG, 6);   // the weights have arrived
 #endif
-  const bool fin = (GRP ? GP->fin_on : A.fin_on) != 0 && !T.no_fin && T.d1 > 0;
+  const bool fin = FIN_CT >= 0 && (GRP ? GP->fin_on : A.fin_on) != 0 && !T.no_fin && T.d1 > 0;
   const GatherSpec& G = GRP ? GP->gather : A.gather;
   for (int rt = 0; rt < RT; ++rt) {
   const int r0 = ((bx >> A.xs) * RT + rt) * MR;
   if (r0 >= rows) break;   // workgroup-uniform
   const bool full_tile = r0 + MR <= rows;   // workgroup-uniform: every row of the (macro) tile is a batch row
   bool fin_logp = false;
+  int sf_a = 0; float* sf_logp = nullptr;   // FINS: the epilogue's action count and (publishing slice) log-pi destination
   if constexpr (PH != 2) {
 #pragma unroll
   for (int i = 0; i < NT0; ++i) b0[i] = b0first[i];
+  if constexpr (FINS) {
+    static_assert(PH == 0 && MT == 1 && GRP == 0 && XCH, "the static epilogue is phase A's target-critic stage");
+    const PolicyFinishArgs& FP = A.fin;   // (`P` is the phase kernel's own block, which the hook names)
+    const bool pub = lead && first_task;
+    int sf_d0 = T.d0, sf_s0 = T.s0, sf_ps = FP.part_stride;
+    const float* sf_x0 = T.x0; const float* sf_part = FP.part; float* sf_xsave = lead ? T.xsave : nullptr;
+    float* sf_raw = pub ? FP.raw : nullptr; float* sf_action = pub ? FP.action : nullptr; float* sf_epss = pub ? FP.eps_save : nullptr;
+    sf_a = FP.a; sf_logp = pub ? FP.logp : nullptr;
+    XCH_PIN(sf_d0); XCH_PIN(sf_s0); XCH_PIN(sf_ps); XCH_PIN(sf_x0); XCH_PIN(sf_part); XCH_PIN(sf_xsave);
+    XCH_PIN(sf_raw); XCH_PIN(sf_action); XCH_PIN(sf_epss); XCH_PIN(sf_a); XCH_PIN(sf_logp);
+    const int a = sf_a, NOp = 2 * a;
+    // the epilogue element (row, action) this thread owns, and its noise
+    const int fr = tid / a, fj = tid - fr * a, fgr = r0 + fr;
+    const bool fon = tid < MR * a && fgr < rows;
+    float fep = 0.0f;
+    if (fon) {   // (drawn in the kernel: launch_phase_a refuses explicit noise, which only one-launch-per-stage steps take)
+      const unsigned long long fstep = FP.scal ? (FP.use_gather_step ? FP.scal->gather_step : FP.scal->step) : FP.step_host;
+      float z4[4];
+      philox_normal4(FP.seed, fstep, FP.rng_stream, fgr, fj >> 2, z4);
+      const int q = fj & 3;
+      fep = q == 0 ? z4[0] : q == 1 ? z4[1] : q == 2 ? z4[2] : z4[3];
+    }
+    // the staged elements of the first STG trips (KP <= 32: all of them): row, column, what to do with it
+    constexpr int STG = 2;
+    int sr[STG], sk[STG];
+#pragma unroll
+    for (int t = 0; t < STG; ++t) { const int e = tid + t * NTH; sr[t] = e / KP; sk[t] = e - sr[t] * KP; }
+    XCH_HOOK_STAGE
+    {
+      float sv[STG];
+#pragma unroll
+      for (int t = 0; t < STG; ++t) {
+        const int gr = r0 + sr[t];
+        sv[t] = (tid + t * NTH < MR * KP && gr < rows && sk[t] < sf_d0) ? xg<true>(sf_x0)[(size_t)gr * sf_s0 + sk[t]] : 0.0f;
+      }
+      // the CS head partials: all requested before any is summed
+      float pm[4], pl[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const size_t at = ((size_t)(c < CS ? c : 0) * sf_ps + (fon ? fgr : r0)) * NOp + fj;
+        pm[c] = fon ? ldx<XCH>(xg<true>(sf_part + at)) : 0.0f;
+        pl[c] = fon ? ldx<XCH>(xg<true>(sf_part + at + a)) : 0.0f;
+      }
+#pragma unroll
+      for (int t = 0; t < STG; ++t) {
+        const int gr = r0 + sr[t];
+        const bool act_col = sk[t] >= sf_d0 && sk[t] < sf_d0 + a;
+        if (tid + t * NTH < MR * KP && !act_col) {   // the action columns: filled by the epilogue below
+          if (sf_xsave && gr < rows) xg<true>(sf_xsave)[(size_t)gr * KP + sk[t]] = sv[t];
+          xs[sr[t] * LDX + sk[t]] = sv[t];
+        }
+      }
+      for (int e = tid + STG * NTH; e < MR * KP; e += NTH) {   // wider inputs: the further trips
+        const int r = e / KP, k = e - r * KP, gr = r0 + r;
+        if (k >= sf_d0 && k < sf_d0 + a) continue;
+        float v = 0.0f;
+        if (gr < rows) {
+          if (k < sf_d0) v = xg<true>(sf_x0)[(size_t)gr * sf_s0 + k];
+          if (sf_xsave) xg<true>(sf_xsave)[(size_t)gr * KP + k] = v;
+        }
+        xs[r * LDX + k] = v;
+      }
+      // combine the head partials, squash (policies.py:262-283, distributions.py:23-28,43-50,74-97); slice 0 of task 0 publishes
+      float* lp3 = red;   // [MR][32][3] log-prob contributions (quad, log_std, jacobian)
+      float act = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+      if (fon) {
+        float mu = 0.f, lsr = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { mu += c < CS ? pm[c] : 0.0f; lsr += c < CS ? pl[c] : 0.0f; }   // slab order
+        const float ls = fminf(fmaxf(lsr, LOG_SIG_MIN), LOG_SIG_MAX);
+        const float sd = expf(ls);
+        const float z = fep * sd + mu;
+        act = tanhf(z);
+        const float dm = mu - z;
+        c0 = dm * dm / expf(2.0f * ls); c1 = ls; c2 = logf(1.0f - act * act + TANH_EPS);
+        if (sf_raw) { stx<XCH>(xg<true>(sf_raw + (size_t)fgr * NOp + fj), mu); stx<XCH>(xg<true>(sf_raw + (size_t)fgr * NOp + a + fj), lsr); }
+        if (sf_xsave) xg<true>(sf_xsave)[(size_t)fgr * KP + sf_d0 + fj] = act;
+        if (sf_action) stx<XCH>(xg<true>(sf_action + (size_t)fgr * a + fj), act);
+        if (sf_epss) stx<XCH>(xg<true>(sf_epss + (size_t)fgr * a + fj), fep);
+      }
+      if (tid < MR * a) {
+        xs[fr * LDX + sf_d0 + fj] = act;
+        lp3[(fr * 32 + fj) * 3 + 0] = c0; lp3[(fr * 32 + fj) * 3 + 1] = c1; lp3[(fr * 32 + fj) * 3 + 2] = c2;
+      }
+      fin_logp = sf_logp != nullptr;
+    }
+  } else {
   XCH_HOOK_STAGE
   if constexpr (PH == 0) {   // narrow inputs (the one-launch form): one element per thread, the row's index drawn where it is used
     long long* ridx0 = reinterpret_cast<long long*>(hs);   // hs is not live before layer 1
@@ -272,6 +370,7 @@
     }
     fin_logp = pub && P.logp && !det;
   }
+  }  // !FINS
   }  // PH != 2
   else {   // PH == 2: layer-0 activations of the tile, as the layer-0 launch left them
     const float* hsrc = T.hsave[0];
@@ -282,13 +381,14 @@
     }
   }
   lds_barrier();
-  ILSX_STAMP(A.dbg, 1);
+  XCH_STAMP(1);
   if (fin_logp && tid < MR && r0 + tid < rows) {   // log pi of the tile's rows from the staged contributions: after the tile's ONE
     const PolicyFinishArgs& P = GRP ? GP->fin : A.fin;   // barrier instead of behind a barrier of its own (`red` is next written two
     float q = 0.f, l = 0.f, jc = 0.f;                    // barriers from here)
-    const int LPS = MT == 1 ? 32 : P.a;
-    for (int j = 0; j < P.a; ++j) { q += red[(tid * LPS + j) * 3]; l += red[(tid * LPS + j) * 3 + 1]; jc += red[(tid * LPS + j) * 3 + 2]; }
-    stx<XCH>(P.logp + r0 + tid, -0.5f * q - (l + HALF_LOG_2PI) - jc);
+    const int pa = FINS ? sf_a : P.a;
+    const int LPS = MT == 1 ? 32 : pa;
+    for (int j = 0; j < pa; ++j) { q += red[(tid * LPS + j) * 3]; l += red[(tid * LPS + j) * 3 + 1]; jc += red[(tid * LPS + j) * 3 + 2]; }
+    stx<XCH>(xg<FINS>((FINS ? sf_logp : P.logp) + r0 + tid), -0.5f * q - (l + HALF_LOG_2PI) - jc);
   }
   // ---- layer 0: CS column tiles per wave, full width (PH 0) ; this slice's own tile (PH 1)
   if constexpr (PH == 1) {
@@ -397,7 +497,7 @@
     continue;
   }
   if constexpr (PH == 0) lds_barrier();
-  ILSX_STAMP(A.dbg, 2);
+  XCH_STAMP(2);
   // ---- layer 1, this slice: straight out of registers
   if constexpr (LATEW) {
     const float* wp = N.base + N.off_W[1] + (size_t)(cs * NWV + wave) * NC * 256 + 4 * lane;
@@ -442,7 +542,7 @@
     }
   }
   lds_barrier();
-  ILSX_STAMP(A.dbg, 3);
+  XCH_STAMP(3);
   // ---- head partial sums over this column slice on the matrix pipe: wave w contracts k16 chunk w of the
   //      slice for every 16-output tile, the NWV partial tiles are summed through LDS
 #pragma unroll

@@ -176,6 +176,9 @@ struct PhaseConst {
 int phase_const_alloc(int device);            // a free slot of that device's tables, or -1
 void phase_const_prepare(ilsx_ctx* ctx, PhaseConst* ct);   // first use: take a slot (once; none free = stays without)
 void phase_const_free(int device, int slot);
+// what the phase kernels fix at compile time about their stages' descriptors (ilsx_core.hip); launch_phase_a / _c refuse the rest
+bool phase_a_static_ok(const PhaseAArgs& P, int H, int cs);
+bool phase_c_static_ok(const PhaseCArgs& P, int H, int cs);
 int launch_phase_a(ilsx_ctx* ctx, const PhaseAArgs& P, int H, int act, int KPmax, int cs, PhaseConst* ct = nullptr, unsigned long long key = 0, bool upload_only = false);
 int launch_phase_c(ilsx_ctx* ctx, const PhaseCArgs& P, int H, int act, int KPmax, int cs, PhaseConst* ct = nullptr, unsigned long long key = 0, bool upload_only = false);
 int device_cus(ilsx_ctx* ctx);   // compute units of the context's device

@@ -620,12 +620,67 @@ static bool phase_const_ready(ilsx_ctx* ctx, PhaseConst* ct, const Blk& blk, uns
   return true;
 }
 
+// What the phase kernels decide at COMPILE time about their stages (the static heads of bwd_split_tile.inc, the static epilogue of
+// fwd_split_tile.inc): the loss kind of each backward stage, one head output per critic, every split per-row scalar in exactly `cs` slabs,
+// the target critics' inputs = rows of T.x0 + the tanh-Gaussian policy's action in `cs` slabs, one epilogue element per thread, noise drawn
+// in the kernel (explicit noise only ever reaches one-launch-per-stage steps) and keyed by the replay-draw counter (read before the wait:
+// the step counter moves inside the launch); phase C's stage 1 finishes no policy (pi(s) was finished in phase A: the policy's loss head
+// reads raw head, noise and action before its wait).  A descriptor that differs is refused.
+bool phase_a_static_ok(const PhaseAArgs& P, int H, int cs) {
+  const int nth = 4 * H / cs;
+  for (int i = 0; i < 2; ++i) {
+    const BwdTask& t = P.b1.t[i];
+    if (t.loss != LOSS_SAC_CRITIC || t.net.NO != 1 || t.q.cs != cs || t.tq1.cs != cs || t.tq2.cs != cs) return false;
+  }
+  if (P.f1.fin_on) return false;
+  const FwdArgs& f = P.f2;
+  if (f.gather.on || !f.fin_on || f.fin.head != HEAD_TANH_SAMPLE || f.fin.cs != cs || f.fin.a < 1 || 16 * f.fin.a > nth) return false;
+  if (f.fin.scal && !f.fin.use_gather_step) return false;
+  if (f.fin.eps || P.fin_pi.eps) return false;
+  for (int i = 0; i < 2; ++i) {
+    const FwdTask& t = f.t[i];
+    if (t.no_fin || t.d1 != f.fin.a || !t.x0) return false;
+  }
+  return true;
+}
+bool phase_c_static_ok(const PhaseCArgs& P, int H, int cs) {
+  (void)H;
+  if (P.f3.fin_on) return false;
+  for (int i = 0; i < 2; ++i) {
+    const BwdTask& t = P.b2.t[i];
+    if (t.loss != LOSS_SAC_ACTORQ || t.net.NO != 1 || t.q1n.cs != cs || t.q2n.cs != cs) return false;
+  }
+  const BwdTask& t = P.b3.t[0];
+  return t.loss == LOSS_SAC_POLICY && t.net.NO >= 2 && t.net.NO % 2 == 0 && P.b3.ga_parts == cs;
+}
+// test aid (no device needed): would a phase launch take descriptors with these properties?  stage: 0 = phase A, 1 = phase C
+extern "C" int ilsx_debug_phase_static_ok(int stage, int loss_critic, int loss_policy, int no_critic, int slabs, int fin_head, int a, int H, int cs, int flags) {
+  if (stage == 0) {
+    PhaseAArgs P; memset(&P, 0, sizeof P);
+    static const float x = 0.0f;
+    for (int i = 0; i < 2; ++i) {
+      BwdTask& t = P.b1.t[i];
+      t.loss = loss_critic; t.net.NO = no_critic; t.q.cs = t.tq1.cs = t.tq2.cs = slabs;
+      P.f2.t[i].d1 = a; P.f2.t[i].x0 = &x;
+    }
+    P.f2.fin_on = 1; P.f2.fin.head = fin_head; P.f2.fin.cs = slabs; P.f2.fin.a = a;
+    if (flags & 1) P.f2.fin.eps = &x;   // explicit noise
+    return phase_a_static_ok(P, H, cs) ? 1 : 0;
+  }
+  PhaseCArgs P; memset(&P, 0, sizeof P);
+  for (int i = 0; i < 2; ++i) { BwdTask& t = P.b2.t[i]; t.loss = loss_critic; t.net.NO = no_critic; t.q1n.cs = t.q2n.cs = slabs; }
+  P.b3.t[0].loss = loss_policy; P.b3.t[0].net.NO = 2 * a; P.b3.ga_parts = slabs;
+  if (flags & 2) P.f3.fin_on = 1;   // stage 1 finishes a policy
+  return phase_c_static_ok(P, H, cs) ? 1 : 0;
+}
+
 int launch_phase_a(ilsx_ctx* ctx, const PhaseAArgs& P0, int H, int act, int KPmax, int cs, PhaseConst* ct, unsigned long long key, bool upload_only) {
   PhaseAArgs P = P0;
   P.f1.xs = P.f2.xs = P.b1.xs = 0; P.f1.rt = P.f2.rt = 1;
   P.f1.dbg = P.f2.dbg = nullptr; P.b1.dbg = nullptr;
   P.dbg = upload_only ? nullptr : ctx->dbg_next();   // (a dry pass takes no slab of the trace buffer)
   if (P.b1.ga_parts < 1) P.b1.ga_parts = 1;
+  if (!phase_a_static_ok(P, H, cs)) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "launch_phase_a: the stages' descriptors are not what the phase kernel is compiled for (loss kind, head, slab count)");
   const int tiles = (P.f1.rows + 15) / 16;
   dim3 grid((tiles + 7) & ~7, P.own_rows ? 7 : 5, cs), block(4 * H / cs);   // y: the four tasks of stage 1, the bookkeeping row, the target critics' own rows
   const size_t lds = phase_lds_bytes(H, KPmax, cs);
@@ -654,6 +709,7 @@ int launch_phase_c(ilsx_ctx* ctx, const PhaseCArgs& P0, int H, int act, int KPma
   P.dbg = upload_only ? nullptr : ctx->dbg_next();
   if (P.b2.ga_parts < 1) P.b2.ga_parts = 1;
   if (P.b3.ga_parts < 1) P.b3.ga_parts = 1;
+  if (!phase_c_static_ok(P, H, cs)) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "launch_phase_c: the stages' descriptors are not what the phase kernel is compiled for (loss kind, head, slab count)");
   const int tiles = (P.f3.rows + 15) / 16;
   dim3 grid((tiles + 7) & ~7, 4, cs), block(4 * H / cs);   // y: Q1, Q2, the policy's backward, the bookkeeping row
   const size_t lds = phase_lds_bytes(H, KPmax, cs);

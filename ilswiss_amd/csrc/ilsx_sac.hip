@@ -96,6 +96,8 @@ struct ilsx_sac {
   bool phase_broken = false;         // a timeout was seen once: stay on the 8-launch path
   bool phase_last = false;           // the last window of steps ran on the phase kernels
   bool debug_break = false;          // ilsx_sac_debug_break_phase
+  bool phase_check_only = false;     // with phase_args_only: the blocks are only held against what the kernels are compiled for, nothing is uploaded
+  int static_heads = -1;             // sac_static_heads_ok: -1 = not yet asked, else its answer
   int phase_fallbacks = 0;           // windows rolled back and re-run (ilsx_sac_phase_state)
   float* vote = nullptr;             // split run: the ranks' agreement on a roll-back (sac_phase_check), one device float
   bool snap_valid = false;           // the checkpoint belongs to the window now running (set by sac_snapshot_take, cleared when the window ends)
@@ -539,7 +541,7 @@ static int sac_critic_backward(ilsx_sac* s) {
         sac_policy_fin(s, Fz, eps2, s->rng_stream + 1, true, w.an, w.logp, w.ppart2);
         PA.fin_pi = Fz.fin; PA.fin_pi.use_gather_step = 1; PA.fin_pi_on = 1;
       }
-      ILSX_TRY(launch_phase_a(s->ctx, PA, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, s->no_ct ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
+      ILSX_TRY(launch_phase_a(s->ctx, PA, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, (s->no_ct || s->phase_check_only) ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
       if (s->phase_args_only) return ILSX_OK;
     } else {
       ILSX_TRY(sac_bwd(s, A, H, act, cs));
@@ -616,7 +618,7 @@ static int sac_actor_backward(ilsx_sac* s) {
       else {   // split run: this rank's alpha-gradient partial lands in the arena's slot before the actor all-reduce (the tail is deferred)
         PC.aslot = s->G + 2 * s->nq + s->np; PC.aslot_logp = w.logp; PC.aslot_B = B; PC.aslot_te = s->target_entropy; PC.aslot_invB = sac_inv_B(s);
       }
-      ILSX_TRY(launch_phase_c(s->ctx, PC, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, s->no_ct ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
+      ILSX_TRY(launch_phase_c(s->ctx, PC, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, (s->no_ct || s->phase_check_only) ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
       if (s->phase_args_only) return ILSX_OK;
     } else {
       ILSX_TRY(sac_bwd(s, A, H, act, cs));
@@ -924,14 +926,33 @@ extern "C" int ilsx_sac_train_step(ilsx_sac* s, const float* obs, const float* a
 
 // The merged phase kernels need: the column-split path on narrow inputs, the fused in-kernel replay draw, the deferred tail, no
 // gradient all-reduce between the phases, no per-workgroup stamps, and every workgroup of a phase launch resident at once.
+// And the stages' descriptors are what the phase kernels are compiled for (static heads: loss kind per stage, one head output per critic,
+// slab counts, the tanh-Gaussian epilogue with one element per thread, no explicit noise).  Asked once per agent, of the blocks themselves:
+// a dry pass builds them as a step would and launch_phase_a / _c hold them against phase_a_static_ok / phase_c_static_ok (nothing is
+// uploaded or launched).  An agent whose blocks are refused stays on one launch per stage.  (Asked last: the dry pass needs a shape the
+// phase kernels exist for.)
+static bool sac_static_heads_ok(ilsx_sac* s) {
+  if (s->static_heads < 0) {
+    const bool phase_now = s->phase_now, fuse_now = s->fuse_now, eps_explicit = s->eps_explicit;
+    ilsx_replay* const rb = s->gather_rb;
+    s->gather_rb = nullptr; s->phase_now = true; s->fuse_now = !sac_is_split(s); s->eps_explicit = false;
+    s->phase_args_only = s->phase_check_only = true;
+    int rc = sac_critic_backward(s);
+    if (rc == ILSX_OK) rc = sac_actor_backward(s);
+    s->phase_args_only = s->phase_check_only = false;
+    s->gather_rb = rb; s->phase_now = phase_now; s->fuse_now = fuse_now; s->eps_explicit = eps_explicit;
+    s->static_heads = rc == ILSX_OK ? 1 : 0;
+  }
+  return s->static_heads == 1;
+}
 static bool sac_phase_ok(ilsx_sac* s, int B) {
   const bool off = getenv("ILSX_NO_PHASE") != nullptr;
   return !off && !s->phase_broken && s->cs > 1 && !s->h0scr && !s->col && s->defer_tail &&
-         s->ctx->xcd_shift == 0 && phase_fits(s->ctx, B, s->Lq.cfg.hidden, s->cs, 4);   // (a split run defers its tail only for the phase kernels: sac_defer_begin)
+         s->ctx->xcd_shift == 0 && phase_fits(s->ctx, B, s->Lq.cfg.hidden, s->cs, 4) && sac_static_heads_ok(s);   // (a split run defers its tail only for the phase kernels: sac_defer_begin)
 }
 static bool sac_phase_possible(ilsx_sac* s, int B) {   // as sac_phase_ok, for the state a train_from_replay call ran in (defer_tail already cleared)
   const bool off = getenv("ILSX_NO_PHASE") != nullptr;   // read per call: tests switch between the two paths in one process
-  return !off && s->cs > 1 && !s->h0scr && phase_fits(s->ctx, B, s->Lq.cfg.hidden, s->cs, 4);
+  return !off && s->cs > 1 && !s->h0scr && phase_fits(s->ctx, B, s->Lq.cfg.hidden, s->cs, 4) && sac_static_heads_ok(s);
 }
 // Checkpoint / roll-back of everything a gradient step mutates — device scalars (log alpha and its moments, step / Philox counters,
 // Adam scalars), parameters + targets, gradients, Adam moments: one contiguous range of the agent's slab (ilsx_sac_create adds them

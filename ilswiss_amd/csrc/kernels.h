@@ -319,8 +319,11 @@ static_assert(offsetof(FwdTask, step_t) == offsetof(FwdTask, g0_off) && sizeof(f
 // __threadfence 9 us, every exchanged word as an agent-scope atomic (sc1: served past the L2) 1.3 us — but each such load is a trip to
 // the fabric and the stage bodies ran 3.5 us slower — this way 0.95 us; a kernel boundary is 2.7 us plus a cold prologue.
 // ldx / stx mark the exchanged accesses (X = the access happens inside a phase kernel); they compile to the ordinary access.
+typedef __attribute__((address_space(1))) float gfloat;   // a float known to live in global memory (xg below)
 template <bool X> __device__ __forceinline__ float ldx(const float* p) { return *p; }
 template <bool X> __device__ __forceinline__ void stx(float* p, float v) { *p = v; }
+template <bool X> __device__ __forceinline__ float ldx(const gfloat* p) { return *p; }
+template <bool X> __device__ __forceinline__ void stx(gfloat* p, float v) { *p = v; }
 // a value another workgroup of this launch wrote to a uniform address: a vector load past every cache (a plain load of a uniform
 // address becomes a scalar load, and the scalar cache is not dropped by buffer_inv sc0)
 template <bool X> __device__ __forceinline__ float ldx_uniform(const float* p) {
@@ -344,6 +347,28 @@ struct PartVal {
     return s;
   }
 };
+// the same sum with the slab count a compile-time constant and pointer / stride in the caller's registers (static heads, bwd_split_tile.inc)
+template <bool X, int CSV>
+__device__ __forceinline__ float partval_get(const float* pp, int stride, int r) {
+  static_assert(CSV >= 1 && CSV <= 4, "cs <= 4");
+  const gfloat* p = (const gfloat*)pp;   // (see xg below)
+  const float v0 = ldx<X>(p + r);
+  const float v1 = CSV > 1 ? ldx<X>(p + (size_t)stride + r) : 0.0f;
+  const float v2 = CSV > 2 ? ldx<X>(p + (size_t)2 * stride + r) : 0.0f;
+  const float v3 = CSV > 3 ? ldx<X>(p + (size_t)3 * stride + r) : 0.0f;
+  float s = v0;
+  if (CSV > 1) s += v1;
+  if (CSV > 2) s += v2;
+  if (CSV > 3) s += v3;
+  return s;
+}
+// a workgroup-uniform value read ahead of a wait stays in a scalar register across it (without this the compiler re-reads a field of
+// the constant table where it is used: a scalar load and a wait for it behind the hand-off)
+#define XCH_PIN(v) asm volatile("" : "+s"(v))
+// A pinned POINTER has lost its provenance too: an access through it would be a FLAT one (counted against the LDS counter as well, and
+// waited for like an LDS access).  xg<true>(p) says again that p points to global memory; xg<false> is the identity (the wrappers' code).
+template <bool G> __device__ __forceinline__ auto xg(const float* p) { if constexpr (G) return (const gfloat*)p; else return p; }
+template <bool G> __device__ __forceinline__ auto xg(float* p) { if constexpr (G) return (gfloat*)p; else return p; }
 // Combine the CS head partials of a tanh-Gaussian policy and run its epilogue (policies.py:262-307):
 // one thread per row.  Launched right after k_mlp2_fwd_split for policy tasks.
 struct PolicyFinishArgs {
@@ -705,34 +730,36 @@ struct BwdArgs {
 
 // dL/d(head output j) of row gr for the loss functor of task T (shared by the generic and the column-split
 // backward kernels).
-template <bool X = false>
+// LOSS_CT >= 0: the loss kind is the including stage's compile-time choice (the merged phase kernels run one kind per stage); -1 = T.loss.
+template <bool X = false, int LOSS_CT = -1>
 __device__ __forceinline__ float bwd_head_grad(const BwdTask& T, const BwdArgs& A, int gr, int j, int NO) {
   float d = 0.0f;
   const DevScalars* scal = T.scal ? T.scal : A.scal;
-  if (T.loss == LOSS_GIVEN) {
+#define BHG_LOSS (LOSS_CT >= 0 ? LOSS_CT : T.loss)   // (read in place: the run-time form compiles as it did before the parameter)
+  if (BHG_LOSS == LOSS_GIVEN) {
     d = T.given[(size_t)gr * NO + j];
-  } else if (T.loss == LOSS_SAC_CRITIC) {
+  } else if (BHG_LOSS == LOSS_SAC_CRITIC) {
     // sac_alpha.py:110-123: y = r + (1-d)*gamma*(min(TQ1,TQ2) - alpha*logpi'); dL/dq = (q-y)/B
     const float alpha = ldx_uniform<X>(&scal->alpha);
     const float r = A.reward_scale * ldx<X>(T.rew + gr);
     const float y = r + (1.0f - ldx<X>(T.done + gr)) * A.gamma * (fminf(T.tq1.get<X>(gr), T.tq2.get<X>(gr)) - alpha * ldx<X>(T.logp_next + gr));
     d = (T.q.get<X>(gr) - y) * A.inv_B;
-  } else if (T.loss == LOSS_SAC_ACTORQ) {
+  } else if (BHG_LOSS == LOSS_SAC_ACTORQ) {
     // sac_alpha.py:144-148: -mean(min(Q1,Q2)); torch.minimum splits ties evenly
     const float a1 = T.q1n.get<X>(gr), a2 = T.q2n.get<X>(gr);
     const float w1 = a1 < a2 ? 1.0f : (a1 == a2 ? 0.5f : 0.0f);
     d = -(T.which == 0 ? w1 : 1.0f - w1) * A.inv_B;
-  } else if (T.loss == LOSS_TD_CRITIC) {
+  } else if (BHG_LOSS == LOSS_TD_CRITIC) {
     // td3.py:84-99 (coef 2: plain MSE) / sac.py:93-105 (coef 1: half MSE, tq1 == tq2 == target V): no entropy term
     const float y = A.reward_scale * T.rew[gr] + (1.0f - T.done[gr]) * A.gamma * fminf(T.tq1.get(gr), T.tq2.get(gr));
     d = T.coef * (T.q.get(gr) - y) * A.inv_B;
-  } else if (T.loss == LOSS_SACV_VALUE) {
+  } else if (BHG_LOSS == LOSS_SACV_VALUE) {
     // sac.py:120-131: v_target = min(Q1,Q2)(s,a~) - alpha*log pi (detached), L = 0.5*mean((v - v_target)^2)
     const float vt = fminf(T.q1n.get(gr), T.q2n.get(gr)) - T.coef * T.logp_next[gr];
     d = (T.q.get(gr) - vt) * A.inv_B;
-  } else if (T.loss == LOSS_CONST) {
+  } else if (BHG_LOSS == LOSS_CONST) {
     d = T.coef * A.inv_B;   // td3.py:113-114: -mean(Q1(s, pi(s)))
-  } else if (T.loss == LOSS_TD3_POLICY) {
+  } else if (BHG_LOSS == LOSS_TD3_POLICY) {
     // action = max_act*tanh(pre): d pre = dL/da * max_act * (1 - tanh(pre)^2); identity output (T.which = 1): d pre = dL/da * max_act
     const float th = T.which ? 0.0f : tanhf(T.raw[(size_t)gr * NO + j]);
     float ga = 0.0f;   // dQ1/da, possibly in column-slice partial slabs (<= 4: all requested before any is summed; a loop with a
@@ -742,14 +769,14 @@ __device__ __forceinline__ float bwd_head_grad(const BwdTask& T, const BwdArgs& 
 #pragma unroll
     for (int pc = 0; pc < 4; ++pc) ga += gp[pc];
     d = ga * T.coef * (1.0f - th * th);
-  } else if (T.loss == LOSS_BC_MLE || T.loss == LOSS_BC_MSE) {
+  } else if (BHG_LOSS == LOSS_BC_MLE || BHG_LOSS == LOSS_BC_MSE) {
     // bc.py:88-101.  raw = mean | log_std_raw [rows][2a]; act_all = expert actions [rows][a]
     const int a = NO >> 1, jj = j < a ? j : j - a;
     const float mu = T.raw[(size_t)gr * NO + jj], lsr = T.raw[(size_t)gr * NO + a + jj];
     const float ls = fminf(fmaxf(lsr, LOG_SIG_MIN), LOG_SIG_MAX);
     const bool gate = lsr >= LOG_SIG_MIN && lsr <= LOG_SIG_MAX;
     const float tgt = T.act_all[(size_t)gr * a + jj];
-    if (T.loss == LOSS_BC_MLE) {   // -mean(log_prob(acts)): z = atanh-with-epsilon of the expert action (distributions.py:85-88)
+    if (BHG_LOSS == LOSS_BC_MLE) {   // -mean(log_prob(acts)): z = atanh-with-epsilon of the expert action (distributions.py:85-88)
       const float z = 0.5f * (logf(1.0f + tgt + TANH_EPS) - logf(1.0f - tgt + TANH_EPS));
       const float var = expf(2.0f * ls), dm = mu - z;
       d = j < a ? dm / var * A.inv_B : (gate ? -(dm * dm / var - 1.0f) * A.inv_B : 0.0f);
@@ -758,7 +785,7 @@ __device__ __forceinline__ float bwd_head_grad(const BwdTask& T, const BwdArgs& 
       const float dz = 2.0f * (pred - tgt) * A.inv_B * (1.0f - pred * pred);
       d = j < a ? dz : (gate ? dz * expf(ls) * T.eps[(size_t)gr * a + jj] : 0.0f);
     }
-  } else if (T.loss == LOSS_MSE) {
+  } else if (BHG_LOSS == LOSS_MSE) {
     // ppo.py:145: mean((v - R)^2) over the minibatch
     const size_t sr = T.rows_idx ? (size_t)T.rows_idx[gr] : (size_t)gr;
     const float v = T.pred[gr], R = T.target[sr];
@@ -773,7 +800,7 @@ __device__ __forceinline__ float bwd_head_grad(const BwdTask& T, const BwdArgs& 
       const float w = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
       d = 2.0f * (w * (v - R) + (1.0f - w) * (vc - R) * inside) * A.inv_B;
     }
-  } else if (T.loss == LOSS_PPO_POLICY) {
+  } else if (BHG_LOSS == LOSS_PPO_POLICY) {
     // ppo.py:155-164: ratio = exp(logp - logp_old); -mean(min(ratio*A, clamp(ratio, 1+-eps)*A)); j indexes the mean
     const size_t sr = T.rows_idx ? (size_t)T.rows_idx[gr] : (size_t)gr;
     const float adv = T.target[sr];
@@ -823,6 +850,7 @@ __device__ __forceinline__ float bwd_head_grad(const BwdTask& T, const BwdArgs& 
       d = (lsr >= LOG_SIG_MIN && lsr <= LOG_SIG_MAX) ? dls : 0.0f;
     }
   }
+#undef BHG_LOSS
   return d;
 }
 
@@ -1033,9 +1061,12 @@ __global__ __launch_bounds__(4 * H / CS, (MT > 1 ? ILSX_MT_WAVES : GRP == 3 ? IL
   constexpr bool XCH = false;
   const int bx = (GRP && MT > 1) ? sw_bx : (int)blockIdx.x, cs = (GRP && MT > 1) ? sw_cs : (int)blockIdx.z;
   const bool first_task = ty == 0;
+  constexpr int FIN_CT = 0;
 #define XCH_HOOK_STAGE
 #define XCH_HOOK_FIN
+#define XCH_STAMP(i) ILSX_STAMP(A.dbg, i)
 #include "fwd_split_tile.inc"
+#undef XCH_STAMP
 #undef XCH_HOOK_STAGE
 #undef XCH_HOOK_FIN
 }
@@ -1096,9 +1127,12 @@ __global__ __launch_bounds__(4 * H / CS, (MT > 1 ? ILSX_MT_WAVES : GRP == 3 ? IL
   const BwdTask& T = GRP >= 2 ? g_bwd_tab[A.ctab - 1 + ty] : GRP == 1 ? Tg : A.t[ty];   // GRP 0 / 2: read in place (kernel arguments / constant table)
   constexpr bool XCH = false;
   const int bx = (GRP && MT > 1) ? sw_bx : (int)blockIdx.x, cs = (GRP && MT > 1) ? sw_cs : (int)blockIdx.z;
+  constexpr int LOSS_CT = -1, NO_CT = 0;   // run time: T.loss, N.NO
 #define XCH_HOOK_ACT
 #define XCH_HOOK_HEAD
+#define XCH_STAMP(i) ILSX_STAMP(A.dbg, i)
 #include "bwd_split_tile.inc"
+#undef XCH_STAMP
 #undef XCH_HOOK_ACT
 #undef XCH_HOOK_HEAD
 }
@@ -1295,9 +1329,12 @@ __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_a(const PhaseAArgs Pk,
       const FwdArgs& A = P.f1;
       const FwdTask& T = A.t[y];
       const bool first_task = y == 0;
+      constexpr int FIN_CT = -1;   // no policy is finished in front of stage 1 (launch_phase_a refuses f1.fin_on)
 #define XCH_HOOK_STAGE
 #define XCH_HOOK_FIN
+#define XCH_STAMP(i) ((void)0)
 #include "fwd_split_tile.inc"
+#undef XCH_STAMP
 #undef XCH_HOOK_STAGE
 #undef XCH_HOOK_FIN
     }
@@ -1321,10 +1358,13 @@ __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_a(const PhaseAArgs Pk,
       const int tq = own ? y - 5 : (y == 0 ? 0 : 1);
       const FwdTask& T = A.t[tq];
       const bool first_task = tq == 0;
+      constexpr int FIN_CT = 1;   // launch_phase_a refuses a second stage that is not {rows from T.x0, tanh-Gaussian epilogue in CS slabs}
 #define XCH_HOOK_STAGE ILSX_STAMP_SYNC(P.dbg, 7); xch_wait(f0, CS, P.err); ILSX_STAMP(P.dbg, 3);
 #define XCH_HOOK_FIN
 #define XCH_FINE_DBG P.dbg
+#define XCH_STAMP(i) do { if (own) ILSX_STAMP(P.dbg, (i) == 3 ? 6 : (i)); } while (0)   // rows 5 / 6: staged, layer 0, layer 1 -> slots 1, 2, 6
 #include "fwd_split_tile.inc"
+#undef XCH_STAMP
 #undef XCH_FINE_DBG
 #undef XCH_HOOK_STAGE
 #undef XCH_HOOK_FIN
@@ -1334,16 +1374,26 @@ __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_a(const PhaseAArgs Pk,
     ILSX_STAMP(P.dbg, 5);
   } else {
     xch_wait(f1, 4 * CS, P.err);   // the other slices' layer-1 activations, the lead slice's layer 0
+    // the pending tail of the previous step: it has run long before the target critics arrive, so this wait is taken HERE, off the chain
+    // (it used to follow the f2 wait: a second poll, barrier and cache drop in series behind the hand-off).  alpha is valid from here on
+    // (the static head reads it before the f2 wait), and the tail, which reads the previous step's log pi, is through before this one's lands
+    xch_wait(tflag, 1u, P.err);
     if (P.fin_pi_on && y == 1 && cs == 0) {   // workgroup-uniform
-      xch_wait(tflag, 1u, P.err);   // the pending tail of the previous step reads that step's log pi: it has to be through before this one's lands
       policy_fin_tile(P.fin_pi, bx * 16, P.f1.rows, smem, 4 * H / CS);
     }
     {
       const BwdArgs& A = P.b1;
       const BwdTask& T = A.t[y - 1];
+      constexpr int LOSS_CT = LOSS_SAC_CRITIC, NO_CT = 1;   // launch_phase_a refuses anything else
 #define XCH_HOOK_ACT
-#define XCH_HOOK_HEAD xch_wait(f2, 2 * CS, P.err); xch_wait(tflag, 1u, P.err); ILSX_STAMP(P.dbg, 3);
+#define XCH_HOOK_HEAD xch_wait(f2, 2 * CS, P.err); ILSX_STAMP(P.dbg, 3);
+#if defined(ILSX_STAMPS_FINE)
+#define XCH_STAMP(i) ((void)0)   // (slots 5 / 6 hold the shader clock)
+#else
+#define XCH_STAMP(i) do { if ((i) < 3) ILSX_STAMP(P.dbg, 4 + (i)); } while (0)   // head, delta_1 -> slots 5, 6 (delta_0 ends the stage: slot 4)
+#endif
 #include "bwd_split_tile.inc"
+#undef XCH_STAMP
 #undef XCH_HOOK_ACT
 #undef XCH_HOOK_HEAD
     }
@@ -1385,13 +1435,17 @@ __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_c(const PhaseCArgs Pk,
   xch_mark_xcd(P.flags + PHASE_MASK_WORD(bx));
   if (y == 2) {
     // the policy's backward has workgroups of its own: weights and saved activations (from phase A's launch) are requested at once,
-    // the head gradient waits for both critics' dQ/da partials (stage 2) — and with them for the action / noise / raw head stage 1 published
+    // the head gradient waits for both critics' dQ/da partials (stage 2) alone: action, noise and raw head are phase A's (pi(s) is finished
+    // there; launch_phase_c refuses a stage 1 that finishes a policy), and the static head reads them before the wait
     {
       const BwdArgs& A = P.b3;
       const BwdTask& T = A.t[0];
+      constexpr int LOSS_CT = LOSS_SAC_POLICY, NO_CT = 0;   // launch_phase_c refuses anything else
 #define XCH_HOOK_ACT
 #define XCH_HOOK_HEAD xch_wait(f2, 2 * CS, P.err); ILSX_STAMP(P.dbg, 4);
+#define XCH_STAMP(i) ILSX_STAMP(P.dbg, i)   // head, delta_1, delta_0 -> slots 1, 2, 3 (the wait returns at slot 4)
 #include "bwd_split_tile.inc"
+#undef XCH_STAMP
 #undef XCH_HOOK_ACT
 #undef XCH_HOOK_HEAD
     }
@@ -1402,9 +1456,12 @@ __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_c(const PhaseCArgs Pk,
     const FwdArgs& A = P.f3;
     const FwdTask& T = A.t[y];
     const bool first_task = y == 0;
+    constexpr int FIN_CT = -1;   // pi(s) was finished in phase A (launch_phase_c refuses f3.fin_on)
 #define XCH_HOOK_STAGE
 #define XCH_HOOK_FIN
+#define XCH_STAMP(i) ((void)0)
 #include "fwd_split_tile.inc"
+#undef XCH_STAMP
 #undef XCH_HOOK_STAGE
 #undef XCH_HOOK_FIN
   }
@@ -1413,9 +1470,12 @@ __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_c(const PhaseCArgs Pk,
   {
     const BwdArgs& A = P.b2;
     const BwdTask& T = A.t[y];
+    constexpr int LOSS_CT = LOSS_SAC_ACTORQ, NO_CT = 1;
 #define XCH_HOOK_ACT xch_wait(f1, 2 * CS, P.err); ILSX_STAMP(P.dbg, 2);
 #define XCH_HOOK_HEAD
+#define XCH_STAMP(i) ILSX_STAMP(P.dbg, 3 + (i))   // head, delta_1, delta_0 -> slots 4, 5, 6 (slot 3: the stage's end, after dL/dx)
 #include "bwd_split_tile.inc"
+#undef XCH_STAMP
 #undef XCH_HOOK_ACT
 #undef XCH_HOOK_HEAD
   }

@@ -267,6 +267,10 @@ int ilsx_sac_train_from_replay(ilsx_sac* sac, ilsx_replay* rb, int n_steps, int 
 int ilsx_sac_phase_state(ilsx_sac* sac, int* fallbacks, int* disabled, int* last_window_on_phase, int* wgs_per_cu_a, int* wgs_per_cu_c);
 /* test aid: the next window behaves as if one of its hand-offs had timed out (exercises the roll-back path on an exclusive GPU) */
 int ilsx_sac_debug_break_phase(ilsx_sac* sac);
+/* Test aid (no device needed) for what the merged phase kernels fix at compile time (loss kind per stage, one head output per critic, slab
+ * counts, the tanh-Gaussian epilogue, no explicit noise, no policy finished in phase C): 1 if a phase launch (stage 0 = A, 1 = C) takes
+ * descriptors with these properties, 0 if it refuses them.  flags: 1 = explicit noise for the epilogue, 2 = phase C's stage 1 finishes a policy. */
+int ilsx_debug_phase_static_ok(int stage, int loss_critic, int loss_policy, int no_critic, int slabs, int fin_head, int a, int H, int cs, int flags);
 /* Split-run (multi-GPU) phases: train_step == critic_backward ; critic_update ; actor_backward ;
  * actor_update, with an all-reduce(sum) of the gradient arena between backward and update. */
 int ilsx_sac_set_batch(ilsx_sac* sac, const float* obs, const float* act, const float* rew,

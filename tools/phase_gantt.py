@@ -7,6 +7,9 @@ Under the rows, per launch, the hand-offs between the stages: for every consumin
 producers to the return of its wait.  Phase A with the target critics on rows of their own (PhaseAArgs::own_rows) has rows 5 / 6; their
 hand-off is also split by the row of the workgroup they share a CU with (slot 7 of the measurement build holds XCD / CU, not a time).
 ILSX_GANTT_NO_BUILD=1 with ILSX_LIB set traces that library (another commit's measurement build) instead of building this tree's.
+
+The four stages that begin behind a wait also stamp their inner boundaries (the stage text's stamp points 1 / 2 / 3, routed to free slots of
+the row, POST_WAIT below); per such row a line "after the wait" gives the median time from the wait's return to each of them.
 """
 import ctypes as C
 import os
@@ -29,6 +32,26 @@ MAXWG, SLOTS, MAXL = 2048, 8, 14
 ROWS_A = {0: "pi(s')", 1: "Q1 fwd, bwd", 2: "Q2 fwd, bwd", 3: "pi(s)", 5: "TQ1, own row", 6: "TQ2, own row"}
 ROWS_A_OLD = {0: "pi(s') then TQ1", 1: "Q1 fwd, bwd", 2: "Q2 fwd, bwd", 3: "pi(s) then TQ2"}
 ROWS_C = {0: "Q1 fwd, bwd", 1: "Q2 fwd, bwd", 2: "pi bwd"}
+# (launch kind, row) -> slot of the wait's return, then (label, slot) of what follows it
+POST_WAIT = {("A", 1): (3, (("head barrier", 5), ("delta_1", 6), ("delta_0 = end", 4))), ("A", 2): (3, (("head barrier", 5), ("delta_1", 6), ("delta_0 = end", 4))),
+             ("A", 5): (3, (("rows staged", 1), ("layer 0", 2), ("layer 1", 6), ("end", 4))), ("A", 6): (3, (("rows staged", 1), ("layer 0", 2), ("layer 1", 6), ("end", 4))),
+             ("C", 0): (2, (("head barrier", 4), ("delta_1", 5), ("delta_0", 6), ("end", 3))), ("C", 1): (2, (("head barrier", 4), ("delta_1", 5), ("delta_0", 6), ("end", 3))),
+             ("C", 2): (4, (("head barrier", 1), ("delta_1", 2), ("delta_0", 3), ("end", 5)))}
+
+
+def post_wait(kind, own, yy, tm):
+    """tm: the row's workgroups x slots, us"""
+    if (kind, yy) not in POST_WAIT or (kind == "A" and yy >= 5 and not own):
+        return
+    w, pts = POST_WAIT[(kind, yy)]
+    out = []
+    for label, sl in pts:
+        ok = (tm[:, w] > 0) & (tm[:, sl] > 0)
+        if ok.any():
+            d = tm[ok, sl] - tm[ok, w]
+            out.append(f"{label} +{np.median(d):5.2f} (max {d.max():5.2f})")
+    if out:
+        print(f"        after the wait (s{w}): " + "  ".join(out))
 
 
 def handoff(name, tl, bx, prod, pslot, cons, cslot, s0):
@@ -92,10 +115,11 @@ for rep in range(2):
                     if ok.any():
                         row.append(f"s{sl}@{np.median(v[ok]) - s0:6.2f}(max {v[ok].max() - s0:6.2f})")
                 print(f"    task row {yy} ({names[yy]}): " + "  ".join(row))
+                post_wait(kind, own, yy, t[L][m])
                 if kind == "A" and yy in (1, 2):     # fine build: slots 5 / 6 hold the shader clock at the same two points as stamps 0 / 4
                     raw = buf_raw[L][m]
                     ok = (raw[:, 5] > 0) & (raw[:, 6] > 0) & (raw[:, 4] > 0)
-                    if ok.any():
+                    if ok.any() and (raw[ok, 6] - raw[ok, 5]).min() > 2 * (raw[ok, 4] - raw[ok, 0]).max():   # (the plain build stamps the head's boundaries there)
                         cyc = (raw[ok, 6] - raw[ok, 5]).astype(np.float64)
                         us = (raw[ok, 4] - raw[ok, 0]).astype(np.float64) * 0.01
                         print(f"        shader clock over the workgroup's life: {np.median(cyc / us):.0f} MHz (s_memtime cycles / 100 MHz stamps)")
