@@ -85,6 +85,97 @@ class AdamTrainer:
         return [p.detach().numpy().copy() for p in self.P]
 
 
+# ------------------------------------------------------------------------------------------------ float64: the gradient of one train step
+B2 = 0.999
+WRONG = ("no_inv_e", "inv_max_batch", "half_dmu", "no_lower", "no_upper", "no_mean_lv", "silu_sigmoid", "no_reward_scale", "next_obs_target",
+         "no_wd", "wd_weights_only", "wd_shifted", "members_swapped")
+
+
+def step_f64(params, mean, std, x, t, weight_decays, wrong=None, max_batch=None, reward_scale=1.0, stale=None):
+    """One train step in float64 autograd: x [E, B, in], t [E, B, D] the members' own rows (x[idx], t[idx]), one weight decay per layer.
+    Returns dict(loss = compute_loss per member [E], grads = g + wd_l * p of every parameter, flat in the parameters' layout, with g the
+    gradient of mean_e[ mean((mu - t)^2 e^-lv) + mean(lv) ] (bnn_trainer.py:71-87,141-154), raw = the head's raw log-variance [E, B, D]).
+    `wrong` names one deliberate mistake (WRONG), for the tests that show a check discriminates; every mistake leaves the loss VALUE's
+    formula alone where it can and changes the gradient.  `stale` (parameters of an earlier step) is one more: the backward chain takes
+    dh = dz @ W^T with THOSE weights, the forward and the weight gradient h^T dz with the current ones — a transposed copy that the
+    optimiser left behind."""
+    assert wrong is None or wrong in WRONG, wrong
+    f64 = lambda a: torch.as_tensor(np.asarray(a, np.float64))   # noqa: E731
+    P = [f64(p).requires_grad_(True) for p in params]
+    L, wd = len(P) // 2, [float(w) for w in weight_decays]
+    assert len(wd) == L
+    x, t = f64(x).clone(), f64(t).clone()
+    E, B, D = t.shape
+    if wrong == "members_swapped":          # member 0 reads member 1's index row
+        x[0], t[0] = x[1], t[1]
+    if wrong == "no_reward_scale":
+        t[:, :, 0] /= reward_scale
+    if wrong == "next_obs_target":          # next_obs where next_obs - obs belongs
+        t[:, :, 1:] += x[:, :, :D - 1]
+    h = (x - f64(mean)) / f64(std)
+    for li in range(L):
+        if stale is None or li == 0:
+            z = torch.matmul(h, P[2 * li]) + P[2 * li + 1]
+        else:                               # value h @ W + b; d/dW = h^T dz; d/dh = dz @ W_stale^T
+            via_stale = torch.matmul(h, f64(stale[2 * li]))
+            z = torch.matmul(h.detach(), P[2 * li]) + (via_stale - via_stale.detach()) + P[2 * li + 1]
+        if li == L - 1:
+            break
+        sg = torch.sigmoid(z)
+        h = z * (sg.detach() if wrong == "silu_sigmoid" else sg)        # detached: the derivative is sigmoid(z) alone
+    mu, raw = z[:, :, :D], z[:, :, D:]
+    lv1 = MAX_LV - F.softplus(MAX_LV - raw)
+    if wrong == "no_upper":                 # the value of lv1, the derivative 1
+        lv1 = raw + (lv1 - raw).detach()
+    lv = MIN_LV + F.softplus(lv1 - MIN_LV)
+    if wrong == "no_lower":
+        lv = lv1 + (lv - lv1).detach()
+    if wrong == "half_dmu":                 # the value of mu, half its derivative
+        mu = 0.5 * mu + 0.5 * mu.detach()
+    per = torch.mean((mu - t) ** 2 * torch.exp(-lv), dim=[-2, -1])
+    if wrong != "no_mean_lv":
+        per = per + torch.mean(lv, dim=[-2, -1])
+    total = torch.sum(per) if wrong == "no_inv_e" else torch.mean(per)
+    if wrong == "inv_max_batch":
+        total = total * (B / float(max_batch))
+    g = torch.autograd.grad(total, P)
+    if wrong == "no_wd":
+        wd = [0.0] * L
+    if wrong == "wd_shifted":
+        wd = wd[-1:] + wd[:-1]
+    out = []
+    for i, (p, gi) in enumerate(zip(P, g)):
+        w = 0.0 if (wrong == "wd_weights_only" and i % 2 == 1) else wd[i // 2]
+        out.append((gi + w * p.detach()).numpy().reshape(-1))
+    return dict(loss=per.detach().numpy(), grads=np.concatenate(out), raw=raw.detach().numpy())
+
+
+def blocks(shp):
+    """[(name, slice)] of a flat vector in the parameters' layout: one block is ONE member's weight or bias of one layer"""
+    out, f = [], 0
+    for i, s in enumerate(shp):
+        n = int(np.prod(s[1:]))
+        for e in range(s[0]):
+            out.append((f"fc{i // 2}.{'bias' if i % 2 else 'weight'}[{e}]", slice(f, f + n)))
+            f += n
+    return out
+
+
+def block_errors(got, ref, shp):
+    """[(name, max|got - ref|, max|ref|)] per block"""
+    got, ref, bl = np.asarray(got, np.float64).reshape(-1), np.asarray(ref, np.float64).reshape(-1), blocks(shp)
+    assert got.shape == ref.shape == (bl[-1][1].stop,), (got.shape, ref.shape)
+    return [(nm, float(np.abs(got[s] - ref[s]).max()), float(np.abs(ref[s]).max())) for nm, s in bl]
+
+
+def adam_moments(grads, beta_1=0.9):
+    """(exp_avg, exp_avg_sq) after Adam (betas beta_1 / 0.999, zero start) has seen `grads` in order"""
+    m, v = np.zeros_like(grads[0]), np.zeros_like(grads[0])
+    for g in grads:
+        m, v = beta_1 * m + (1 - beta_1) * g, B2 * v + (1 - B2) * g * g
+    return m, v
+
+
 def data_from_rows(obs, act, rew, nobs, reward_scale=1.0):
     """inputs [obs | act], targets [reward_scale * rew | next_obs - obs] (bnn_trainer.py:92-97), float32"""
     obs, act, nobs = (np.asarray(a, np.float32) for a in (obs, act, nobs))
