@@ -136,10 +136,9 @@ class MLPDisc:
             bn = self.get_bn_stats()
         if self.h is not None:   # re-bind (e.g. a forward on an unbound discriminator bound it with default settings): parameters AND the
             from .snapshot import get_opt   # optimiser's moments / step count move to the new library object
-            self._flat = self.get_flat_params()
             opt = get_opt(self.ctx.lib, "disc", self.h, self._nphys)
-            _lib.check(self.ctx.lib.ilsx_disc_destroy(self.h))
-        cfg = _lib.DiscCfg(obs_dim, second_dim, self._Hp, _ACT[self.hid_act], int(bool(use_grad_pen)), self.clamp_magnitude,
+            self.close()
+        cfg =_lib.DiscCfg(obs_dim, second_dim, self._Hp, _ACT[self.hid_act], int(bool(use_grad_pen)), self.clamp_magnitude,
                            disc_lr, disc_momentum, grad_pen_weight, int(max_batch), int(bool(state_only)), self.num_layer_blocks,
                            int(self.use_bn), int(grad_world))   # grad_world: ilsx_disc_cfg (one run split over G ranks)
         self.h = C.c_void_p()
@@ -154,6 +153,14 @@ class MLPDisc:
         if bn is not None:
             self.set_bn_stats(*bn)
         return self
+
+    def close(self):
+        """Destroy the library object, once: the discriminator is unbound again and keeps its parameters (not the optimiser's state or the
+        running statistics).  A closed context has freed the object's memory with its own."""
+        if self.h is not None and self.ctx.h:
+            self._flat = self.get_flat_params()
+            _lib.check(self.ctx.lib.ilsx_disc_destroy(self.h))
+        self.h = self._bound = None
 
     def _need(self):
         if self.h is None:

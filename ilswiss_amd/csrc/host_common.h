@@ -12,9 +12,8 @@
 #include <vector>
 
 #include "../../include/ilsx.h"
+#include "dev_owner.h"
 #include "kernels.h"
-
-void ilsx_set_err(const char* fmt, ...);
 
 #define ILSX_FAIL(code, ...)   \
   do {                         \
@@ -50,11 +49,6 @@ struct ilsx_ctx {
   void* stage = nullptr;
   size_t stage_bytes = 0;
   // optional per-kernel HIP-event timing (include/ilsx.h "kernel timing")
-  // row-range slabs of split weight-gradient launches (large batches): ONE region per gradient arena (keyed by the table's g_lo).  The kernels
-  // write only the live words of a slab and rely on the padding words staying zero — true as long as no table with another layout ever
-  // writes the same region (PPO's value and policy tables used to share one: ADVICE r4)
-  struct DwScratch { const float* key; size_t span; void* p; size_t bytes; };   // key + span name the table's gradient range
-  std::vector<DwScratch> dw_scratch;
   int rt_single = 1, rt_grouped = 1;   // 16-row tiles per workgroup in the column-split kernels (ILSX_RT / ILSX_RT_GROUPED)
   int xcd_shift = 0;  // ILSX_XCD_SHIFT: confine the split-MLP / dW kernels to every 2^k-th workgroup slot (3 = one XCD)
   unsigned long long* dbg_stamps = nullptr;  // device trace buffer for ILSX_STAMP (debug): [launch][ILSX_TRACE_MAXWG][ILSX_TRACE_SLOTS]
@@ -93,27 +87,6 @@ struct ProfScope {
   } while (0)
 
 int comm_allreduce_sum(ilsx_ctx* c, float* buf, size_t n);   // in place, on c->stream
-int ctx_alloc(ilsx_ctx* c, size_t bytes, void** out, bool zero = true);
-// One allocation carved into many buffers.  Every buffer an agent touches in a step then sits in ONE virtually contiguous
-// range (a handful of 2 MiB translation fragments) instead of ~60 separate hipMalloc's: a kernel that reads a dozen of them
-// as its first operands otherwise pays a dozen page-table walks before its first useful byte (measured: the first operands of
-// the backward launch landed 2.5 us after workgroup start, the weights — one allocation — after 0.55 us).
-struct Slab {
-  std::vector<std::pair<void**, size_t>> items;
-  size_t bytes = 0;
-  template <class T> void add(T** p, size_t count) {
-    bytes = (bytes + 255) & ~(size_t)255;
-    items.push_back({(void**)p, bytes});
-    bytes += count * sizeof(T);
-  }
-  int commit(ilsx_ctx* c, void** base) {   // zero-filled
-    int rc = ctx_alloc(c, bytes ? bytes : 256, base, true);
-    if (rc != ILSX_OK) return rc;
-    for (auto& it : items) *it.first = (char*)*base + it.second;
-    return ILSX_OK;
-  }
-};
-int ctx_free(ilsx_ctx* c, void* p);
 int ctx_stage(ilsx_ctx* c, size_t bytes, void** out);
 
 // Layout of one network: flat ABI order <-> internal (first-layer rows padded to KP, heads fused).
@@ -154,6 +127,9 @@ struct ilsx_net {
 int launch_categorical_act(ilsx_ctx* ctx, const float* z, int rows, int n, int deterministic, unsigned long long step, float* act, float* logp);
 // the epsilon-greedy argmax over raw head outputs z[rows][n] (dqn.h k_egreedy_act; ilsx_ac.hip)
 int launch_egreedy_act(ilsx_ctx* ctx, const float* z, int rows, int n, int deterministic, float epsilon, unsigned long long step, float* act);
+
+int net_adopt(ilsx_net* n, float* arena);   // an agent takes the network into its parameter arena (ilsx_core.hip)
+void net_give_back(ilsx_net* n);            // the agent's destroy: private storage back; no-op on a network that owns its storage
 
 int net_upload_flat(ilsx_ctx* ctx, const NetLayout& L, float* dev_base, const float* src, size_t n, int src_is_device);
 int net_download_flat(ilsx_ctx* ctx, const NetLayout& L, const float* dev_base, float* dst, size_t n, int dst_is_device);
@@ -201,7 +177,8 @@ int sac_snapshot_restore(ilsx_sac* s);
 bool sac_window_may_use_phase(ilsx_sac* s, int B);
 // column-split factor the 2-hidden-layer fast path uses for width H (1 = generic kernels)
 int mlp2_split_factor(int n_hidden, int H);
-int launch_bwd_dw(ilsx_ctx* ctx, const DwArgs& table, int rows, const AdamFuse* fuse = nullptr);
+// `owner`: the object whose gradient arena the table writes; it keeps the row-range scratch of the split launch (DevOwner::dw_region)
+int launch_bwd_dw(ilsx_ctx* ctx, DevOwner& owner, const DwArgs& table, int rows, const AdamFuse* fuse = nullptr);
 // appends one matrix to a dW table (computes its tile range)
 int dw_table_add(DwArgs* T, const float* A, int lda, int NA, const float* Bm, int ldb, int NB, float* dW, float* dWb, int ldw,
                  float* db, int mode, int rows = 0, int bias_rows = 0);

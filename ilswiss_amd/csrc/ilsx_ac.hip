@@ -49,6 +49,7 @@ __global__ __launch_bounds__(256) void k_ac_polyak(const float* __restrict__ p, 
 
 struct AcAgent {
   ilsx_ctx* ctx = nullptr;
+  DevOwner own;   // every device allocation of the agent, its algorithm's buffers included
   int nnets = 0, max_batch = 0, o = 0, a = 0, H = 0, act = 0, B = 0;
   NetLayout L[AC_MAX_NETS];
   ilsx_net* adopted[AC_MAX_NETS] = {nullptr, nullptr, nullptr, nullptr};
@@ -71,11 +72,16 @@ struct AcAgent {
   NetView view(int i, bool target = false) const { return net_view(L[i], (target ? T : P) + off[i]); }
 };
 
-static int ac_alloc(AcAgent* g, float** q, size_t n) { return ctx_alloc(g->ctx, n * sizeof(float), (void**)q, true); }
+static int ac_alloc(AcAgent* g, float** q, size_t n) { return g->own.alloc(q, n); }
+struct AcBuf { float** p; size_t n; };
+static int ac_alloc(AcAgent* g, std::initializer_list<AcBuf> bufs) {   // in the order given; stops at the first failure
+  for (const AcBuf& b : bufs) ILSX_TRY(ac_alloc(g, b.p, b.n));
+  return ILSX_OK;
+}
 
 // nets[i] are adopted into the arena in the given order; every net must share hidden width / depth / activation
 static int ac_init(AcAgent* g, ilsx_ctx* ctx, ilsx_net* const* nets, int nnets, const int* opt_of, int max_batch, int o, int a) {
-  g->ctx = ctx; g->nnets = nnets; g->max_batch = max_batch; g->o = o; g->a = a;
+  g->ctx = g->own.ctx = ctx; g->nnets = nnets; g->max_batch = max_batch; g->o = o; g->a = a;
   const ilsx_mlp_cfg& c0 = nets[0]->lay.cfg;
   g->H = c0.hidden; g->act = c0.act;
   g->cs = getenv("ILSX_NO_SPLIT") ? 1 : mlp2_split_factor(c0.n_hidden, c0.hidden);
@@ -92,8 +98,8 @@ static int ac_init(AcAgent* g, ilsx_ctx* ctx, ilsx_net* const* nets, int nnets, 
   const size_t n = g->off[nnets], B = (size_t)max_batch, H = (size_t)g->H;
   ILSX_TRY(ac_alloc(g, &g->P, n)); ILSX_TRY(ac_alloc(g, &g->G, n)); ILSX_TRY(ac_alloc(g, &g->M, n));
   ILSX_TRY(ac_alloc(g, &g->V, n)); ILSX_TRY(ac_alloc(g, &g->T, n));
-  ILSX_TRY(ctx_alloc(ctx, sizeof(AcScalars), (void**)&g->sc));
-  ILSX_TRY(ctx_alloc(ctx, sizeof(DevScalars), (void**)&g->dsc));
+  ILSX_TRY(g->own.alloc(&g->sc, 1));
+  ILSX_TRY(g->own.alloc(&g->dsc, 1));
   ILSX_TRY(ac_alloc(g, &g->s, B * o)); ILSX_TRY(ac_alloc(g, &g->ac, B * a)); ILSX_TRY(ac_alloc(g, &g->r, B));
   ILSX_TRY(ac_alloc(g, &g->d, B)); ILSX_TRY(ac_alloc(g, &g->s2, B * o)); ILSX_TRY(ac_alloc(g, &g->eps, B * a));
   hipStream_t st = ctx->stream;
@@ -108,9 +114,7 @@ static int ac_init(AcAgent* g, ilsx_ctx* ctx, ilsx_net* const* nets, int nnets, 
   }
   HIPCHK(hipStreamSynchronize(st));
   for (int i = 0; i < nnets; ++i) {
-    ILSX_TRY(ctx_free(ctx, nets[i]->base));
-    nets[i]->base = g->p(i);
-    nets[i]->owns = false;
+    ILSX_TRY(net_adopt(nets[i], g->p(i)));
     g->adopted[i] = nets[i];
   }
   g->rng_stream = ctx->next_rng_stream;
@@ -121,16 +125,8 @@ static int ac_init(AcAgent* g, ilsx_ctx* ctx, ilsx_net* const* nets, int nnets, 
 static void ac_release(AcAgent* g) {
   hipSetDevice(g->ctx->device);
   hipStreamSynchronize(g->ctx->stream);
-  for (int i = 0; i < g->nnets; ++i) {  // give the networks private storage back so their handles stay usable
-    float* nb = nullptr;
-    if (g->adopted[i] && ctx_alloc(g->ctx, g->L[i].n_int * 4, (void**)&nb, false) == ILSX_OK) {
-      hipMemcpyAsync(nb, g->p(i), g->L[i].n_int * 4, hipMemcpyDeviceToDevice, g->ctx->stream);
-      hipStreamSynchronize(g->ctx->stream);
-      g->adopted[i]->base = nb;
-      g->adopted[i]->owns = true;
-    }
-  }
-  ctx_free(g->ctx, g->P); ctx_free(g->ctx, g->G); ctx_free(g->ctx, g->M); ctx_free(g->ctx, g->V); ctx_free(g->ctx, g->T);
+  for (int i = 0; i < g->nnets; ++i) net_give_back(g->adopted[i]);   // private storage back: their handles stay usable
+  g->own.release();
 }
 
 static int ac_tick(AcAgent* g, int mask, int advance) {
@@ -200,7 +196,7 @@ static int ac_dw_adam(AcAgent* g, int net0, int nnet, bool polyak, float tau) {
   F.on = 1; F.Gbase = g->G; F.P = g->P; F.M = g->M; F.V = g->V; F.T = polyak ? g->T : nullptr;
   F.b1 = g->beta_1; F.b2 = 0.999f; F.eps = 1e-8f; F.tau = tau;
   F.step_size = &g->sc->step[op]; F.bc2_sqrt = &g->sc->bc2s[op];
-  return launch_bwd_dw(g->ctx, table, g->B, &F);
+  return launch_bwd_dw(g->ctx, g->own, table, g->B, &F);
 }
 static PartVal pv(AcAgent* g, const float* p) { return PartVal{p, g->cs, g->max_batch}; }
 
@@ -324,17 +320,11 @@ extern "C" int ilsx_td3_create(ilsx_ctx* ctx, const ilsx_td3_cfg* cfg, ilsx_net*
   int rc = ac_init(g, ctx, nets, 3, opt_of, cfg->max_batch, cp.in_dim, cp.out_dim);
   const size_t B = (size_t)cfg->max_batch, a = (size_t)cp.out_dim;
   const size_t CS = (size_t)g->cs;
-  float** bufs[] = {&t->q1, &t->q2, &t->tq1, &t->tq2, &t->qn};
-  for (float** b : bufs) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &t->a2, B * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &t->pa, B * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &t->pre, B * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &t->ga, CS * B * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &t->ppt, CS * B * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &t->ppc, CS * B * a);
+  if (rc == ILSX_OK) rc = ac_alloc(g, {{&t->q1, CS * B}, {&t->q2, CS * B}, {&t->tq1, CS * B}, {&t->tq2, CS * B}, {&t->qn, CS * B},
+                                      {&t->a2, B * a}, {&t->pa, B * a}, {&t->pre, B * a}, {&t->ga, CS * B * a}, {&t->ppt, CS * B * a}, {&t->ppc, CS * B * a}});
   if (rc == ILSX_OK && cfg->her) rc = ac_alloc(g, &t->tqc, B);
   if (rc == ILSX_OK) rc = ac_tick(g, 0, 0);
-  if (rc != ILSX_OK) { delete t; return rc; }
+  if (rc != ILSX_OK) { ilsx_td3_destroy(t); return rc; }
   pi->noise = cfg->policy_noise; pi->noise_clip = cfg->policy_noise_clip; pi->max_act = cfg->max_act; pi->noise_policy = true;
   t->out_linear = pi->out_linear;
   *out = t;
@@ -650,17 +640,12 @@ extern "C" int ilsx_ddpg_create(ilsx_ctx* ctx, const ilsx_ddpg_cfg* cfg, ilsx_ne
   g->lr[0] = cfg->qf_lr; g->lr[1] = cfg->policy_lr; g->beta_1 = 0.9f;   // optimizer_class defaults, ddpg.py:86-93
   int rc = ac_init(g, ctx, nets, 2, opt_of, cfg->max_batch, cp.in_dim, cp.out_dim);
   const size_t B = (size_t)cfg->max_batch, a = (size_t)cp.out_dim, CS = (size_t)g->cs;
-  float** bufs[] = {&t->tq, &t->q, &t->qn};
-  for (float** b : bufs) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B);
-  float** rows[] = {&t->y, &t->dq};
-  for (float** b : rows) if (rc == ILSX_OK) rc = ac_alloc(g, b, std::max<size_t>(B, 4) );
-  float** acts[] = {&t->a2, &t->pa, &t->pre, &t->dpre};
-  for (float** b : acts) if (rc == ILSX_OK) rc = ac_alloc(g, b, B * std::max<size_t>(a, 4));
-  float** parts[] = {&t->ga, &t->ppt, &t->ppc};
-  for (float** b : parts) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B * a);
+  const size_t B4 = std::max<size_t>(B, 4), Ba = B * std::max<size_t>(a, 4);
+  if (rc == ILSX_OK) rc = ac_alloc(g, {{&t->tq, CS * B}, {&t->q, CS * B}, {&t->qn, CS * B}, {&t->y, B4}, {&t->dq, B4},
+                                      {&t->a2, Ba}, {&t->pa, Ba}, {&t->pre, Ba}, {&t->dpre, Ba}, {&t->ga, CS * B * a}, {&t->ppt, CS * B * a}, {&t->ppc, CS * B * a}});
   for (int l = 0; l < cq.n_hidden; ++l) if (rc == ILSX_OK) rc = ac_alloc(g, &t->hq2[l], B * (size_t)g->H);
   if (rc == ILSX_OK) rc = ac_tick(g, 0, 0);
-  if (rc != ILSX_OK) { delete t; return rc; }
+  if (rc != ILSX_OK) { ilsx_ddpg_destroy(t); return rc; }
   pi->noise = 0.f; pi->noise_clip = 0.f; pi->max_act = cfg->max_act; pi->noise_policy = true;   // MlpPolicy: deterministic
   t->out_linear = pi->out_linear;
   *out = t;
@@ -762,7 +747,7 @@ static int ddpg_step(ilsx_ddpg* t, ilsx_ddpg_stats* stats) {
     DwArgs table;
     memset(&table, 0, sizeof table);
     ILSX_TRY(build_dw_jobs(g->L[DD_Q], g->G + g->off[DD_Q], g->x[DD_Q], g->h[DD_Q], g->dl[DD_Q], g->dh[DD_Q], &table));
-    ILSX_TRY(launch_bwd_dw(g->ctx, table, g->B, nullptr));
+    ILSX_TRY(launch_bwd_dw(g->ctx, g->own, table, g->B, nullptr));
     const NetLayout& L = g->L[DD_Q];
     DdpgBiasRanges R;
     memset(&R, 0, sizeof R);
@@ -873,14 +858,9 @@ extern "C" int ilsx_sacv_create(ilsx_ctx* ctx, const ilsx_sacv_cfg* cfg, ilsx_ne
   int rc = ac_init(g, ctx, nets, 4, opt_of, cfg->max_batch, cp.in_dim, cp.out_dim);
   const size_t B = (size_t)cfg->max_batch, a = (size_t)cp.out_dim;
   const size_t CS = (size_t)g->cs;
-  float** bufs[] = {&s->q1, &s->q2, &s->tv, &s->v, &s->q1n0, &s->q2n0, &s->q1n, &s->q2n};
-  for (float** b : bufs) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &s->logp, B);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &s->raw, B * 2 * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &s->ppart, CS * B * 2 * a);
-  float** abufs[] = {&s->an, &s->epss};
-  for (float** b : abufs) if (rc == ILSX_OK) rc = ac_alloc(g, b, B * a);
-  for (int i = 0; i < 2; ++i) if (rc == ILSX_OK) rc = ac_alloc(g, &s->ga[i], CS * B * a);
+  if (rc == ILSX_OK) rc = ac_alloc(g, {{&s->q1, CS * B}, {&s->q2, CS * B}, {&s->tv, CS * B}, {&s->v, CS * B}, {&s->q1n0, CS * B}, {&s->q2n0, CS * B},
+                                      {&s->q1n, CS * B}, {&s->q2n, CS * B}, {&s->logp, B}, {&s->raw, B * 2 * a}, {&s->ppart, CS * B * 2 * a},
+                                      {&s->an, B * a}, {&s->epss, B * a}, {&s->ga[0], CS * B * a}, {&s->ga[1], CS * B * a}});
   if (rc == ILSX_OK) {  // fixed temperature (sac.py:68): the policy loss head reads it from the device scalars
     DevScalars h;
     memset(&h, 0, sizeof h);
@@ -889,7 +869,7 @@ extern "C" int ilsx_sacv_create(ilsx_ctx* ctx, const ilsx_sacv_cfg* cfg, ilsx_ne
     hipStreamSynchronize(ctx->stream);
     rc = ac_tick(g, 0, 0);
   }
-  if (rc != ILSX_OK) { delete s; return rc; }
+  if (rc != ILSX_OK) { ilsx_sacv_destroy(s); return rc; }
   *out = s;
   return ILSX_OK;
 }
@@ -1067,12 +1047,9 @@ extern "C" int ilsx_bc_create(ilsx_ctx* ctx, const ilsx_bc_cfg* cfg, ilsx_net* p
   g->lr[0] = cfg->lr; g->beta_1 = cfg->momentum;
   int rc = ac_init(g, ctx, nets, 1, opt_of, cfg->max_batch, pi->lay.cfg.in_dim, pi->lay.cfg.out_dim);
   const size_t B = (size_t)cfg->max_batch, a = (size_t)pi->lay.cfg.out_dim;
-  if (rc == ILSX_OK) rc = ac_alloc(g, &b->raw, B * 2 * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &b->pred, B * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &b->epss, B * a);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &b->logp, B);
+  if (rc == ILSX_OK) rc = ac_alloc(g, {{&b->raw, B * 2 * a}, {&b->pred, B * a}, {&b->epss, B * a}, {&b->logp, B}});
   if (rc == ILSX_OK) rc = ac_tick(g, 0, 0);
-  if (rc != ILSX_OK) { delete b; return rc; }
+  if (rc != ILSX_OK) { ilsx_bc_destroy(b); return rc; }
   *out = b;
   return ILSX_OK;
 }
@@ -1218,14 +1195,11 @@ extern "C" int ilsx_dsac_create(ilsx_ctx* ctx, const ilsx_dsac_cfg* cfg, ilsx_ne
   g->lr[0] = cfg->qf_lr; g->lr[1] = cfg->policy_lr; g->beta_1 = cfg->beta_1;   // discrete_sac.py:50-58
   int rc = ac_init(g, ctx, nets, 3, opt_of, cfg->max_batch, cp.in_dim, 1);
   const size_t B = (size_t)cfg->max_batch, n = (size_t)d->n, CS = (size_t)g->cs;
-  float** heads[] = {&d->zpi, &d->zpn, &d->q1, &d->q2, &d->tq1, &d->tq2, &d->q1n, &d->q2n};
-  for (float** b : heads) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B * n);
-  float** grads[] = {&d->gq1, &d->gq2, &d->gpi};
-  for (float** b : grads) if (rc == ILSX_OK) rc = ac_alloc(g, b, B * n);
-  float** rows[] = {&d->y, &d->qa1, &d->qa2, &d->ploss};
-  for (float** b : rows) if (rc == ILSX_OK) rc = ac_alloc(g, b, B);
+  const size_t Z = CS * B * n;
+  if (rc == ILSX_OK) rc = ac_alloc(g, {{&d->zpi, Z}, {&d->zpn, Z}, {&d->q1, Z}, {&d->q2, Z}, {&d->tq1, Z}, {&d->tq2, Z}, {&d->q1n, Z}, {&d->q2n, Z},
+                                      {&d->gq1, B * n}, {&d->gq2, B * n}, {&d->gpi, B * n}, {&d->y, B}, {&d->qa1, B}, {&d->qa2, B}, {&d->ploss, B}});
   if (rc == ILSX_OK) rc = ac_tick(g, 0, 0);
-  if (rc != ILSX_OK) { delete d; return rc; }
+  if (rc != ILSX_OK) { ilsx_dsac_destroy(d); return rc; }
   *out = d;
   return ILSX_OK;
 }
@@ -1396,13 +1370,9 @@ extern "C" int ilsx_dqn_create(ilsx_ctx* ctx, const ilsx_dqn_cfg* cfg, ilsx_net*
   g->lr[0] = cfg->learning_rate; g->beta_1 = 0.9f;   // optim.Adam(lr=learning_rate), dqn.py:59-62
   int rc = ac_init(g, ctx, nets, 1, opt_of, cfg->max_batch, cq.in_dim, 1);
   const size_t B = (size_t)cfg->max_batch, n = (size_t)t->n, CS = (size_t)g->cs;
-  float** heads[] = {&t->tq, &t->qn, &t->q};
-  for (float** b : heads) if (rc == ILSX_OK) rc = ac_alloc(g, b, CS * B * n);
-  if (rc == ILSX_OK) rc = ac_alloc(g, &t->gq, B * n);
-  float** rows[] = {&t->y, &t->qa};
-  for (float** b : rows) if (rc == ILSX_OK) rc = ac_alloc(g, b, B);
+  if (rc == ILSX_OK) rc = ac_alloc(g, {{&t->tq, CS * B * n}, {&t->qn, CS * B * n}, {&t->q, CS * B * n}, {&t->gq, B * n}, {&t->y, B}, {&t->qa, B}});
   if (rc == ILSX_OK) rc = ac_tick(g, 0, 0);
-  if (rc != ILSX_OK) { delete t; return rc; }
+  if (rc != ILSX_OK) { ilsx_dqn_destroy(t); return rc; }
   *out = t;
   return ILSX_OK;
 }

@@ -9,6 +9,7 @@
 
 struct ilsx_bnn {
   ilsx_ctx* ctx = nullptr;
+  DevOwner own;   // the slab, `part` and the rollout buffers s_*
   ilsx_bnn_cfg cfg{};
   int nl = 0, HP = 0, NOP = 0, D = 0, KP0 = 0;
   int in_l[ILSX_BNN_MAX_LAYERS] = {0}, out_l[ILSX_BNN_MAX_LAYERS] = {0};
@@ -62,9 +63,9 @@ static BnnNet bnn_net(const ilsx_bnn* b) {
 
 static int bnn_grow(ilsx_bnn* b, float** p, size_t* have, size_t need) {
   if (need <= *have) return ILSX_OK;
-  if (*p) ILSX_TRY(ctx_free(b->ctx, *p));
+  ILSX_TRY(b->own.free(*p));
   *p = nullptr;
-  ILSX_TRY(ctx_alloc(b->ctx, need * sizeof(float), (void**)p, true));
+  ILSX_TRY(b->own.alloc(p, need));
   *have = need;
   return ILSX_OK;
 }
@@ -80,7 +81,7 @@ extern "C" int ilsx_bnn_create(ilsx_ctx* ctx, const ilsx_bnn_cfg* cfg, ilsx_bnn*
               ILSX_BNN_MAX_WIDE, c.hidden, c.in_dim, 2 * c.out_dim);
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_bnn* b = new ilsx_bnn();
-  b->ctx = ctx; b->cfg = c;
+  b->ctx = b->own.ctx = ctx; b->cfg = c;
   b->nl = c.n_hidden + 1; b->HP = r16(c.hidden); b->D = c.out_dim; b->NOP = r16(2 * c.out_dim); b->KP0 = r16(c.in_dim);
   long long off = 0;
   for (int l = 0; l < b->nl; ++l) {
@@ -107,11 +108,11 @@ extern "C" int ilsx_bnn_create(ilsx_ctx* ctx, const ilsx_bnn_cfg* cfg, ilsx_bnn*
   s.add(&b->dhead, E * b->ldr * b->NOP);
   s.add(&b->loss, E);
   void* base = nullptr;
-  rc = s.commit(ctx, &base);
-  if (rc != ILSX_OK) { delete b; return rc; }
+  rc = b->own.commit(s, &base);
+  if (rc != ILSX_OK) { ilsx_bnn_destroy(b); return rc; }
   for (int k = 0; k < 256; ++k) { b->h_mean[k] = 0.f; b->h_std[k] = 1.0f + 1e-8f; }   // FixedNormalizer(mean=0, std=1): std + eps
   rc = ilsx_bnn_set_normalizer(b, b->h_mean, b->h_std);
-  if (rc != ILSX_OK) { delete b; return rc; }
+  if (rc != ILSX_OK) { ilsx_bnn_destroy(b); return rc; }
   b->rng_stream = ctx->next_rng_stream++;
   *out = b;
   return ILSX_OK;
@@ -119,12 +120,9 @@ extern "C" int ilsx_bnn_create(ilsx_ctx* ctx, const ilsx_bnn_cfg* cfg, ilsx_bnn*
 
 extern "C" int ilsx_bnn_destroy(ilsx_bnn* b) {
   if (!b) return ILSX_OK;
-  ilsx_ctx* c = b->ctx;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (void* p : {(void*)b->part, (void*)b->s_mean, (void*)b->s_lv, (void*)b->s_x, (void*)b->s_act, (void*)b->s_rew, (void*)b->s_nobs, (void*)b->s_done,
-                  (void*)b->s_midx, (void*)b->s_elites, (void*)b->s_count})
-    if (p) ctx_free(c, p);
-  if (b->P) ctx_free(c, b->P);   // the slab's base
+  hipSetDevice(b->ctx->device);
+  hipStreamSynchronize(b->ctx->stream);
+  b->own.release();
   delete b;
   return ILSX_OK;
 }
@@ -379,21 +377,24 @@ extern "C" int ilsx_bnn_predict(ilsx_bnn* b, const float* x, int n, float* mean,
 
 static int bnn_step_scratch(ilsx_bnn* b, int n, int o, int a) {
   if (n <= b->step_cap) return ILSX_OK;
-  ilsx_ctx* c = b->ctx;
-  for (void* p : {(void*)b->s_mean, (void*)b->s_lv, (void*)b->s_x, (void*)b->s_act, (void*)b->s_rew, (void*)b->s_nobs, (void*)b->s_done,
-                  (void*)b->s_midx})
-    if (p) ILSX_TRY(ctx_free(c, p));
+  DevOwner& own = b->own;
+  for (void** p : {(void**)&b->s_mean, (void**)&b->s_lv, (void**)&b->s_x, (void**)&b->s_act, (void**)&b->s_rew, (void**)&b->s_nobs, (void**)&b->s_done,
+                   (void**)&b->s_midx}) {
+    ILSX_TRY(own.free(*p));
+    *p = nullptr;
+  }
+  b->step_cap = 0;
   const size_t E = b->cfg.ensemble, D = b->D;
-  ILSX_TRY(ctx_alloc(c, E * n * D * 4, (void**)&b->s_mean, false));
-  ILSX_TRY(ctx_alloc(c, E * n * D * 4, (void**)&b->s_lv, false));
-  ILSX_TRY(ctx_alloc(c, (size_t)n * b->cfg.in_dim * 4, (void**)&b->s_x, false));
-  ILSX_TRY(ctx_alloc(c, (size_t)n * a * 4, (void**)&b->s_act, false));
-  ILSX_TRY(ctx_alloc(c, (size_t)n * 4, (void**)&b->s_rew, false));
-  ILSX_TRY(ctx_alloc(c, (size_t)n * o * 4, (void**)&b->s_nobs, false));
-  ILSX_TRY(ctx_alloc(c, (size_t)n, (void**)&b->s_done, false));
-  ILSX_TRY(ctx_alloc(c, (size_t)n * 4, (void**)&b->s_midx, false));
-  if (!b->s_elites) ILSX_TRY(ctx_alloc(c, 256 * 4, (void**)&b->s_elites, true));
-  if (!b->s_count) ILSX_TRY(ctx_alloc(c, 64, (void**)&b->s_count, true));
+  ILSX_TRY(own.alloc(&b->s_mean, E * n * D, false));
+  ILSX_TRY(own.alloc(&b->s_lv, E * n * D, false));
+  ILSX_TRY(own.alloc(&b->s_x, (size_t)n * b->cfg.in_dim, false));
+  ILSX_TRY(own.alloc(&b->s_act, (size_t)n * a, false));
+  ILSX_TRY(own.alloc(&b->s_rew, (size_t)n, false));
+  ILSX_TRY(own.alloc(&b->s_nobs, (size_t)n * o, false));
+  ILSX_TRY(own.alloc(&b->s_done, (size_t)n, false));
+  ILSX_TRY(own.alloc(&b->s_midx, (size_t)n, false));
+  if (!b->s_elites) ILSX_TRY(own.alloc(&b->s_elites, 256));
+  if (!b->s_count) ILSX_TRY(own.alloc_bytes(&b->s_count, 64));
   b->step_cap = n;
   return ILSX_OK;
 }

@@ -40,24 +40,6 @@ int ctx_free(ilsx_ctx* c, void* p) {
   if (it == c->allocs.end()) ILSX_FAIL(ILSX_ERR_ARG, "ctx_free: pointer not owned by this ctx");
   c->allocs.erase(it);
   HIPCHK(hipStreamSynchronize(c->stream));
-  // row-range slabs of split weight-gradient launches are keyed by the gradient range they belong to (launch_bwd_dw): when the allocation
-  // holding that range goes, so do they — hipMalloc hands the address to the next trainer, whose table (same span, another live / padding
-  // layout) must not inherit this one's nonzero words, and a destroyed trainer's slabs should not stay allocated until the ctx goes
-  hipDeviceptr_t base = nullptr; size_t size = 0;
-  if (!c->dw_scratch.empty() && hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess) {
-    for (size_t i = 0; i < c->dw_scratch.size();) {
-      const char* k = (const char*)c->dw_scratch[i].key;
-      if (k >= (const char*)base && k < (const char*)base + size) {
-        void* sp = c->dw_scratch[i].p;
-        c->dw_scratch.erase(c->dw_scratch.begin() + i);
-        if (sp) {
-          auto js = std::find(c->allocs.begin(), c->allocs.end(), sp);
-          if (js != c->allocs.end()) c->allocs.erase(js);
-          HIPCHK(hipFree(sp));
-        }
-      } else ++i;
-    }
-  }
   HIPCHK(hipFree(p));
   return ILSX_OK;
 }
@@ -800,7 +782,7 @@ extern "C" int ilsx_debug_dw_split(int rows, int big, int* splits, int* rows_per
   return ILSX_OK;
 }
 
-int launch_bwd_dw(ilsx_ctx* ctx, const DwArgs& table, int rows, const AdamFuse* fuse) {
+int launch_bwd_dw(ilsx_ctx* ctx, DevOwner& owner, const DwArgs& table, int rows, const AdamFuse* fuse) {
   if (table.ntiles <= 0 || rows <= 0) return ILSX_OK;
   DwArgs D = table;
   D.rows_all = rows;
@@ -820,17 +802,10 @@ int launch_bwd_dw(ilsx_ctx* ctx, const DwArgs& table, int rows, const AdamFuse* 
     dw_split_plan(rows, big, &splits, &rps);
     const size_t span = (size_t)(D.g_hi - D.g_lo);
     const size_t need = (size_t)splits * span * sizeof(float);
-    ilsx_ctx::DwScratch* reg = nullptr;
-    for (auto& r : ctx->dw_scratch) if (r.key == D.g_lo && r.span == span) reg = &r;
-    if (!reg) { ctx->dw_scratch.push_back({D.g_lo, span, nullptr, 0}); reg = &ctx->dw_scratch.back(); }
-    if (reg->bytes < need) {
-      if (reg->p) ILSX_TRY(ctx_free(ctx, reg->p));
-      reg->p = nullptr; reg->bytes = 0;
-      ILSX_TRY(ctx_alloc(ctx, need, &reg->p, true));   // zeroed: padding words are never written, and no other table writes this region
-      reg->bytes = need;
-    }
+    void* scratch = nullptr;
+    ILSX_TRY(owner.dw_region(D.g_lo, span, need, &scratch));
     D.splits = splits; D.rows_per_split = rps;
-    D.scratch = (float*)reg->p; D.span = span; D.xs = 0;
+    D.scratch = (float*)scratch; D.span = span; D.xs = 0;
     const AdamFuse keep = D.F;
     D.F.on = 0;
     if (big) {
@@ -962,10 +937,27 @@ extern "C" int ilsx_net_create(ilsx_ctx* ctx, const ilsx_mlp_cfg* cfg, ilsx_net*
 }
 extern "C" int ilsx_net_destroy(ilsx_net* n) {
   if (!n) return ILSX_OK;
-  if (n->owns && n->base) ctx_free(n->ctx, n->base);
+  if (!n->owns) ILSX_FAIL(ILSX_ERR_STATE, "ilsx_net_destroy: the network belongs to an agent, which writes through it when it is destroyed: destroy the agent first");
+  if (n->base) ctx_free(n->ctx, n->base);
   if (n->ws_out) ctx_free(n->ctx, n->ws_out);
   delete n;
   return ILSX_OK;
+}
+// An agent adopts a network whose parameters it has copied to `arena`: the network's own storage goes, its handle reads and writes the arena
+int net_adopt(ilsx_net* n, float* arena) {
+  ILSX_TRY(ctx_free(n->ctx, n->base));
+  n->base = arena;
+  n->owns = false;
+  return ILSX_OK;
+}
+// ... and gets private storage back (a copy of its arena slice) when the agent is destroyed, so its handle stays usable
+void net_give_back(ilsx_net* n) {
+  float* nb = nullptr;
+  if (!n || n->owns || ctx_alloc(n->ctx, n->lay.n_int * 4, (void**)&nb, false) != ILSX_OK) return;
+  hipMemcpyAsync(nb, n->base, n->lay.n_int * 4, hipMemcpyDeviceToDevice, n->ctx->stream);
+  hipStreamSynchronize(n->ctx->stream);
+  n->base = nb;
+  n->owns = true;
 }
 extern "C" int ilsx_net_num_params(const ilsx_net* n, size_t* out) {
   if (!n || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_net_num_params: NULL argument");

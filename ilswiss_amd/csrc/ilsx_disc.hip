@@ -349,6 +349,7 @@ struct DiscBn {
 // ------------------------------------------------------------------------------------------------ host
 struct ilsx_disc {
   ilsx_ctx* ctx = nullptr;
+  DevOwner own;   // arenas, workspaces (the DiscBn ones included) and the lazily allocated snap
   ilsx_disc_cfg cfg;
   NetLayout L;
   int cs = 1, D = 0, o = 0, a = 0;
@@ -377,6 +378,70 @@ static int disc_refresh(ilsx_disc* d) {
   return ILSX_OK;
 }
 
+// use_bn: Linear -> BatchNorm1d -> act blocks: natural layout, any width, the phase chain of csrc/disc_bn_step.h
+static int disc_setup_bn(ilsx_disc* d) {
+  const ilsx_disc_cfg* cfg = &d->cfg;
+  ilsx_ctx* ctx = d->ctx;
+  if (cfg->hid_dim < 1 || cfg->hid_dim > 1024) ILSX_FAIL(ILSX_ERR_ARG, "hid_dim=%d out of range", cfg->hid_dim);
+  if (cfg->hid_act != ILSX_ACT_RELU && cfg->hid_act != ILSX_ACT_TANH) ILSX_FAIL(ILSX_ERR_ARG, "hid_act=%d unknown", cfg->hid_act);
+  DiscBn* b = d->bn = new DiscBn();
+  DbnNet& N = b->N;
+  N.D = d->D; N.H = cfg->hid_dim; N.nblk = d->nblk; N.act = cfg->hid_act == ILSX_ACT_TANH ? DBN_TANH : DBN_RELU; N.clampv = cfg->clamp_magnitude;
+  const size_t np = (size_t)N.n_params(), H = (size_t)N.H, rows = 3 * (size_t)cfg->max_batch, wd = std::max(H, (size_t)d->D);
+  b->rows = (int)rows;
+  d->L.n_flat = np; d->L.n_int = np;   // flat ABI order == storage order (torch's parameters(): per block W | b | gamma | beta, then the output layer)
+  d->cs = 1;
+  d->rng_stream = ctx->next_rng_stream++;
+  auto A = [&](float** p, size_t cnt) { return d->own.alloc(p, cnt); };
+  ILSX_TRY(A(&d->P, np)); ILSX_TRY(A(&d->G, np)); ILSX_TRY(A(&d->M, np)); ILSX_TRY(A(&d->V, np));
+  ILSX_TRY(d->own.alloc(&d->scal, 1));
+  ILSX_TRY(A(&d->X, rows * d->D));
+  ILSX_TRY(A(&d->eps_used, (size_t)cfg->max_batch));
+  ILSX_TRY(A(&N.rmean, (size_t)N.nblk * H));
+  ILSX_TRY(A(&N.rvar, (size_t)N.nblk * H));
+  N.P = d->P; N.G = d->G; N.M = d->M; N.V = d->V;
+  DbnWs& W = b->W;
+  for (int l = 0; l < N.nblk; ++l) {
+    for (float** m : {&W.ch[l], &W.ah[l], &W.h[l], &W.p[l], &W.gch[l], &W.gah[l], &W.gh[l], &W.gp[l], &W.uh[l], &W.uy[l], &W.uah[l], &W.tt[l], &W.ua[l],
+                      &W.ybar[l], &W.ahbar[l]}) ILSX_TRY(A(m, rows * H));
+    for (float** v : {&W.s[l], &W.gs[l], &W.m2[l], &W.sbar[l]}) ILSX_TRY(A(v, H));
+  }
+  ILSX_TRY(A(&W.t0, rows * wd)); ILSX_TRY(A(&W.t1, rows * wd)); ILSX_TRY(A(&W.gt0, rows * wd)); ILSX_TRY(A(&W.gt1, rows * wd));
+  ILSX_TRY(A(&W.bstat, (size_t)2 * N.nblk * 2 * H));
+  for (float** v : {&W.logit, &W.dlogit, &W.gate, &W.ce_row, &W.correct, &W.gp_row, &b->lg}) ILSX_TRY(A(v, rows));
+  ILSX_TRY(A(&b->stats3, 4));
+  ILSX_TRY(A(&b->xcat, rows * d->D));
+  std::vector<float> ones((size_t)N.nblk * H, 1.0f);   // running_var starts at 1 (torch.nn.BatchNorm1d), running_mean at 0
+  HIPCHK(hipMemcpyAsync(N.rvar, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  W.X = d->X; W.XH = d->X + 2 * (size_t)cfg->max_batch * d->D;   // re-pointed per step (the interpolates follow the 2B stacked rows)
+  return ILSX_OK;
+}
+static int disc_setup_mlp(ilsx_disc* d) {
+  const ilsx_disc_cfg* cfg = &d->cfg;
+  ilsx_mlp_cfg mc = {d->D, d->nblk, cfg->hid_dim, 1, 1, cfg->hid_act};
+  ILSX_TRY(net_layout_build(mc, &d->L));
+  d->cs = (getenv("ILSX_NO_SPLIT") || d->nblk != 2) ? 1 : mlp2_split_factor(2, cfg->hid_dim);
+  d->rng_stream = d->ctx->next_rng_stream++;
+  const size_t n = d->L.n_int, B = (size_t)cfg->max_batch, H = (size_t)cfg->hid_dim, KP = (size_t)d->L.KP;
+  auto A = [&](float** p, size_t cnt) { return d->own.alloc(p, cnt); };
+  ILSX_TRY(A(&d->P, n)); ILSX_TRY(A(&d->G, n)); ILSX_TRY(A(&d->M, n)); ILSX_TRY(A(&d->V, n));
+  ILSX_TRY(d->own.alloc(&d->scal, 1));
+  ILSX_TRY(A(&d->X, 3 * B * d->D));
+  ILSX_TRY(A(&d->xs, 4 * B * KP));
+  ILSX_TRY(A(&d->hs0, 4 * B * H)); ILSX_TRY(A(&d->hs1, 3 * B * H));
+  ILSX_TRY(A(&d->A2, 4 * B * H)); ILSX_TRY(A(&d->A1, 4 * B * H));
+  ILSX_TRY(A(&d->dhead, 3 * B));
+  ILSX_TRY(A(&d->raw, (size_t)d->cs * 3 * B));
+  ILSX_TRY(A(&d->ce_row, 2 * B)); ILSX_TRY(A(&d->correct, 2 * B));
+  ILSX_TRY(A(&d->gp_row, B)); ILSX_TRY(A(&d->eps_used, B));
+  if (d->nblk != 2) {
+    for (int l = 0; l < d->nblk; ++l) { ILSX_TRY(A(&d->hsb[l], 4 * B * H)); ILSX_TRY(A(&d->Ab[l], 4 * B * H)); ILSX_TRY(A(&d->zb[l], B * H)); }
+    ILSX_TRY(A(&d->given, 3 * B)); ILSX_TRY(A(&d->gdx, B * 64)); ILSX_TRY(A(&d->dhead4, 4 * B));
+  }
+  return disc_refresh(d);
+}
+
 extern "C" int ilsx_disc_create(ilsx_ctx* ctx, const ilsx_disc_cfg* cfg, ilsx_disc** out) {
   if (!ctx || !cfg || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_disc_create: NULL argument");
   if (cfg->obs_dim < 1 || cfg->act_dim < 1 || cfg->obs_dim + cfg->act_dim > 64)
@@ -386,7 +451,7 @@ extern "C" int ilsx_disc_create(ilsx_ctx* ctx, const ilsx_disc_cfg* cfg, ilsx_di
     ILSX_FAIL(ILSX_ERR_ARG, "state_only: the second input segment is next_obs, act_dim (%d) must equal obs_dim (%d)", cfg->act_dim, cfg->obs_dim);
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_disc* d = new ilsx_disc();
-  d->ctx = ctx; d->cfg = *cfg; d->o = cfg->obs_dim; d->a = cfg->act_dim; d->D = d->o + d->a;
+  d->ctx = d->own.ctx = ctx; d->cfg = *cfg; d->o = cfg->obs_dim; d->a = cfg->act_dim; d->D = d->o + d->a;
   if (d->cfg.grad_world < 1) d->cfg.grad_world = 1;
   if (d->cfg.grad_world > 1 && cfg->use_bn) {
     delete d;
@@ -394,115 +459,18 @@ extern "C" int ilsx_disc_create(ilsx_ctx* ctx, const ilsx_disc_cfg* cfg, ilsx_di
   }
   d->nblk = cfg->num_layer_blocks ? cfg->num_layer_blocks : 2;
   if (d->nblk < 1 || d->nblk > ILSX_MAX_HID) { const int nb = d->nblk; delete d; ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "num_layer_blocks=%d: 1..%d", nb, ILSX_MAX_HID); }
-  if (cfg->use_bn) {   // Linear -> BatchNorm1d -> act blocks: natural layout, any width, the phase chain of csrc/disc_bn_step.h
-    if (cfg->hid_dim < 1 || cfg->hid_dim > 1024) { delete d; ILSX_FAIL(ILSX_ERR_ARG, "hid_dim=%d out of range", cfg->hid_dim); }
-    if (cfg->hid_act != ILSX_ACT_RELU && cfg->hid_act != ILSX_ACT_TANH) { delete d; ILSX_FAIL(ILSX_ERR_ARG, "hid_act=%d unknown", cfg->hid_act); }
-    DiscBn* b = d->bn = new DiscBn();
-    DbnNet& N = b->N;
-    N.D = d->D; N.H = cfg->hid_dim; N.nblk = d->nblk; N.act = cfg->hid_act == ILSX_ACT_TANH ? DBN_TANH : DBN_RELU; N.clampv = cfg->clamp_magnitude;
-    const size_t np = (size_t)N.n_params(), H = (size_t)N.H, rows = 3 * (size_t)cfg->max_batch, wd = std::max(H, (size_t)d->D);
-    b->rows = (int)rows;
-    d->L.n_flat = np; d->L.n_int = np;   // flat ABI order == storage order (torch's parameters(): per block W | b | gamma | beta, then the output layer)
-    d->cs = 1;
-    d->rng_stream = ctx->next_rng_stream++;
-    auto A = [&](float** p, size_t cnt) { return ctx_alloc(ctx, cnt * sizeof(float), (void**)p, true); };
-    int rc = A(&d->P, np);
-    if (rc == ILSX_OK) rc = A(&d->G, np);
-    if (rc == ILSX_OK) rc = A(&d->M, np);
-    if (rc == ILSX_OK) rc = A(&d->V, np);
-    if (rc == ILSX_OK) rc = ctx_alloc(ctx, sizeof(DiscScalars), (void**)&d->scal);
-    if (rc == ILSX_OK) rc = A(&d->X, rows * d->D);
-    if (rc == ILSX_OK) rc = A(&d->eps_used, (size_t)cfg->max_batch);
-    if (rc == ILSX_OK) rc = A(&N.rmean, (size_t)N.nblk * H);
-    if (rc == ILSX_OK) rc = A(&N.rvar, (size_t)N.nblk * H);
-    N.P = d->P; N.G = d->G; N.M = d->M; N.V = d->V;
-    DbnWs& W = b->W;
-    for (int l = 0; l < N.nblk && rc == ILSX_OK; ++l) {
-      float** mats[] = {&W.ch[l], &W.ah[l], &W.h[l], &W.p[l], &W.gch[l], &W.gah[l], &W.gh[l], &W.gp[l], &W.uh[l], &W.uy[l], &W.uah[l], &W.tt[l], &W.ua[l],
-                        &W.ybar[l], &W.ahbar[l]};
-      for (float** m : mats) if (rc == ILSX_OK) rc = A(m, rows * H);
-      float** vecs[] = {&W.s[l], &W.gs[l], &W.m2[l], &W.sbar[l]};
-      for (float** v : vecs) if (rc == ILSX_OK) rc = A(v, H);
-    }
-    if (rc == ILSX_OK) rc = A(&W.t0, rows * wd);
-    if (rc == ILSX_OK) rc = A(&W.t1, rows * wd);
-    if (rc == ILSX_OK) rc = A(&W.gt0, rows * wd);
-    if (rc == ILSX_OK) rc = A(&W.gt1, rows * wd);
-    if (rc == ILSX_OK) rc = A(&W.bstat, (size_t)2 * N.nblk * 2 * H);
-    float** rowv[] = {&W.logit, &W.dlogit, &W.gate, &W.ce_row, &W.correct, &W.gp_row, &b->lg};
-    for (float** v : rowv) if (rc == ILSX_OK) rc = A(v, rows);
-    if (rc == ILSX_OK) rc = A(&b->stats3, 4);
-    if (rc == ILSX_OK) rc = A(&b->xcat, rows * d->D);
-    if (rc == ILSX_OK) {   // running_var starts at 1 (torch.nn.BatchNorm1d), running_mean at 0
-      std::vector<float> ones((size_t)N.nblk * H, 1.0f);
-      hipError_t e = hipMemcpyAsync(N.rvar, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) { ilsx_set_err("ilsx_disc_create: %s", hipGetErrorString(e)); rc = ILSX_ERR_HIP; }
-    }
-    if (rc != ILSX_OK) { ilsx_disc_destroy(d); return rc; }   // releases every buffer allocated so far (the destroy path takes nulls)
-    W.X = d->X; W.XH = d->X + 2 * (size_t)cfg->max_batch * d->D;   // re-pointed per step (the interpolates follow the 2B stacked rows)
-    *out = d;
-    return ILSX_OK;
-  }
-  ilsx_mlp_cfg mc = {d->D, d->nblk, cfg->hid_dim, 1, 1, cfg->hid_act};
-  int rc = net_layout_build(mc, &d->L);
-  if (rc != ILSX_OK) { delete d; return rc; }   // nothing allocated yet
-  d->cs = (getenv("ILSX_NO_SPLIT") || d->nblk != 2) ? 1 : mlp2_split_factor(2, cfg->hid_dim);
-  d->rng_stream = ctx->next_rng_stream++;
-  const size_t n = d->L.n_int, B = (size_t)cfg->max_batch, H = (size_t)cfg->hid_dim, KP = (size_t)d->L.KP;
-  auto A = [&](float** p, size_t cnt) { return ctx_alloc(ctx, cnt * sizeof(float), (void**)p, true); };
-  rc = A(&d->P, n);
-  if (rc == ILSX_OK) rc = A(&d->G, n);
-  if (rc == ILSX_OK) rc = A(&d->M, n);
-  if (rc == ILSX_OK) rc = A(&d->V, n);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, sizeof(DiscScalars), (void**)&d->scal);
-  if (rc == ILSX_OK) rc = A(&d->X, 3 * B * d->D);
-  if (rc == ILSX_OK) rc = A(&d->xs, 4 * B * KP);
-  if (rc == ILSX_OK) rc = A(&d->hs0, 4 * B * H);
-  if (rc == ILSX_OK) rc = A(&d->hs1, 3 * B * H);
-  if (rc == ILSX_OK) rc = A(&d->A2, 4 * B * H);
-  if (rc == ILSX_OK) rc = A(&d->A1, 4 * B * H);
-  if (rc == ILSX_OK) rc = A(&d->dhead, 3 * B);
-  if (rc == ILSX_OK) rc = A(&d->raw, (size_t)d->cs * 3 * B);
-  if (rc == ILSX_OK) rc = A(&d->ce_row, 2 * B);
-  if (rc == ILSX_OK) rc = A(&d->correct, 2 * B);
-  if (rc == ILSX_OK) rc = A(&d->gp_row, B);
-  if (rc == ILSX_OK) rc = A(&d->eps_used, B);
-  if (d->nblk != 2) {
-    for (int l = 0; l < d->nblk && rc == ILSX_OK; ++l) {
-      rc = A(&d->hsb[l], 4 * B * H);
-      if (rc == ILSX_OK) rc = A(&d->Ab[l], 4 * B * H);
-      if (rc == ILSX_OK) rc = A(&d->zb[l], B * H);
-    }
-    if (rc == ILSX_OK) rc = A(&d->given, 3 * B);
-    if (rc == ILSX_OK) rc = A(&d->gdx, B * 64);
-    if (rc == ILSX_OK) rc = A(&d->dhead4, 4 * B);
-  }
-  if (rc == ILSX_OK) rc = disc_refresh(d);
-  if (rc != ILSX_OK) { ilsx_disc_destroy(d); return rc; }
+  int rc = cfg->use_bn ? disc_setup_bn(d) : disc_setup_mlp(d);
+  if (rc != ILSX_OK) { ilsx_disc_destroy(d); return rc; }   // releases every buffer allocated so far
   *out = d;
   return ILSX_OK;
 }
 
 extern "C" int ilsx_disc_destroy(ilsx_disc* d) {
   if (!d) return ILSX_OK;
-  void* ps[] = {d->P, d->G, d->M, d->V, d->scal, d->X, d->xs, d->hs0, d->hs1, d->A2, d->A1, d->dhead, d->raw, d->ce_row,
-                d->correct, d->gp_row, d->eps_used};
-  for (void* p : ps) ctx_free(d->ctx, p);
-  for (int l = 0; l < ILSX_MAX_HID; ++l) { if (d->hsb[l]) ctx_free(d->ctx, d->hsb[l]); if (d->Ab[l]) ctx_free(d->ctx, d->Ab[l]); if (d->zb[l]) ctx_free(d->ctx, d->zb[l]); }
-  if (d->given) ctx_free(d->ctx, d->given);
-  if (d->gdx) ctx_free(d->ctx, d->gdx);
-  if (d->dhead4) ctx_free(d->ctx, d->dhead4);
-  if (d->snap) ctx_free(d->ctx, d->snap);
-  if (d->bn) {
-    DiscBn* b = d->bn;
-    DbnWs& W = b->W;
-    for (int l = 0; l < b->N.nblk; ++l)
-      for (float* p : {W.ch[l], W.ah[l], W.h[l], W.p[l], W.gch[l], W.gah[l], W.gh[l], W.gp[l], W.gs[l], W.uh[l], W.uy[l], W.uah[l], W.tt[l], W.ua[l], W.ybar[l],
-                       W.ahbar[l], W.s[l], W.m2[l], W.sbar[l]}) ctx_free(d->ctx, p);
-    for (float* p : {W.t0, W.t1, W.gt0, W.gt1, W.bstat, W.logit, W.dlogit, W.gate, W.ce_row, W.correct, W.gp_row, b->lg, b->stats3, b->xcat, b->N.rmean, b->N.rvar}) ctx_free(d->ctx, p);
-    delete b;
-  }
+  hipSetDevice(d->ctx->device);
+  hipStreamSynchronize(d->ctx->stream);
+  d->own.release();
+  delete d->bn;
   delete d;
   return ILSX_OK;
 }
@@ -694,12 +662,12 @@ static int disc_dw_adam(ilsx_disc* d, int rows) {
   F.on = 1; F.Gbase = d->G; F.P = d->P; F.M = d->M; F.V = d->V; F.T = nullptr;
   F.b1 = d->cfg.disc_momentum; F.b2 = 0.999f; F.eps = 1e-8f; F.tau = 0.f;
   F.step_size = &d->scal->adam_step; F.bc2_sqrt = &d->scal->adam_bc2s;
-  if (!disc_is_split(d)) return launch_bwd_dw(ctx, d->jobs, rows, &F);
+  if (!disc_is_split(d)) return launch_bwd_dw(ctx, d->own, d->jobs, rows, &F);
   if (d->cfg.grad_world > 1 && (!ctx->comm || ctx->comm_n != d->cfg.grad_world) &&
       !(ctx->comm && ctx->comm_n == 1 && getenv("ILSX_SPLIT_FORCE")))   // (tests: a one-rank communicator stands in, the arena holds this rank's share)
     ILSX_FAIL(ILSX_ERR_STATE, "discriminator step: grad_world=%d needs a communicator of that many ranks on the ctx (ilsx_comm_init; found %d)",
               d->cfg.grad_world, ctx->comm ? ctx->comm_n : 0);
-  ILSX_TRY(launch_bwd_dw(ctx, d->jobs, rows, nullptr));
+  ILSX_TRY(launch_bwd_dw(ctx, d->own, d->jobs, rows, nullptr));
   ILSX_TRY(comm_allreduce_sum(ctx, d->G, d->L.n_int));
   AdamArgs A;
   memset(&A, 0, sizeof A);
@@ -931,7 +899,7 @@ extern "C" int ilsx_advirl_train(ilsx_disc* d, ilsx_sac* sac, ilsx_replay* exper
   const unsigned long long c_e = expert_rb->sample_ctr, c_p = policy_rb->sample_ctr, c_d = d->step_ctr;
   if (checkpoint) {
     hipStream_t st = d->ctx->stream;
-    if (!d->snap) ILSX_TRY(ctx_alloc(d->ctx, (3 * n) * sizeof(float) + sizeof(DiscScalars), (void**)&d->snap, false));
+    if (!d->snap) ILSX_TRY(d->own.alloc_bytes(&d->snap, (3 * n) * sizeof(float) + sizeof(DiscScalars), false));
     HIPCHK(hipMemcpyAsync(d->snap, d->P, n * 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(d->snap + n, d->M, n * 4, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(d->snap + 2 * n, d->V, n * 4, hipMemcpyDeviceToDevice, st));

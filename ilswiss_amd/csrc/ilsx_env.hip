@@ -37,7 +37,7 @@ struct PlanarModelDev {
 struct EnvStepArgs;
 struct ilsx_vecenv {
   ilsx_ctx* ctx = nullptr;
-  std::vector<void*> owned;   // every device allocation of this handle (env_alloc): ilsx_vecenv_destroy frees exactly these
+  DevOwner own;   // every device allocation of this handle, at creation or later: ilsx_vecenv_destroy gives all of it back
   // the step and reset kernels of this handle, chosen once at creation (env_select_planar / _spatial / _classic)
   int (*step_fn)(ilsx_vecenv*, ProfScope&, const EnvStepArgs&) = nullptr;
   int (*reset_fn)(ilsx_vecenv*, const int* ids_dev, int n_ids, float* obs, unsigned long long step) = nullptr;
@@ -84,18 +84,6 @@ struct ilsx_vecenv {
   unsigned long long explore_calls = 0;   // Philox counter of k_explore (one draw per call)
   const float* policy_obs() const { return norm_obs ? obs_n : obs_cur; }
 };
-
-// Device memory of a vec-env, at creation or later: recorded in the handle, so that destroying the handle gives all of it back
-template <class T>
-static int env_alloc(ilsx_vecenv* e, size_t bytes, T** out) {
-  ILSX_TRY(ctx_alloc(e->ctx, bytes, (void**)out));
-  e->owned.push_back(*out);
-  return ILSX_OK;
-}
-static int env_free(ilsx_vecenv* e, void* p) {
-  e->owned.erase(std::remove(e->owned.begin(), e->owned.end(), p), e->owned.end());
-  return ctx_free(e->ctx, p);
-}
 
 // RunningMeanStd (normalizer.py:128-152): float64, one owner workgroup per observation dimension (count is kept per
 // dimension so that no workgroup depends on another's update).
@@ -894,7 +882,7 @@ struct EnvGuard {
 };
 static ilsx_vecenv* env_new(ilsx_ctx* ctx, int engine, int n_env, uint64_t seed) {
   ilsx_vecenv* e = new ilsx_vecenv();
-  e->ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++; e->engine = engine;
+  e->ctx = e->own.ctx = ctx; e->n_env = n_env; e->seed = seed; e->rng_stream = ctx->next_rng_stream++; e->engine = engine;
   return e;
 }
 // What every creator does once nq / nv / o / a and the kernels of the handle are known: the buffers all engines share, RunningMeanStd() and
@@ -902,19 +890,19 @@ static ilsx_vecenv* env_new(ilsx_ctx* ctx, int engine, int n_env, uint64_t seed)
 static int env_create_finish(EnvGuard& guard, ilsx_vecenv** out) {
   ilsx_vecenv* e = guard.e;
   const size_t N = (size_t)e->n_env;
-  ILSX_TRY(env_alloc(e, N * e->nq * 8, &e->qpos));
-  ILSX_TRY(env_alloc(e, N * e->nv * 8, &e->qvel));
-  ILSX_TRY(env_alloc(e, N * e->o * 4, &e->obs_cur));
-  ILSX_TRY(env_alloc(e, N * e->a * 4, &e->act));
-  ILSX_TRY(env_alloc(e, N * e->o * 4, &e->nobs));
-  ILSX_TRY(env_alloc(e, N * 4, &e->rew));
-  ILSX_TRY(env_alloc(e, N, &e->done));
-  ILSX_TRY(env_alloc(e, N * 4, &e->ep_len));
-  ILSX_TRY(env_alloc(e, N * e->o * 4, &e->obs_n));
-  ILSX_TRY(env_alloc(e, sizeof(ObsRms), &e->rms));
-  ILSX_TRY(env_alloc(e, N * 8, &e->ep_ret));
-  ILSX_TRY(env_alloc(e, 4 * 8, &e->stats));
-  ILSX_TRY(env_alloc(e, N * 4, &e->ids));
+  ILSX_TRY(e->own.alloc_bytes(&e->qpos, N * e->nq * 8));
+  ILSX_TRY(e->own.alloc_bytes(&e->qvel, N * e->nv * 8));
+  ILSX_TRY(e->own.alloc_bytes(&e->obs_cur, N * e->o * 4));
+  ILSX_TRY(e->own.alloc_bytes(&e->act, N * e->a * 4));
+  ILSX_TRY(e->own.alloc_bytes(&e->nobs, N * e->o * 4));
+  ILSX_TRY(e->own.alloc_bytes(&e->rew, N * 4));
+  ILSX_TRY(e->own.alloc_bytes(&e->done, N));
+  ILSX_TRY(e->own.alloc_bytes(&e->ep_len, N * 4));
+  ILSX_TRY(e->own.alloc_bytes(&e->obs_n, N * e->o * 4));
+  ILSX_TRY(e->own.alloc_bytes(&e->rms, sizeof(ObsRms)));
+  ILSX_TRY(e->own.alloc_bytes(&e->ep_ret, N * 8));
+  ILSX_TRY(e->own.alloc_bytes(&e->stats, 4 * 8));
+  ILSX_TRY(e->own.alloc_bytes(&e->ids, N * 4));
   ObsRms h;   // RunningMeanStd(): mean 0, var 1, count 0 (normalizer.py:133-136)
   for (int i = 0; i < ENV_MAX_OBS; ++i) { h.mean[i] = 0.0; h.var[i] = 1.0; h.count[i] = 0.0; }
   HIPCHK(hipMemcpyAsync(e->rms, &h, sizeof h, hipMemcpyHostToDevice, e->ctx->stream));
@@ -970,7 +958,7 @@ extern "C" int ilsx_vecenv_create(ilsx_ctx* ctx, const ilsx_planar_model* pm, in
   for (int i = 0; i < e->n; ++i) m.init_qpos[i] = pm->init_qpos[i];
   for (int i = 0; i < 2 * (ENV_MAXB + 2); ++i) { m.obs_shift[i] = 0.0; m.obs_inv_scale[i] = 1.0; }
   ILSX_TRY(env_select_planar(e));
-  ILSX_TRY(env_alloc(e, sizeof m, &e->dm));
+  ILSX_TRY(e->own.alloc_bytes(&e->dm, sizeof m));
   HIPCHK(hipMemcpyAsync(e->dm, &m, sizeof m, hipMemcpyHostToDevice, ctx->stream));
   return env_create_finish(guard, out);
 }
@@ -998,8 +986,8 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
     ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_create_spatial: obs_trunc is available for the Ant (14 dofs) and the Humanoid (23), not for %d dofs", m.nv);
   e->n = m.nq; e->nq = m.nq; e->nv = m.nv; e->o = m.obs_dim; e->a = m.n_act;
   env_select_spatial(e);
-  ILSX_TRY(env_alloc(e, sizeof m, &e->dm3));
-  ILSX_TRY(env_alloc(e, (size_t)E3Off::TOTAL * n_env * 8, &e->scr3));
+  ILSX_TRY(e->own.alloc_bytes(&e->dm3, sizeof m));
+  ILSX_TRY(e->own.alloc_bytes(&e->scr3, (size_t)E3Off::TOTAL * n_env * 8));
   HIPCHK(hipMemcpyAsync(e->dm3, &m, sizeof m, hipMemcpyHostToDevice, ctx->stream));
   return env_create_finish(guard, out);
 }
@@ -1230,7 +1218,9 @@ extern "C" int ilsx_vecenv_state_dims(const ilsx_vecenv* e, int* nq, int* nv) {
 
 extern "C" int ilsx_vecenv_destroy(ilsx_vecenv* e) {
   if (!e) return ILSX_OK;
-  for (void* p : e->owned) ctx_free(e->ctx, p);
+  hipSetDevice(e->ctx->device);
+  hipStreamSynchronize(e->ctx->stream);
+  e->own.release();
   if (e->flush_host) hipHostFree(e->flush_host);
   if (e->grp_flush_host) hipHostFree(e->grp_flush_host);
   delete e->hm3;
@@ -1453,8 +1443,8 @@ static int rollout_env_args(ilsx_vecenv* e, ilsx_replay* rb, int max_path_length
                 max_path_length, rb->rec);
     if (!e->stage) {
       if (max_path_length < 1 || max_path_length >= rb->cap) ILSX_FAIL(ILSX_ERR_ARG, "path mode needs 1 <= max_path_length < replay capacity");
-      ILSX_TRY(env_alloc(e, (size_t)e->n_env * max_path_length * rb->rec * 4, &e->stage));
-      ILSX_TRY(env_alloc(e, (size_t)e->n_env * 4, &e->flush_len));
+      ILSX_TRY(e->own.alloc_bytes(&e->stage, (size_t)e->n_env * max_path_length * rb->rec * 4));
+      ILSX_TRY(e->own.alloc_bytes(&e->flush_len, (size_t)e->n_env * 4));
       e->stage_len = max_path_length; e->stage_rec = rb->rec;
       HIPCHK(hipHostMalloc((void**)&e->flush_host, (size_t)e->n_env * sizeof(int), hipHostMallocDefault));
     }
@@ -1497,7 +1487,7 @@ extern "C" int ilsx_vecenv_set_exploration(ilsx_vecenv* e, const ilsx_explore_cf
   e->explore = *cfg;
   if (!cfg->kind) return ILSX_OK;
   const size_t n = (size_t)e->n_env * e->a;
-  if (!e->ou_state) { ILSX_TRY(env_alloc(e, n * 8, &e->ou_state)); ILSX_TRY(env_alloc(e, n * 8, &e->ou_sigma)); }
+  if (!e->ou_state) { ILSX_TRY(e->own.alloc_bytes(&e->ou_state, n * 8)); ILSX_TRY(e->own.alloc_bytes(&e->ou_sigma, n * 8)); }
   std::vector<double> h(n, cfg->mu);   // OUStrategy.__init__: state = mu, sigma = max_sigma
   HIPCHK(hipMemcpyAsync(e->ou_state, h.data(), n * 8, hipMemcpyHostToDevice, e->ctx->stream));
   HIPCHK(hipStreamSynchronize(e->ctx->stream));
@@ -1560,7 +1550,7 @@ static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, i
   EnvStepArgs A;
   ILSX_TRY(rollout_env_args(e, rb, max_path_length, no_terminal, step, &A));
   if (label_pi) {   // DAgger._handle_step (dagger.py:45-71): the stored action is the expert's for the observation acted on
-    if (!e->act_label) ILSX_TRY(env_alloc(e, (size_t)e->n_env * e->a * 4, &e->act_label));
+    if (!e->act_label) ILSX_TRY(e->own.alloc_bytes(&e->act_label, (size_t)e->n_env * e->a * 4));
     ILSX_TRY(ilsx_policy_act(label_pi, e->policy_obs(), e->n_env, label_deterministic, nullptr, e->act_label, nullptr));
     A.rec_act = e->act_label;
   }
@@ -1671,10 +1661,10 @@ static int rollout_lockstep_grouped(ilsx_vecenv* const* envs, ilsx_net* const* p
   for (int k = 0; k < n_runs; ++k) all_paths = all_paths && envs[k]->path_mode;
   const int ne = e0m->n_env;
   if (all_paths && e0m->grp_flush_n < n_runs * ne) {   // the group's flag array (owned by run 0's env, freed with it)
-    if (e0m->grp_flush_dev) ILSX_TRY(env_free(e0m, e0m->grp_flush_dev));
+    if (e0m->grp_flush_dev) ILSX_TRY(e0m->own.free(e0m->grp_flush_dev));
     if (e0m->grp_flush_host) HIPCHK(hipHostFree(e0m->grp_flush_host));
     e0m->grp_flush_dev = nullptr; e0m->grp_flush_host = nullptr; e0m->grp_flush_n = 0;
-    ILSX_TRY(env_alloc(e0m, (size_t)n_runs * ne * sizeof(int), &e0m->grp_flush_dev));
+    ILSX_TRY(e0m->own.alloc_bytes(&e0m->grp_flush_dev, (size_t)n_runs * ne * sizeof(int)));
     HIPCHK(hipHostMalloc((void**)&e0m->grp_flush_host, (size_t)n_runs * ne * sizeof(int), hipHostMallocDefault));
     e0m->grp_flush_n = n_runs * ne;
   }
@@ -1857,9 +1847,9 @@ __global__ void k_eval_accum(const float* __restrict__ rew, const unsigned char*
 static int eval_buffers(ilsx_vecenv* e) {   // allocated by the env's first evaluation rollout
   if (e->ev_frozen) return ILSX_OK;
   const int n = e->n_env;
-  ILSX_TRY(env_alloc(e, n, &e->ev_frozen)); ILSX_TRY(env_alloc(e, (size_t)n * 8, &e->ev_ret));
-  ILSX_TRY(env_alloc(e, (size_t)n * 4, &e->ev_len)); ILSX_TRY(env_alloc(e, EV_N * 8, &e->ev_stats));
-  ILSX_TRY(env_alloc(e, 4, &e->ev_alive));
+  ILSX_TRY(e->own.alloc_bytes(&e->ev_frozen, n)); ILSX_TRY(e->own.alloc_bytes(&e->ev_ret, (size_t)n * 8));
+  ILSX_TRY(e->own.alloc_bytes(&e->ev_len, (size_t)n * 4)); ILSX_TRY(e->own.alloc_bytes(&e->ev_stats, EV_N * 8));
+  ILSX_TRY(e->own.alloc_bytes(&e->ev_alive, 4));
   return ILSX_OK;
 }
 
@@ -1966,11 +1956,11 @@ extern "C" int ilsx_eval_rollouts_lockstep(ilsx_vecenv* const* envs, ilsx_net* c
     if (envs[k]->ctx->stream != gs) HIPCHK(hipStreamSynchronize(envs[k]->ctx->stream));
   }
   if (e0->grp_flush_n < n_runs) {   // the group's small int array (alive counters here, episode-end flags in the training rollouts)
-    if (e0->grp_flush_dev) ILSX_TRY(env_free(e0, e0->grp_flush_dev));
+    if (e0->grp_flush_dev) ILSX_TRY(e0->own.free(e0->grp_flush_dev));
     if (e0->grp_flush_host) HIPCHK(hipHostFree(e0->grp_flush_host));
     e0->grp_flush_dev = nullptr; e0->grp_flush_host = nullptr; e0->grp_flush_n = 0;
     const int cnt = std::max(n_runs, n_runs * ne);
-    ILSX_TRY(env_alloc(e0, (size_t)cnt * sizeof(int), &e0->grp_flush_dev));
+    ILSX_TRY(e0->own.alloc_bytes(&e0->grp_flush_dev, (size_t)cnt * sizeof(int)));
     HIPCHK(hipHostMalloc((void**)&e0->grp_flush_host, (size_t)cnt * sizeof(int), hipHostMallocDefault));
     e0->grp_flush_n = cnt;
   }

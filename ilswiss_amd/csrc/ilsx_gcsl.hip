@@ -54,19 +54,41 @@ struct ilsx_bncat {
   unsigned long long draws = 0;   // Philox counter of the stochastic act calls
   uint32_t rng_stream = 0;
   float* stats = nullptr;      // device [2]: mean CE, accuracy of the last step
-  std::vector<void*> owned;
+  DevOwner own;
 };
-
-static int bncat_alloc(ilsx_bncat* b, float** p, size_t cnt) {
-  int rc = ctx_alloc(b->ctx, cnt * sizeof(float), (void**)p, true);
-  if (rc == ILSX_OK) b->owned.push_back(*p);
-  return rc;
-}
 
 extern "C" int ilsx_bncat_destroy(ilsx_bncat* b) {
   if (!b) return ILSX_OK;
-  for (void* p : b->owned) ctx_free(b->ctx, p);
+  hipSetDevice(b->ctx->device);
+  hipStreamSynchronize(b->ctx->stream);
+  b->own.release();
   delete b;
+  return ILSX_OK;
+}
+
+// parameters, running statistics and the step workspace of a new policy
+static int bncat_setup(ilsx_bncat* b) {
+  GcslNet& N = b->N;
+  GcslWs& W = b->W;
+  const size_t np = (size_t)N.n_params(), H = (size_t)N.H, R = (size_t)b->rows, nb = (size_t)N.nblk;
+  auto A = [&](float** p, size_t cnt) { return b->own.alloc(p, cnt); };
+  for (float** p : {&N.P, &N.G, &N.M, &N.V}) ILSX_TRY(A(p, np));
+  ILSX_TRY(A(&N.rmean, nb * H)); ILSX_TRY(A(&N.rvar, nb * H));
+  ILSX_TRY(A(&W.X, R * N.D));
+  ILSX_TRY(A((float**)&W.label, R));
+  for (int l = 0; l < N.nblk; ++l) {
+    for (float** p : {&W.ch[l], &W.ah[l], &W.h[l], &W.p[l]}) ILSX_TRY(A(p, R * H));
+    ILSX_TRY(A(&W.s[l], H));
+  }
+  ILSX_TRY(A(&W.t0, R * H)); ILSX_TRY(A(&W.t1, R * H));
+  ILSX_TRY(A(&W.logit, R * N.n)); ILSX_TRY(A(&W.dlogit, R * N.n));
+  ILSX_TRY(A(&W.ce_row, R)); ILSX_TRY(A(&W.correct, R));
+  ILSX_TRY(A(&W.bstat, nb * 2 * H));
+  ILSX_TRY(A(&b->stats, 2));
+  // BatchNorm1d's initial running statistics: mean 0, variance 1 — on the ctx stream, behind the zeroing of the allocation
+  std::vector<float> ones(nb * H, 1.0f);
+  HIPCHK(hipMemcpyAsync(N.rvar, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice, b->ctx->stream));
+  HIPCHK(hipStreamSynchronize(b->ctx->stream));
   return ILSX_OK;
 }
 
@@ -78,41 +100,12 @@ extern "C" int ilsx_bncat_create(ilsx_ctx* ctx, int in_dim, int hidden, int n_bl
   if (max_rows < 2 || max_rows > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_bncat_create: max_rows=%d out of range", max_rows);
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_bncat* b = new ilsx_bncat();
-  b->ctx = ctx;
+  b->ctx = b->own.ctx = ctx;
   b->rows = max_rows;
   b->rng_stream = ctx->next_rng_stream++;
   GcslNet& N = b->N;
   N.D = in_dim; N.H = hidden; N.nblk = n_blocks; N.n = n_classes;
-  const size_t np = (size_t)N.n_params(), H = (size_t)hidden, R = (size_t)max_rows;
-  GcslWs& W = b->W;
-  int rc = ILSX_OK;
-  float** bufs[] = {&N.P, &N.G, &N.M, &N.V};
-  for (float** p : bufs) if (rc == ILSX_OK) rc = bncat_alloc(b, p, np);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &N.rmean, n_blocks * H);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &N.rvar, n_blocks * H);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &W.X, R * in_dim);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, (float**)&W.label, R);
-  for (int l = 0; l < n_blocks && rc == ILSX_OK; ++l) {
-    rc = bncat_alloc(b, &W.ch[l], R * H);
-    if (rc == ILSX_OK) rc = bncat_alloc(b, &W.ah[l], R * H);
-    if (rc == ILSX_OK) rc = bncat_alloc(b, &W.h[l], R * H);
-    if (rc == ILSX_OK) rc = bncat_alloc(b, &W.p[l], R * H);
-    if (rc == ILSX_OK) rc = bncat_alloc(b, &W.s[l], H);
-  }
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &W.t0, R * H);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &W.t1, R * H);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &W.logit, R * n_classes);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &W.dlogit, R * n_classes);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &W.ce_row, R);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &W.correct, R);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &W.bstat, (size_t)n_blocks * 2 * H);
-  if (rc == ILSX_OK) rc = bncat_alloc(b, &b->stats, 2);
-  if (rc == ILSX_OK) {   // BatchNorm1d's initial running statistics: mean 0, variance 1 — on the ctx stream, behind the zeroing of the allocation
-    std::vector<float> ones((size_t)n_blocks * H, 1.0f);
-    hipError_t e = hipMemcpyAsync(N.rvar, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ilsx_set_err("ilsx_bncat_create: %s", hipGetErrorString(e)); rc = ILSX_ERR_HIP; }
-  }
+  int rc = bncat_setup(b);
   if (rc != ILSX_OK) { ilsx_bncat_destroy(b); return rc; }
   *out = b;
   return ILSX_OK;
@@ -236,11 +229,14 @@ struct ilsx_gcsl {
   ilsx_bc* bc = nullptr;       // MSE
   int a = 0;                   // MSE: action width
   float *X = nullptr, *act = nullptr, *zeros = nullptr;   // MSE: gathered input, actions, the BC trainer's (zero) noise
+  DevOwner own;
 };
 
 extern "C" int ilsx_gcsl_destroy(ilsx_gcsl* g) {
   if (!g) return ILSX_OK;
-  for (float* p : {g->X, g->act, g->zeros}) if (p) ctx_free(g->ctx, p);
+  hipSetDevice(g->ctx->device);
+  hipStreamSynchronize(g->ctx->stream);
+  g->own.release();
   delete g;
   return ILSX_OK;
 }
@@ -257,12 +253,12 @@ extern "C" int ilsx_gcsl_create(ilsx_ctx* ctx, const ilsx_gcsl_cfg* cfg, ilsx_bn
   if (bc && act_dim < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_gcsl_create: act_dim=%d", act_dim);
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_gcsl* g = new ilsx_gcsl();
-  g->ctx = ctx; g->cfg = *cfg; g->cat = cat; g->bc = bc; g->a = act_dim;
+  g->ctx = g->own.ctx = ctx; g->cfg = *cfg; g->cat = cat; g->bc = bc; g->a = act_dim;
   if (bc) {
     const size_t B = (size_t)cfg->max_batch;
-    int rc = ctx_alloc(ctx, B * D * sizeof(float), (void**)&g->X, true);
-    if (rc == ILSX_OK) rc = ctx_alloc(ctx, B * act_dim * sizeof(float), (void**)&g->act, true);
-    if (rc == ILSX_OK) rc = ctx_alloc(ctx, B * act_dim * sizeof(float), (void**)&g->zeros, true);
+    int rc = g->own.alloc(&g->X, B * D);
+    if (rc == ILSX_OK) rc = g->own.alloc(&g->act, B * act_dim);
+    if (rc == ILSX_OK) rc = g->own.alloc(&g->zeros, B * act_dim);
     if (rc != ILSX_OK) { ilsx_gcsl_destroy(g); return rc; }
   }
   *out = g;

@@ -250,6 +250,7 @@ __global__ void k_ppo_refresh(PpoScalars* sc, int which, float v_lr, float p_lr)
 // ------------------------------------------------------------------------------------------------ host
 struct ilsx_ppo {
   ilsx_ctx* ctx = nullptr;
+  DevOwner own;
   ilsx_ppo_cfg cfg;
   NetLayout Lp, Lv;
   int o = 0, a = 0, N = 0;
@@ -280,13 +281,42 @@ static int ppo_refresh(ilsx_ppo* p, int which) {
   return ILSX_OK;
 }
 
+// arenas, workspaces and the weight-gradient table of a new trainer
+static int ppo_setup(ilsx_ppo* p) {
+  const ilsx_ppo_cfg* cfg = &p->cfg;
+  const size_t N = (size_t)cfg->max_samples, mb = (size_t)cfg->mini_batch_size, H = (size_t)cfg->hidden;
+  DevOwner& own = p->own;
+  p->nv_pad = (p->nv + 63) / 64 * 64;
+  ILSX_TRY(own.alloc(&p->Pp, p->np));
+  ILSX_TRY(own.alloc(&p->Gv, p->nv_pad + p->np));   // Gv | Gp in one allocation: one weight-gradient table, one all-reduce in a split run
+  p->Gp = p->Gv + p->nv_pad;
+  ILSX_TRY(own.alloc(&p->Mp, p->np)); ILSX_TRY(own.alloc(&p->Vp, p->np));
+  ILSX_TRY(own.alloc(&p->Pv, p->nv)); ILSX_TRY(own.alloc(&p->Mv, p->nv)); ILSX_TRY(own.alloc(&p->Vv, p->nv));
+  ILSX_TRY(own.alloc(&p->sc, 1));
+  ILSX_TRY(own.alloc(&p->values, N)); ILSX_TRY(own.alloc(&p->returns, N)); ILSX_TRY(own.alloc(&p->adv, N)); ILSX_TRY(own.alloc(&p->lp_old, N));
+  ILSX_TRY(own.alloc(&p->xv, mb * p->Lv.KP)); ILSX_TRY(own.alloc(&p->xp, mb * p->Lp.KP));
+  for (int l = 0; l < cfg->n_hidden; ++l) {
+    ILSX_TRY(own.alloc(&p->hv[l], mb * H)); ILSX_TRY(own.alloc(&p->dv[l], mb * H));
+    ILSX_TRY(own.alloc(&p->hp[l], mb * H)); ILSX_TRY(own.alloc(&p->dp[l], mb * H));
+  }
+  ILSX_TRY(own.alloc(&p->dhv, mb)); ILSX_TRY(own.alloc(&p->vpred, mb));
+  ILSX_TRY(own.alloc(&p->dhp, mb * p->no())); ILSX_TRY(own.alloc(&p->mu, mb * p->no()));
+  ILSX_TRY(own.alloc(&p->lp, mb)); ILSX_TRY(own.alloc(&p->aux, mb * p->a));
+  ILSX_TRY(own.alloc(&p->partial, 64 + 64 * PPO_MAX_A));
+  ILSX_TRY(own.alloc(&p->offs, N + 1)); ILSX_TRY(own.alloc(&p->perm, N));
+  memset(&p->jobs_vp, 0, sizeof p->jobs_vp);
+  ILSX_TRY(build_dw_jobs(p->Lv, p->Gv, p->xv, p->hv, p->dv, p->dhv, &p->jobs_vp));
+  ILSX_TRY(build_dw_jobs(p->Lp, p->Gp, p->xp, p->hp, p->dp, p->dhp, &p->jobs_vp));
+  return ppo_refresh(p, -1);
+}
+
 extern "C" int ilsx_ppo_create(ilsx_ctx* ctx, const ilsx_ppo_cfg* cfg, ilsx_ppo** out) {
   if (!ctx || !cfg || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_ppo_create: NULL argument");
   if (cfg->max_samples < 1 || cfg->mini_batch_size < 1) ILSX_FAIL(ILSX_ERR_ARG, "max_samples / mini_batch_size must be >= 1");
   if (cfg->act_dim > PPO_MAX_A) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "act_dim %d > %d", cfg->act_dim, PPO_MAX_A);
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_ppo* p = new ilsx_ppo();
-  p->ctx = ctx; p->cfg = *cfg; p->o = cfg->obs_dim; p->a = cfg->act_dim;
+  p->ctx = p->own.ctx = ctx; p->cfg = *cfg; p->o = cfg->obs_dim; p->a = cfg->act_dim;
   if (p->cfg.grad_world < 1) p->cfg.grad_world = 1;
   ilsx_mlp_cfg mp = {cfg->obs_dim, cfg->n_hidden, cfg->hidden, cfg->act_dim, cfg->conditioned_std ? 2 : 1, ILSX_ACT_TANH,
                      {cfg->hidden_sizes[0], cfg->hidden_sizes[1], cfg->hidden_sizes[2]}};
@@ -296,44 +326,8 @@ extern "C" int ilsx_ppo_create(ilsx_ctx* ctx, const ilsx_ppo_cfg* cfg, ilsx_ppo*
   if (rc != ILSX_OK) { delete p; return rc; }
   p->np = p->Lp.n_int + ((p->n_ls() + 3) / 4) * 4;
   p->nv = p->Lv.n_int;
-  const size_t N = (size_t)cfg->max_samples, mb = (size_t)cfg->mini_batch_size, H = (size_t)cfg->hidden;
-  auto A = [&](float** q, size_t cnt) { return ctx_alloc(ctx, cnt * sizeof(float), (void**)q, true); };
-  p->nv_pad = (p->nv + 63) / 64 * 64;
-  rc = A(&p->Pp, p->np);
-  if (rc == ILSX_OK) rc = A(&p->Gv, p->nv_pad + p->np);   // Gv | Gp in one allocation: one weight-gradient table, one all-reduce in a split run
-  if (rc == ILSX_OK) p->Gp = p->Gv + p->nv_pad;
-  if (rc == ILSX_OK) rc = A(&p->Mp, p->np);
-  if (rc == ILSX_OK) rc = A(&p->Vp, p->np);
-  if (rc == ILSX_OK) rc = A(&p->Pv, p->nv);
-  if (rc == ILSX_OK) rc = A(&p->Mv, p->nv);
-  if (rc == ILSX_OK) rc = A(&p->Vv, p->nv);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, sizeof(PpoScalars), (void**)&p->sc);
-  if (rc == ILSX_OK) rc = A(&p->values, N);
-  if (rc == ILSX_OK) rc = A(&p->returns, N);
-  if (rc == ILSX_OK) rc = A(&p->adv, N);
-  if (rc == ILSX_OK) rc = A(&p->lp_old, N);
-  if (rc == ILSX_OK) rc = A(&p->xv, mb * p->Lv.KP);
-  if (rc == ILSX_OK) rc = A(&p->xp, mb * p->Lp.KP);
-  for (int l = 0; l < cfg->n_hidden && rc == ILSX_OK; ++l) {
-    rc = A(&p->hv[l], mb * H);
-    if (rc == ILSX_OK) rc = A(&p->dv[l], mb * H);
-    if (rc == ILSX_OK) rc = A(&p->hp[l], mb * H);
-    if (rc == ILSX_OK) rc = A(&p->dp[l], mb * H);
-  }
-  if (rc == ILSX_OK) rc = A(&p->dhv, mb);
-  if (rc == ILSX_OK) rc = A(&p->vpred, mb);
-  if (rc == ILSX_OK) rc = A(&p->dhp, mb * p->no());
-  if (rc == ILSX_OK) rc = A(&p->mu, mb * p->no());
-  if (rc == ILSX_OK) rc = A(&p->lp, mb);
-  if (rc == ILSX_OK) rc = A(&p->aux, mb * p->a);
-  if (rc == ILSX_OK) rc = A(&p->partial, 64 + 64 * PPO_MAX_A);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, (N + 1) * sizeof(int), (void**)&p->offs);
-  if (rc == ILSX_OK) rc = ctx_alloc(ctx, N * sizeof(int), (void**)&p->perm);
-  if (rc != ILSX_OK) { delete p; return rc; }
-  memset(&p->jobs_vp, 0, sizeof p->jobs_vp);
-  ILSX_TRY(build_dw_jobs(p->Lv, p->Gv, p->xv, p->hv, p->dv, p->dhv, &p->jobs_vp));
-  ILSX_TRY(build_dw_jobs(p->Lp, p->Gp, p->xp, p->hp, p->dp, p->dhp, &p->jobs_vp));
-  ILSX_TRY(ppo_refresh(p, -1));
+  rc = ppo_setup(p);
+  if (rc != ILSX_OK) { ilsx_ppo_destroy(p); return rc; }
   *out = p;
   return ILSX_OK;
 }
@@ -342,7 +336,7 @@ extern "C" int ilsx_ppo_destroy(ilsx_ppo* p) {
   if (!p) return ILSX_OK;
   hipSetDevice(p->ctx->device);
   hipStreamSynchronize(p->ctx->stream);
-  // arenas and workspaces are released with the ctx
+  p->own.release();
   delete p;
   return ILSX_OK;
 }
@@ -522,7 +516,7 @@ static int ppo_minibatch(ilsx_ppo* p, const float* obs, const float* act, const 
     bp.aux = p->cond() ? nullptr : p->aux; bp.clip_eps = p->cfg.clip_eps;
     ILSX_TRY(launch_bwd_dx(ctx, Bw, H, ILSX_ACT_TANH));
   }
-  ILSX_TRY(launch_bwd_dw(ctx, p->jobs_vp, rows, nullptr));
+  ILSX_TRY(launch_bwd_dw(ctx, p->own, p->jobs_vp, rows, nullptr));
   PpoNormArgs Nn;
   Nn.G = p->Gp; Nn.n = (int)p->Lp.n_int;
   for (int l = 1; l <= 2; ++l) {

@@ -52,13 +52,14 @@ struct SacCollector { std::vector<SacLaunch> L; };
 
 struct ilsx_sac {
   ilsx_ctx* ctx = nullptr;
+  DevOwner own;   // the slab and the lazily allocated records (tail_dev, snap, vote)
   SacCollector* col = nullptr;
   ilsx_sac_cfg cfg;
   ilsx_net *pi = nullptr, *q1 = nullptr, *q2 = nullptr;
   NetLayout Lq, Lp;
   int o = 0, a = 0;
   size_t nq = 0, np = 0;     // internal floats per critic / policy
-  void* slab = nullptr;      // the agent's one device allocation: scal | P | G | M | V | workspace
+  void* slab = nullptr;      // scal | P | G | M | V | workspace in one device allocation
   float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
   DevScalars* scal = nullptr;
   SacWs ws;
@@ -279,40 +280,11 @@ static void sac_plan_ws(ilsx_sac* s, Slab& L) {
   if (s->cs == 4 && H == 256 && std::max(s->Lq.KP, s->Lp.KP) >= thr) A(&s->h0scr, 4 * B * H);
 }
 
-extern "C" int ilsx_sac_create(ilsx_ctx* ctx, const ilsx_sac_cfg* cfg, ilsx_net* pi, ilsx_net* q1, ilsx_net* q2,
-                               ilsx_sac** out) {
-  if (!ctx || !cfg || !pi || !q1 || !q2 || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_sac_create: NULL argument");
-  if (pi->ctx != ctx || q1->ctx != ctx || q2->ctx != ctx) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_sac_create: nets belong to another ctx");
-  const ilsx_mlp_cfg &cp = pi->lay.cfg, &c1 = q1->lay.cfg, &c2 = q2->lay.cfg;
-  if (cp.n_heads != 2) ILSX_FAIL(ILSX_ERR_ARG, "policy must have 2 heads (mean | log_std), policies.py:231-239");
-  if (c1.n_heads != 1 || c1.out_dim != 1 || memcmp(&c1, &c2, sizeof c1) != 0)
-    ILSX_FAIL(ILSX_ERR_ARG, "qf1/qf2 must be identical single-output FlattenMlp's");
-  if (c1.in_dim != cp.in_dim + cp.out_dim) ILSX_FAIL(ILSX_ERR_ARG, "qf input %d != obs %d + act %d", c1.in_dim, cp.in_dim, cp.out_dim);
-  if (c1.hidden != cp.hidden || c1.n_hidden != cp.n_hidden || c1.act != cp.act)
-    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "policy and critics must share hidden width/depth/activation");
-  if (!pi->owns || !q1->owns || !q2->owns) ILSX_FAIL(ILSX_ERR_STATE, "a network already belongs to an agent");
-  if (cfg->max_batch < 1 || cfg->max_batch > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "max_batch=%d out of range", cfg->max_batch);
-  HIPCHK(hipSetDevice(ctx->device));
-  ilsx_sac* s = new ilsx_sac();
-  s->ctx = ctx; s->cfg = *cfg; s->pi = pi; s->q1 = q1; s->q2 = q2;
-  if (s->cfg.grad_world < 1) s->cfg.grad_world = 1;
-  s->Lq = q1->lay; s->Lp = pi->lay;
-  s->o = cp.in_dim; s->a = cp.out_dim;
-  s->nq = s->Lq.n_int; s->np = s->Lp.n_int;
-  s->cs = getenv("ILSX_NO_SPLIT") ? 1 : mlp2_split_factor(cp.n_hidden, cp.hidden);
-  s->target_entropy = cfg->has_target_entropy ? cfg->target_entropy : -(float)s->a / 2.0f;  // sac_alpha.py:56-58
-  s->rng_stream = ctx->next_rng_stream;
-  ctx->next_rng_stream += 2;
-  const size_t nP = 4 * s->nq + s->np, nT = 2 * s->nq + s->np;
-  Slab L;   // parameters, optimiser state, scalars and the whole step workspace: one allocation (see Slab)
-  L.add(&s->scal, 1);
-  L.add(&s->P, nP); L.add(&s->G, nT + 4); L.add(&s->M, nT); L.add(&s->V, nT);
-  L.add(&s->phase_flags, (size_t)PHASE_FLAG_WORDS); L.add(&s->phase_err, 32);
-  sac_plan_ws(s, L);
-  int rc = L.commit(ctx, &s->slab);
-  if (rc != ILSX_OK) { delete s; return rc; }
+// what ilsx_sac_create does once the slab stands: parameters in, networks adopted, scalars and weight-gradient tables
+static int sac_setup(ilsx_sac* s) {
   // adopt the networks' storage: copy into the arena, targets = copies (sac_alpha.py:60-61)
-  hipStream_t st = ctx->stream;
+  ilsx_net *pi = s->pi, *q1 = s->q1, *q2 = s->q2;
+  hipStream_t st = s->ctx->stream;
   HIPCHK(hipMemcpyAsync(s->base(W_Q1), q1->base, s->nq * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(s->base(W_Q2), q2->base, s->nq * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(s->base(W_PI), pi->base, s->np * 4, hipMemcpyDeviceToDevice, st));
@@ -321,14 +293,10 @@ extern "C" int ilsx_sac_create(ilsx_ctx* ctx, const ilsx_sac_cfg* cfg, ilsx_net*
   HIPCHK(hipStreamSynchronize(st));
   ilsx_net* nets[3] = {pi, q1, q2};
   const int wh[3] = {W_PI, W_Q1, W_Q2};
-  for (int i = 0; i < 3; ++i) {
-    ILSX_TRY(ctx_free(ctx, nets[i]->base));
-    nets[i]->base = s->base(wh[i]);
-    nets[i]->owns = false;
-  }
+  for (int i = 0; i < 3; ++i) ILSX_TRY(net_adopt(nets[i], s->base(wh[i])));
   DevScalars h;
   memset(&h, 0, sizeof h);
-  h.log_alpha = std::log((double)cfg->alpha);  // sac_alpha.py:51-53 (np.log -> float64)
+  h.log_alpha = std::log((double)s->cfg.alpha);  // sac_alpha.py:51-53 (np.log -> float64)
   h.alpha = (float)std::exp(h.log_alpha);
   h.alpha_used = h.alpha;
   h.log_alpha_used = h.log_alpha;
@@ -344,6 +312,42 @@ extern "C" int ilsx_sac_create(ilsx_ctx* ctx, const ilsx_sac_cfg* cfg, ilsx_net*
   s->jobs_q.zero_flags = s->phase_flags;   // each dW launch re-arms the arrival counters of the phase launch that follows it
   s->jobs_p.zero_flags = s->phase_flags;
   s->jobs_q.zero_err = s->phase_err; s->jobs_p.zero_err = s->phase_err;
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_sac_create(ilsx_ctx* ctx, const ilsx_sac_cfg* cfg, ilsx_net* pi, ilsx_net* q1, ilsx_net* q2,
+                               ilsx_sac** out) {
+  if (!ctx || !cfg || !pi || !q1 || !q2 || !out) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_sac_create: NULL argument");
+  if (pi->ctx != ctx || q1->ctx != ctx || q2->ctx != ctx) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_sac_create: nets belong to another ctx");
+  const ilsx_mlp_cfg &cp = pi->lay.cfg, &c1 = q1->lay.cfg, &c2 = q2->lay.cfg;
+  if (cp.n_heads != 2) ILSX_FAIL(ILSX_ERR_ARG, "policy must have 2 heads (mean | log_std), policies.py:231-239");
+  if (c1.n_heads != 1 || c1.out_dim != 1 || memcmp(&c1, &c2, sizeof c1) != 0)
+    ILSX_FAIL(ILSX_ERR_ARG, "qf1/qf2 must be identical single-output FlattenMlp's");
+  if (c1.in_dim != cp.in_dim + cp.out_dim) ILSX_FAIL(ILSX_ERR_ARG, "qf input %d != obs %d + act %d", c1.in_dim, cp.in_dim, cp.out_dim);
+  if (c1.hidden != cp.hidden || c1.n_hidden != cp.n_hidden || c1.act != cp.act)
+    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "policy and critics must share hidden width/depth/activation");
+  if (!pi->owns || !q1->owns || !q2->owns) ILSX_FAIL(ILSX_ERR_STATE, "a network already belongs to an agent");
+  if (cfg->max_batch < 1 || cfg->max_batch > (1 << 20)) ILSX_FAIL(ILSX_ERR_ARG, "max_batch=%d out of range", cfg->max_batch);
+  HIPCHK(hipSetDevice(ctx->device));
+  ilsx_sac* s = new ilsx_sac();
+  s->ctx = s->own.ctx = ctx; s->cfg = *cfg; s->pi = pi; s->q1 = q1; s->q2 = q2;
+  if (s->cfg.grad_world < 1) s->cfg.grad_world = 1;
+  s->Lq = q1->lay; s->Lp = pi->lay;
+  s->o = cp.in_dim; s->a = cp.out_dim;
+  s->nq = s->Lq.n_int; s->np = s->Lp.n_int;
+  s->cs = getenv("ILSX_NO_SPLIT") ? 1 : mlp2_split_factor(cp.n_hidden, cp.hidden);
+  s->target_entropy = cfg->has_target_entropy ? cfg->target_entropy : -(float)s->a / 2.0f;  // sac_alpha.py:56-58
+  s->rng_stream = ctx->next_rng_stream;
+  ctx->next_rng_stream += 2;
+  const size_t nP = 4 * s->nq + s->np, nT = 2 * s->nq + s->np;
+  Slab L;   // parameters, optimiser state, scalars and the whole step workspace: one allocation (see Slab)
+  L.add(&s->scal, 1);
+  L.add(&s->P, nP); L.add(&s->G, nT + 4); L.add(&s->M, nT); L.add(&s->V, nT);
+  L.add(&s->phase_flags, (size_t)PHASE_FLAG_WORDS); L.add(&s->phase_err, 32);
+  sac_plan_ws(s, L);
+  int rc = s->own.commit(L, &s->slab);
+  if (rc == ILSX_OK) rc = sac_setup(s);
+  if (rc != ILSX_OK) { ilsx_sac_destroy(s); return rc; }
   *out = s;
   return ILSX_OK;
 }
@@ -360,23 +364,8 @@ extern "C" int ilsx_sac_destroy(ilsx_sac* s) {
     v.erase(std::remove(v.begin(), v.end(), s->pct.slot), v.end());
     s->pct.slot = -1;
   }
-  if (s->tail_dev) ctx_free(s->ctx, s->tail_dev);
-  if (s->snap) ctx_free(s->ctx, s->snap);
-  if (s->vote) ctx_free(s->ctx, s->vote);
-  // give the networks private storage back so their handles stay usable
-  ilsx_net* nets[3] = {s->pi, s->q1, s->q2};
-  const int wh[3] = {W_PI, W_Q1, W_Q2};
-  for (int i = 0; i < 3; ++i) {
-    float* nb = nullptr;
-    if (ctx_alloc(s->ctx, nets[i]->lay.n_int * 4, (void**)&nb, false) == ILSX_OK) {
-      hipMemcpyAsync(nb, s->base(wh[i]), nets[i]->lay.n_int * 4, hipMemcpyDeviceToDevice, s->ctx->stream);
-      hipStreamSynchronize(s->ctx->stream);
-      nets[i]->base = nb;
-      nets[i]->owns = true;
-    }
-  }
-  // workspace / arenas are released with the ctx (ctx owns every allocation); free the big ones now
-  ctx_free(s->ctx, s->slab);
+  for (ilsx_net* n : {s->pi, s->q1, s->q2}) net_give_back(n);   // private storage back: their handles stay usable
+  s->own.release();
   delete s;
   return ILSX_OK;
 }
@@ -446,7 +435,7 @@ static int sac_bwd(ilsx_sac* s, const BwdArgs& A, int H, int act, int cs) {
   return ILSX_OK;
 }
 static int sac_dw(ilsx_sac* s, const DwArgs& table, int rows, const AdamFuse* F) {
-  if (!s->col) return launch_bwd_dw(s->ctx, table, rows, F);
+  if (!s->col) return launch_bwd_dw(s->ctx, s->own, table, rows, F);
   SacLaunch l; memset(&l, 0, sizeof l); l.kind = 2; l.d = table; l.F = *F;
   s->col->L.push_back(l);
   return ILSX_OK;
@@ -731,7 +720,7 @@ static int sac_split_on_phase(ilsx_sac* s, int B, bool* on) {
   if (!(s->ctx->comm && s->ctx->comm_n > 1)) return ILSX_OK;
   if (getenv("ILSX_SPLIT_PHASE") == nullptr) { *on = false; return ILSX_OK; }
   hipStream_t st = s->ctx->stream;
-  if (!s->vote) ILSX_TRY(ctx_alloc(s->ctx, 4 * sizeof(float), (void**)&s->vote, true));
+  if (!s->vote) ILSX_TRY(s->own.alloc(&s->vote, 4));
   float v = mine ? 0.0f : 1.0f;
   HIPCHK(hipMemcpyAsync(s->vote, &v, sizeof v, hipMemcpyHostToDevice, st));
   ILSX_TRY(comm_allreduce_sum(s->ctx, s->vote, 1));
@@ -750,7 +739,7 @@ static int sac_defer_begin(ilsx_sac* s, int B) {
     ILSX_TRY(sac_split_on_phase(s, B, &on));
     if (!on) return ILSX_OK;
   }
-  if (!s->tail_dev) ILSX_TRY(ctx_alloc(s->ctx, sizeof(TailLite), (void**)&s->tail_dev));
+  if (!s->tail_dev) ILSX_TRY(s->own.alloc(&s->tail_dev, 1));
   if (s->tail_B != B || s->tail_split != split) {
     const TailLite t = sac_tail_lite(s, B);
     HIPCHK(hipMemcpyAsync(s->tail_dev, &t, sizeof t, hipMemcpyHostToDevice, s->ctx->stream));
@@ -961,7 +950,7 @@ static bool sac_phase_possible(ilsx_sac* s, int B) {   // as sac_phase_ok, for t
 static size_t sac_snap_range(const ilsx_sac* s) { return (size_t)((const char*)(s->V + (2 * s->nq + s->np)) - (const char*)s->scal); }
 int sac_snapshot_take(ilsx_sac* s) {
   const size_t n = sac_snap_range(s);
-  if (!s->snap) { ILSX_TRY(ctx_alloc(s->ctx, n, &s->snap, false)); s->snap_bytes = n; }
+  if (!s->snap) { ILSX_TRY(s->own.alloc_bytes(&s->snap, n, false)); s->snap_bytes = n; }
   HIPCHK(hipMemcpyAsync(s->snap, s->scal, n, hipMemcpyDeviceToDevice, s->ctx->stream));
   s->snap_valid = true;
   return ILSX_OK;
@@ -997,7 +986,7 @@ static int sac_phase_check(ilsx_sac* s, int B, bool deferred, const char* who, b
     if (sac_is_split(s) && s->ctx->comm && s->ctx->comm_n > 1) {
       // a split run rolls back on EVERY rank or on none: a window re-run on one rank alone would issue collectives the others never join.
       // One float per rank through the run's own communicator, once per window (not per step); nothing to vote on at one rank.
-      if (!s->vote) ILSX_TRY(ctx_alloc(s->ctx, 4 * sizeof(float), (void**)&s->vote, true));
+      if (!s->vote) ILSX_TRY(s->own.alloc(&s->vote, 4));
       float v = err ? 1.0f : 0.0f;
       HIPCHK(hipMemcpyAsync(s->vote, &v, sizeof v, hipMemcpyHostToDevice, st));
       ILSX_TRY(comm_allreduce_sum(s->ctx, s->vote, 1));
@@ -1392,6 +1381,7 @@ extern "C" int ilsx_sac_debug_last_batch(ilsx_sac* s, int B, float* obs, float* 
 // 9K, and each launch brings K times the workgroups to hide the dependent-load latency that bounds the single step.
 struct ilsx_sac_group {
   ilsx_ctx* ctx = nullptr;
+  DevOwner own;   // the stages' descriptor tables, tails_lite, and the row-range scratch of the grouped weight-gradient launches
   std::vector<ilsx_sac*> agents;
   std::vector<ilsx_replay*> rbs;
   int B = 0;
@@ -1413,16 +1403,15 @@ struct ilsx_sac_group {
 };
 
 template <class T>
-static int upload_table(ilsx_ctx* ctx, const std::vector<T>& v, void** dev) {
-  ILSX_TRY(ctx_alloc(ctx, v.size() * sizeof(T), dev, false));
-  HIPCHK(hipMemcpyAsync(*dev, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+static int upload_table(DevOwner& own, const std::vector<T>& v, void** dev) {
+  ILSX_TRY(own.alloc_bytes(dev, v.size() * sizeof(T), false));
+  HIPCHK(hipMemcpyAsync(*dev, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, own.ctx->stream));
   return ILSX_OK;
 }
 
 static void group_release_tables(ilsx_sac_group* g) {
   for (auto& st : g->stages) {
-    for (void* p : {st.tasks, st.gtiles, st.tails})
-      if (p) ctx_free(g->ctx, p);
+    for (void* p : {st.tasks, st.gtiles, st.tails}) g->own.free(p);
     if (st.cslot >= 0) grp_const_free(g->ctx->device, st.kind == 0, st.cslot);
   }
   g->stages.clear();
@@ -1466,7 +1455,7 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
         }
       }
       st.ntasks = (int)tasks.size();
-      ILSX_TRY(upload_table(g->ctx, tasks, &st.tasks));
+      ILSX_TRY(upload_table(g->own, tasks, &st.tasks));
       st.f.tasks = (const FwdTaskG*)st.tasks; st.f.ntasks = st.ntasks;
       if (use_const && grp_const_alloc(g->ctx->device, true, st.ntasks, &st.cslot) == 0) {   // the same records in constant memory (kernels.h GRP == 2)
         ILSX_TRY(grp_const_upload(g->ctx, true, st.cslot, tasks.data(), tasks.size()));
@@ -1483,7 +1472,7 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
         for (int t = 0; t < A.ntasks; ++t) { BwdTask T = A.t[t]; T.scal = A.scal; tasks.push_back(T); }
       }
       st.ntasks = (int)tasks.size();
-      ILSX_TRY(upload_table(g->ctx, tasks, &st.tasks));
+      ILSX_TRY(upload_table(g->own, tasks, &st.tasks));
       st.b.tasks = (const BwdTask*)st.tasks; st.b.ntasks = st.ntasks;
       if (use_const && grp_const_alloc(g->ctx->device, false, st.ntasks, &st.cslot) == 0) {
         ILSX_TRY(grp_const_upload(g->ctx, false, st.cslot, tasks.data(), tasks.size()));
@@ -1532,21 +1521,21 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
         }
       }
       st.d.ntiles = tiles; st.d.nmat = nmat;
-      ILSX_TRY(upload_table(g->ctx, gt, &st.gtiles));
+      ILSX_TRY(upload_table(g->own, gt, &st.gtiles));
       st.d.gtiles = (const DwTileG*)st.gtiles;
       st.d.g_lo = nullptr;   // never the row-split path (B is the SAC batch)
     } else {
       std::vector<SacTailItem> items;
       for (int k = 0; k < K; ++k) items.push_back(cols[k].L[i].t);
-      ILSX_TRY(upload_table(g->ctx, items, &st.tails));
+      ILSX_TRY(upload_table(g->own, items, &st.tails));
     }
   }
   {
     std::vector<TailLite> lite;
     for (int k = 0; k < K; ++k) lite.push_back(sac_tail_lite(g->agents[k], B));
-    if (g->tails_lite) ctx_free(g->ctx, g->tails_lite);
+    g->own.free(g->tails_lite);
     g->tails_lite = nullptr;
-    ILSX_TRY(upload_table(g->ctx, lite, (void**)&g->tails_lite));
+    ILSX_TRY(upload_table(g->own, lite, (void**)&g->tails_lite));
   }
   HIPCHK(hipStreamSynchronize(g->ctx->stream));
   g->rbs.assign(rbs, rbs + K);
@@ -1592,7 +1581,7 @@ static int group_launch_step(ilsx_sac_group* g) {
       ILSX_TRY(launch_fwd(g->ctx, A, H, act, st.KP, cs));
     }
     else if (st.kind == 1) { BwdArgs A = st.b; A.mt = g->mt; A.swz.agents = K; A.late = g->late; ILSX_TRY(launch_bwd_dx(g->ctx, A, H, act, cs)); }
-    else if (st.kind == 2) { AdamFuse on; memset(&on, 0, sizeof on); on.on = 1; ILSX_TRY(launch_bwd_dw(g->ctx, st.d, g->B, &on)); }
+    else if (st.kind == 2) { AdamFuse on; memset(&on, 0, sizeof on); on.on = 1; ILSX_TRY(launch_bwd_dw(g->ctx, g->own, st.d, g->B, &on)); }
     else if (!g->defer) ILSX_TRY(group_launch_tail(g, st.tails, 0));
   }
   return ILSX_OK;
@@ -1613,7 +1602,7 @@ extern "C" int ilsx_sac_group_create(ilsx_ctx* ctx, ilsx_sac* const* agents, int
       ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "agents of a group must have identical network shapes and max_batch");
   }
   ilsx_sac_group* g = new ilsx_sac_group();
-  g->ctx = ctx;
+  g->ctx = g->own.ctx = ctx;
   g->agents.assign(agents, agents + n_agents);
   HIPCHK(hipSetDevice(ctx->device));
   for (int k = 0; k < n_agents; ++k) {
@@ -1656,8 +1645,8 @@ extern "C" int ilsx_sac_group_destroy(ilsx_sac_group* g) {
   if (!g) return ILSX_OK;
   hipSetDevice(g->ctx->device);
   hipStreamSynchronize(g->ctx->stream);
-  group_release_tables(g);
-  if (g->tails_lite) ctx_free(g->ctx, g->tails_lite);
+  group_release_tables(g);   // (the constant-table slots and the graph go with them)
+  g->own.release();
   for (hipEvent_t ev : g->peer_events) hipEventDestroy(ev);
   if (g->done_event) hipEventDestroy(g->done_event);
   delete g;

@@ -377,6 +377,11 @@ class GCSL(DeviceTrainer):
             self.policy.set_device_flat_params(snap["policy"]["params"])
             self._bc._set_opt(snap["policy"]["optimizer"])
 
+    def close(self):
+        super().close()
+        if self._bc is not None:   # MSE: the behaviour-cloning trainer this one steps
+            self._bc.close()
+
     def __del__(self):
         h = getattr(self, "h", None)
         if h is not None and h.value and getattr(self.ctx, "h", None):

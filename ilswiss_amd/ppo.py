@@ -80,6 +80,12 @@ class PPO(Trainer):
         policy._ppo = self
         self.eval_statistics = None
 
+    def close(self):
+        """ilsx_ppo_destroy, once.  Nothing to do when the context is closed already: it has freed the memory with its own."""
+        if self.h and self.ctx.h:
+            _lib.check(self.ctx.lib.ilsx_ppo_destroy(self.h))
+        self.h = None
+
     # ---- parameters (0 = policy: mean net | action_log_std ; 1 = value net)
     def _num(self, which):
         n = C.c_size_t()

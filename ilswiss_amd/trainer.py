@@ -80,6 +80,13 @@ class DeviceTrainer(Trainer):
         self.eval_statistics = None
         self._stats = self.Stats()
 
+    def close(self):
+        """ilsx_<ABI>_destroy, once: the object's device memory goes back to the context and the networks it adopted get storage of their
+        own again, so they stay usable.  Nothing to do when the context is closed already: it has freed the memory with its own."""
+        if self.h and self.ctx.h:
+            _lib.check(self._fn("destroy")(self.h))
+        self.h = None
+
     def _call(self, name, *args, keep=()):
         """ilsx_<ABI>_<name>(handle, *args, statistics): the statistics of the first step of the call are asked for and recorded when none
         are held since the last end_epoch.  `keep`: the staged device copies of host arrays among `args`; the call is asynchronous and only

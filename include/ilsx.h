@@ -137,6 +137,8 @@ typedef struct {
 } ilsx_mlp_cfg;
 
 int ilsx_net_create(ilsx_ctx* ctx, const ilsx_mlp_cfg* cfg, ilsx_net** out);
+/* ILSX_ERR_STATE (and the network stays alive) while an agent created around it exists: the agent's destroy writes through the
+ * network to give it storage of its own back — destroy the agent first. */
 int ilsx_net_destroy(ilsx_net* net);
 int ilsx_net_num_params(const ilsx_net* net, size_t* out);
 /* networks.py:57-83 + pytorch_util.py:20-29 init rule: hidden W ~ U(+-1/sqrt(out_features)),
