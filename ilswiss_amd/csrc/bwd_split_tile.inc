@@ -1,6 +1,5 @@
 // bwd_split_tile.inc — the column-split backward-to-activations of ONE 16-row tile slice, as TEXT (see fwd_split_tile.inc).
-// Names the including scope provides: template parameters H, ACT, CS; `constexpr bool XCH`; `constexpr int MT` (row tiles per workgroup, see
-// fwd_split_tile.inc: same MFMA chains per row tile for every MT, bit-identical results); `A` (BwdArgs), `T` (BwdTask), `bx`, `cs`, `smem`;
+// Names the including scope provides: template parameters H, ACT, CS; `constexpr bool XCH`; `A` (BwdArgs), `T` (BwdTask), `bx`, `cs`, `smem`;
 // `constexpr int LOSS_CT` (the stage's loss kind, -1 = T.loss at run time) and `constexpr int NO_CT` (head outputs, 0 = N.NO at run time).
 // A phase-kernel stage (XCH) with a compile-time loss runs the STATIC HEAD: no dispatch over the loss kinds, every descriptor field the head
 // and the delta_1 phase need read ahead of the waits (XCH_HOOK_*) and held in scalar registers, and every operand and sub-expression that
@@ -10,14 +9,14 @@
   constexpr int NTH = 4 * H / CS, NWV = NTH / 64, NC = H / 16, SLW = H / CS, RPW = 16 / NWV, KPL = SLW / 64;
   constexpr int RPT = 16 * H / NTH, RSTEP = NTH / H;   // delta_1: thread <-> one column, RPT rows RSTEP apart
   constexpr int LDH = H + ILSX_LDS_PAD, LDSL = SLW + ILSX_LDS_PAD;
-  constexpr int MR = 16 * MT;
+  constexpr int MT = 1;   // row tiles per workgroup: one.  The loops `for (m < MT)` below are kept as text (see fwd_split_tile.inc)
+  constexpr int MR = 16;
   static_assert(NTH % H == 0 && RPW >= 1 && KPL >= 1, "unsupported split geometry");
-  static_assert(MT == 1 || MT == 2 || MT == 4, "macro tile = 1, 2 or 4 row tiles");
   const NetView& N = T.net;
   constexpr bool SH = XCH && LOSS_CT >= 0;
   int NO = NO_CT > 0 ? NO_CT : N.NO;
   if constexpr (SH && NO_CT == 0) XCH_PIN(NO);
-  static_assert(!SH || (MT == 1 && (LOSS_CT == LOSS_SAC_CRITIC || LOSS_CT == LOSS_SAC_ACTORQ || LOSS_CT == LOSS_SAC_POLICY)), "static heads: the SAC step's three");
+  static_assert(!SH || LOSS_CT == LOSS_SAC_CRITIC || LOSS_CT == LOSS_SAC_ACTORQ || LOSS_CT == LOSS_SAC_POLICY, "static heads: the SAC step's three");
   static_assert(!SH || LOSS_CT == LOSS_SAC_POLICY || NO_CT == 1, "a critic has one head output");
   float* d1 = smem;                      // [MR][LDH]  delta_1, all H columns
   float* d0s = d1 + MR * LDH;            // [MR][LDSL] this slice of delta_0
@@ -27,7 +26,7 @@
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
   const int r0 = (bx >> A.xs) * MR, rows = A.rows;
   const bool lead = cs == 0;
-  // Whole (macro) tile inside the batch — workgroup-uniform: the saved-activation loads and the delta stores below then go without row
+  // Whole tile inside the batch — workgroup-uniform: the saved-activation loads and the delta stores below then go without row
   // guards and off one 64-bit address per run (the guarded form compiled to a compare, an EXEC branch and three address instructions per
   // element: ~200 of the backward's instructions per thread for the 16 h_1 loads alone)
   const bool full_tile = r0 + MR <= rows;
@@ -36,7 +35,7 @@
   // ---- operands of the later phases, requested first (they land while the loss head is evaluated)
   const int k1 = tid % H, rb1 = tid / H;
   const int lc = wave * 16 + li, col0 = cs * SLW + lc;
-  float h1v[MT > 1 ? 2 : 1][RPT];   // MT > 1: the next row tile's values are requested while this one's are used
+  float h1v[MT][RPT];
   float h0v[MT][4];
   float4 wreg[NC];
   // Order of the requests.  Ordinary launch: activations, small weights, the loss head, then the 64 KB burst of W_1 (so that the
@@ -99,9 +98,7 @@
 #pragma unroll
       for (int i = 0; i < RPT; ++i) h1v[0][i] = ldx<XCH>(xg<SH>(h1p + (size_t)(RSTEP * i) * H));
 #pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) h0v[m][v] = ldx<XCH>(xg<SH>(h0p + (size_t)(16 * m + v) * H));
+      for (int v = 0; v < 4; ++v) h0v[0][v] = ldx<XCH>(xg<SH>(h0p + (size_t)v * H));
     } else {
 #pragma unroll
       for (int i = 0; i < RPT; ++i) {
@@ -109,12 +106,10 @@
         h1v[0][i] = gr < rows ? ldx<XCH>(xg<SH>(h1p + (size_t)(RSTEP * i) * H)) : 0.0f;
       }
 #pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int gr = r0 + 16 * m + 4 * g + v;
-          h0v[m][v] = gr < rows ? ldx<XCH>(xg<SH>(h0p + (size_t)(16 * m + v) * H)) : 0.0f;
-        }
+      for (int v = 0; v < 4; ++v) {
+        const int gr = r0 + 4 * g + v;
+        h0v[0][v] = gr < rows ? ldx<XCH>(xg<SH>(h0p + (size_t)v * H)) : 0.0f;
+      }
     }
   }
   // ---- static head.  Per trip of the head loop (one trip while 16 NO <= NTH, a <= 8; thread <-> (row, output)): first the operands and
@@ -205,7 +200,7 @@
     dout[row * ILSX_MAX_NO + j] = d;
   }
   }
-  constexpr bool LATEW = GRP == 3 && MT == 1 && !XCH;
+  constexpr bool LATEW = GRP == 3 && !XCH;
   if constexpr (!XCH && !LATEW) {
   // ---- this wave's slice of W_1 (backward-packed: all H rows x its 16 columns), one coalesced burst
     {
@@ -219,13 +214,6 @@
   // ---- delta_1 = (dout Wh) * act'(h_1), full width on the VALU: thread <-> column k1
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
-    if (m + 1 < MT) {
-#pragma unroll
-      for (int i = 0; i < RPT; ++i) {
-        const int gr = r0 + 16 * (m + 1) + rb1 + RSTEP * i;
-        h1v[(m + 1) & 1][i] = gr < rows ? T.hsave[1][(size_t)gr * H + k1] : 0.0f;
-      }
-    }
     const float* Wh = SH ? sh_Wh : N.base + N.off_Wh;
     const float* dom = dout + 16 * m * ILSX_MAX_NO;
     float accd[RPT];
@@ -276,7 +264,7 @@
     if (full_tile) {
 #pragma unroll
       for (int i = 0; i < RPT; ++i) {
-        const float dv = accd[i] * act_grad_from_out<ACT>(h1v[m & 1][i]);
+        const float dv = accd[i] * act_grad_from_out<ACT>(h1v[m][i]);
         if (ds) xg<SH>(dsp)[(size_t)(RSTEP * i) * H] = dv;
         d1[(16 * m + rb1 + RSTEP * i) * LDH + k1] = dv;
       }
@@ -286,7 +274,7 @@
         const int row = 16 * m + rb1 + RSTEP * i, gr = r0 + row;
         float dv = 0.0f;
         if (gr < rows) {
-          dv = accd[i] * act_grad_from_out<ACT>(h1v[m & 1][i]);
+          dv = accd[i] * act_grad_from_out<ACT>(h1v[m][i]);
           if (ds) xg<SH>(dsp)[(size_t)(RSTEP * i) * H] = dv;
         }
         d1[row * LDH + k1] = dv;

@@ -76,7 +76,7 @@ __device__ __forceinline__ void lane_step_frame(const EnvStepArgs& A, const type
   float* const rew_p = A.rew ? A.rew + t : nullptr;
   unsigned char* const done_p = A.done ? A.done + t : nullptr;
   float* const cur_p = A.obs_cur ? A.obs_cur + (size_t)env * O : nullptr;
-  float* rec = nullptr;   // fused replay insert (k_env_step's record layout: obs | act | rew | done | next_obs | absorbing[2])
+  float* rec = nullptr;   // fused replay insert (the planar stepper's record layout: obs | act | rew | done | next_obs | absorbing[2])
   if (A.replay) {
     long long slot = A.top + env;
     if (slot >= A.cap) slot -= A.cap;
@@ -129,7 +129,7 @@ __device__ __forceinline__ void lane_step_frame(const EnvStepArgs& A, const type
   }
   if (auto_reset) {
     const double ret = ret0 + reward;
-    const bool end = terminal || limit || !finite;   // as k_env_step
+    const bool end = terminal || limit || !finite;   // as envg_step_dev
     if (end) {
       atomicAdd(&stats_p[0], 1.0);
       atomicAdd(&stats_p[1], ret);
@@ -461,7 +461,7 @@ __device__ void cartchain_dynamics(const CartChainDev& m, const double (&q)[NP +
   qfrc[0] = g0; qfrc[1] = g1;
 }
 
-// classic RK4 on (q, qd), env_substep's form: ONE dynamics call site in a 4-trip loop, sums in the order q + h/6 (k1 + 2 k2 + 2 k3 + k4).
+// classic RK4 on (q, qd), the planar stepper's form: ONE dynamics call site in a 4-trip loop, sums in the order q + h/6 (k1 + 2 k2 + 2 k3 + k4).
 // qfrc is left holding the constraint force of the last stage.
 template <int NP>
 __device__ __forceinline__ void cartchain_substep(const CartChainDev& m, double (&q)[NP + 1], double (&v)[NP + 1], double tau0,

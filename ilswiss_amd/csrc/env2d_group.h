@@ -1,7 +1,7 @@
 // env2d_group.h — the planar articulated-body stepper with SIXTEEN LANES PER ENV (Hopper, Walker2d, HalfCheetah).
 //
-// The first form (k_env_step in ilsx_env.hip, kept for A/B runs: ILSX_ENV2D_LANE=1) gives every env ONE lane: 4096 envs are 64
-// wavefronts on a chip with 1024 SIMDs, and a vec step lasts as long as one lane needs for 16 dynamics evaluations of dependent fp64
+// The first form (removed: DESIGN §27) gave every env ONE lane: 4096 envs were 64
+// wavefronts on a chip with 1024 SIMDs, and a vec step lasted as long as one lane needs for 16 dynamics evaluations of dependent fp64
 // arithmetic (0.9 ms: rocprofv3 — 165k instructions per wave per env step, half of the wave's cycles spent waiting on the previous
 // instruction's result), whatever the number of envs.  Here a DPP row of 16 lanes shares one env (4 envs per wavefront, one wavefront
 // per workgroup): lane l is degree of freedom l (0 = x, 1 = z, 2 + b = the hinge of body b), body l - 2, constraint row l and
@@ -493,7 +493,7 @@ __device__ __forceinline__ double eg_dynamics(const PlanarModelDev& m, double q,
   return dof ? qacc0 + w : 0.0;
 }
 
-// One vec-env step; the arguments, the reward / termination / record / auto-reset rules are those of k_env_step.
+// One vec-env step (EnvStepArgs): reward / termination (hopper.py:16-25, walker2d.py:17-20), the fused replay record, auto-reset.
 template <int NB, int MR>
 __device__ __forceinline__ void envg_step_dev(const EnvStepArgs& A) {
   constexpr int N = NB + 2;
@@ -541,7 +541,7 @@ __device__ __forceinline__ void envg_step_dev(const EnvStepArgs& A) {
   const unsigned long long eg_t1 = __builtin_amdgcn_s_memtime();
 #endif
   const double h = m.timestep;
-  for (int s = 0; s < m.frame_skip; ++s) {   // RK4, the oracle's accumulation order (env_substep)
+  for (int s = 0; s < m.frame_skip; ++s) {   // RK4, the oracle's accumulation order
     double qs = q, vs = v, qsum = 0.0, vsum = 0.0;
 #pragma unroll 1
     for (int stage = 0; stage < 4; ++stage) {
@@ -608,6 +608,9 @@ __device__ __forceinline__ void envg_step_dev(const EnvStepArgs& A) {
   if (A.auto_reset) {
     const int len = A.ep_len[env] + 1;
     const double ret = A.ep_ret[env] + reward;
+    // time-limit ends are NOT terminal (base_algorithm.py:264-277).  With no_terminal the reference overwrites `terminals` BEFORE it
+    // decides to reset (:195-196 ahead of :215), so an unhealthy env is stepped on until the time limit: the fallen states are visited
+    // and rewarded, which is what grounds their values in adversarial IRL.  A state that is no longer finite always resets.
     const bool end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;
     EG_SYNC();   // every lane has read ep_len / ep_ret
     if (end) {

@@ -1,4 +1,7 @@
 // env3d.h — device code of the 3-D articulated-body stepper (Ant-v2 / Humanoid-v2), included by ilsx_env.hip.
+// Since the lane-per-env kernels were removed this file is the REFERENCE STATEMENT of the stepper, not a launched kernel: the
+// model record, its host-side construction and the one-lane-per-env recursions that env3d_wave.h (the form that runs) includes and is
+// cross-checked against in the host build of both forms (tests/harness/env3d_host.cpp).
 //
 // Replaces the MuJoCo call under gym's AntEnv / HumanoidEnv.step (rlkit/envs/envs_dict.py:6,9); reward / termination /
 // observation / reset rules as restated in rlkit/envs/mujoco/humanoid.py:24-73 and ant.py:11-43.  The model and its solver are

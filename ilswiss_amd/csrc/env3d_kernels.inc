@@ -1,88 +1,7 @@
-// env3d_kernels.inc — the four kernels of the 3-D stepper (lane-per-env step / reset, wave-per-env step / reset), included by
-// ilsx_env.hip once per observation layout: E3K(name) names the kernels, E3K_TRUNC is e3_observe's / e3w_observe's TRUNC (0: the full
-// observation, kernels k_env3d_*; 1: qpos[2:] | qvel of the *_trunc_obs tasks, kernels k_env3d_*_trunc).  Two inclusions of one text rather
-// than one templated body: the full-observation kernels compile to the instructions they had before the truncated tasks existed.
-__global__ __launch_bounds__(64) void E3K(k_env3d_step)(const EnvStepArgs A, const Spatial3Dev* mp, double* scr) {
-  const Spatial3Dev& m = *mp;
-  const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= A.n_ids) return;
-  const int env = A.ids ? A.ids[t] : t, n_env = A.n_env;
-  if (A.frozen && A.frozen[env]) return;
-  const E3Ctx C{scr, n_env, env, mp};
-  const int o = m.obs_dim, na = m.n_act;
-  for (int i = 0; i < m.nq; ++i) E3S(E3St::Q0 + i) = A.qpos[(size_t)i * n_env + env];
-  for (int i = 0; i < m.nv; ++i) E3S(E3St::V0 + i) = A.qvel[(size_t)i * n_env + env];
-  float* rec = nullptr;
-  if (A.replay) {   // fused replay insert: the observation the policy acted on is the stored current observation
-    long long slot = A.top + env;
-    if (slot >= A.cap) slot -= A.cap;
-    rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
-    for (int i = 0; i < o; ++i) rec[i] = A.obs_cur[(size_t)env * o + i];
-  }
-  double reward; bool done;
-  e3_task_step(C, A.act + (size_t)t * na, reward, done);
-  bool end = false; int len = 0; double ret = 0.0;
-  if (A.auto_reset) {
-    len = A.ep_len[env] + 1; ret = A.ep_ret[env] + reward;
-    bool finite = isfinite(reward);
-    end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // see k_env_step: no_terminal keeps stepping an unhealthy env
-  }
-  float* obs_out = A.obs ? A.obs + (size_t)t * o : nullptr;
-  float* cur = (A.obs_cur && !end) ? A.obs_cur + (size_t)env * o : nullptr;
-  float* rnext = rec ? rec + o + na + 2 : nullptr;
-  e3_observe<E3K_TRUNC>(C, [&](int i, double val) {
-    const float f = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]);
-    if (obs_out) obs_out[i] = f;
-    if (cur) cur[i] = f;
-    if (rnext) rnext[i] = f;
-  });
-  if (A.rew) A.rew[t] = (float)reward;
-  if (A.done) A.done[t] = done ? 1 : 0;
-  if (rec) {
-    const float* ra = A.rec_act ? A.rec_act : A.act;
-    for (int k = 0; k < na; ++k) rec[o + k] = ra[(size_t)t * na + k];
-    rec[o + na] = (float)reward;
-    rec[o + na + 1] = (done && !A.no_terminal) ? 1.0f : 0.0f;
-    rec[2 * o + na + 2] = 0.0f; rec[2 * o + na + 3] = 0.0f;
-  }
-  if (A.auto_reset) {
-    if (end) {
-      atomicAdd(&A.stats[0], 1.0);
-      atomicAdd(&A.stats[1], ret);
-      e3_reset_state(C, A.seed, A.stream, A.step, (uint32_t)env);
-      e3_kinematics(C, E3St::Q0, E3St::V0);
-      float* c2 = A.obs_cur + (size_t)env * o;
-      e3_observe<E3K_TRUNC>(C, [&](int i, double val) { c2[i] = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]); });
-    }
-    A.ep_len[env] = end ? 0 : len;
-    A.ep_ret[env] = end ? 0.0 : ret;
-    if (A.flush_len) A.flush_len[env] = end ? (len | ((done && !A.no_terminal) ? (1 << 30) : 0)) : 0;
-  }
-  for (int i = 0; i < m.nq; ++i) A.qpos[(size_t)i * n_env + env] = E3S(E3St::Q0 + i);
-  for (int i = 0; i < m.nv; ++i) A.qvel[(size_t)i * n_env + env] = E3S(E3St::V0 + i);
-}
-
-__global__ __launch_bounds__(64) void E3K(k_env3d_reset)(const Spatial3Dev* mp, double* scr, double* qpos, double* qvel, int n_env, const int* ids,
-                                                    int n_ids, float* obs, float* obs_cur, int* ep_len, double* ep_ret, uint64_t seed,
-                                                    uint32_t stream, unsigned long long step) {
-  const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= n_ids) return;
-  const int env = ids ? ids[t] : t;
-  const Spatial3Dev& m = *mp;
-  const E3Ctx C{scr, n_env, env, mp};
-  e3_reset_state(C, seed, stream, step, (uint32_t)env);
-  e3_kinematics(C, E3St::Q0, E3St::V0);
-  const int o = m.obs_dim;
-  e3_observe<E3K_TRUNC>(C, [&](int i, double val) {
-    const float f = (float)((val - m.obs_shift[i]) * m.obs_inv_scale[i]);
-    if (obs) obs[(size_t)t * o + i] = f;
-    if (obs_cur) obs_cur[(size_t)env * o + i] = f;
-  });
-  ep_len[env] = 0; ep_ret[env] = 0.0;
-  for (int i = 0; i < m.nq; ++i) qpos[(size_t)i * n_env + env] = E3S(E3St::Q0 + i);
-  for (int i = 0; i < m.nv; ++i) qvel[(size_t)i * n_env + env] = E3S(E3St::V0 + i);
-}
-
+// env3d_kernels.inc — the two kernels of the 3-D stepper (wave-per-env step / reset), included by ilsx_env.hip once per observation
+// layout: E3K(name) names the kernels, E3K_TRUNC is e3w_observe's TRUNC (0: the full observation, kernels k_env3dw_*; 1: qpos[2:] | qvel
+// of the *_trunc_obs tasks, kernels k_env3dw_*_trunc).  Two inclusions of one text rather than one templated body: the full-observation
+// kernels compile to the instructions they had before the truncated tasks existed.  (The lane-per-env kernels were removed: DESIGN §27.)
 template <int NV>
 __global__ __launch_bounds__(64) void E3K(k_env3dw_step)(const EnvStepArgs A, const Spatial3Dev* mp) {
   extern __shared__ __attribute__((aligned(16))) double e3w_smem[];
@@ -111,7 +30,7 @@ __global__ __launch_bounds__(64) void E3K(k_env3dw_step)(const EnvStepArgs A, co
   if (A.auto_reset) {
     len = A.ep_len[env] + 1; ret = A.ep_ret[env] + reward;
     bool finite = isfinite(reward);
-    end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // see k_env_step: no_terminal keeps stepping an unhealthy env
+    end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;   // see envg_step_dev: no_terminal keeps stepping an unhealthy env
   }
   float* obs_out = A.obs ? A.obs + (size_t)t * o : nullptr;
   float* cur = (A.obs_cur && !end) ? A.obs_cur + (size_t)env * o : nullptr;

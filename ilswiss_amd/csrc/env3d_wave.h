@@ -1,8 +1,8 @@
 // env3d_wave.h — the 3-D articulated-body stepper (Ant-v2 / Humanoid-v2), ONE WAVEFRONT PER ENV, working set in LDS.
 //
 // Same model, same equations and the same oracle as env3d.h (oracle/spatial_env.py; reference rules rlkit/envs/mujoco/humanoid.py:24-73,
-// ant.py:11-43).  env3d.h runs one env per lane with its ~2.8k-double working set in global scratch: every access is a memory round
-// trip and a 1024-env launch is 16 waves on a 1024-SIMD chip (measured 36.7 ms per vec-env step, profiles/r02).  Here the 64 lanes of a
+// ant.py:11-43).  env3d.h (the reference statement; its kernels were removed) ran one env per lane with its ~2.8k-double
+// working set in global scratch: every access a memory round trip, a 1024-env launch 16 waves on a 1024-SIMD chip (36.7 ms per vec-env step).  Here the 64 lanes of a
 // wave share one env: link frames, composite inertias, the mass matrix / Cholesky factor, the constraint rows and the constraint-space
 // matrix live in 23 KB of LDS owned by that wave (6 envs resident per CU), and every O(n^2) / O(n^3) stage is spread over the lanes:
 //   kinematics            parallel over the links of one tree level (levels in sequence), joint rotations of all links first

@@ -2,10 +2,9 @@
 // and, once per stage, inside the merged phase kernels (k_sac_phase_a / _c).  A device function with the descriptors passed by reference
 // compiled differently (the kernel-argument records stopped being read in place: +100 scalar-spill lane operations and a private
 // segment in the backward kernel), so the body is shared as text and every user compiles it against its own kernel arguments.
-// MT (constexpr int, provided by the including scope): 16-row tiles the workgroup processes TOGETHER (a "macro tile" of 16 MT rows).  Every
-// weight fragment a wave fetched (layer 0, its layer-1 slice, the head rows) is then used for MT row tiles, and the per-workgroup overhead
-// (descriptor reads, weight burst, barriers) is paid once per 16 MT rows: the throughput shape of the grouped / large-batch launches.
-// Each row tile runs the SAME chain of MFMAs on the SAME operands as with MT = 1, so results are bit-identical for every MT.
+// A workgroup processes ONE 16-row tile at a time.  (The macro-tile shape — MT = 2 | 4 row tiles together — was measured slower and removed,
+// DESIGN §27.  Three blocks below still carry a loop `for (m < MT)` with MT = 1, defined here: written without the one-trip loop they compile
+// to other instructions in the phase kernels, and this text does not change what the hot path executes.  They go in a change that measures it.)
 // Names the including scope provides: template parameters H, ACT, CS, GRP, PH; `constexpr bool XCH` (see ldx / stx); `A` (FwdArgs),
 // `T` (FwdTask), `GP` (const FwdGroup*, GRP only), `bx` (tile index in grid units), `cs` (column slice), `first_task` (this task's lead
 // slice publishes the finished policy head), `smem` (dynamic LDS); the macros XCH_HOOK_STAGE (before the input rows are staged) and
@@ -21,19 +20,19 @@
   constexpr int NTH = 4 * H / CS, NWV = NTH / 64, NC = H / 16, SLW = H / CS, NCS = SLW / 16;
   constexpr int NT0 = PH == 1 ? 1 : CS;   // layer-0 column tiles per wave
   constexpr int LDH = H + ILSX_LDS_PAD, LDSL = SLW + ILSX_LDS_PAD;
-  constexpr int MR = 16 * MT;       // rows of the macro tile
+  constexpr int MT = 1;             // row tiles per workgroup: one (see above)
+  constexpr int MR = 16;            // rows of the tile
   static_assert(NCS == NWV, "one k16 chunk of the slice per wave in the head phase");
-  static_assert(MT == 1 || MT == 2 || MT == 4, "macro tile = 1, 2 or 4 row tiles");
   const DevScalars* scal = GRP ? GP->scal : A.scal;
   const NetView& N = T.net;
   int KP = N.KP;
   if constexpr (FINS) XCH_PIN(KP);
   const int LDX = KP + ILSX_LDS_PAD, NO = N.NO, NCH0 = KP >> 4, NOT = (NO + 15) >> 4;
   float* xs = smem;                 // [MR][LDX]
-  float* h0 = xs + (PH == 2 && MT > 1 ? 0 : MR * LDX);        // [MR][LDH]   layer-0 activations, all H columns   (macro tiles: the regions a phase
-  float* hs = h0 + (PH == 1 && MT > 1 ? 0 : MR * LDH);        // [MR][LDSL]  this slice of the layer-1 activations  does not touch take no LDS, see fwd_split_lds_bytes)
-  float* red = hs + MR * LDSL;      // MT = 1: [4 tiles][NWV][4][64] head partial tiles; MT > 1: [MT][NOT][NWV][4][64] (sized by the host for the launch's widest head)
-  const int RNT = MT == 1 ? 4 : NOT;   // head-output tiles per row tile in `red`
+  float* h0 = xs + MR * LDX;        // [MR][LDH]   layer-0 activations, all H columns
+  float* hs = h0 + MR * LDH;        // [MR][LDSL]  this slice of the layer-1 activations
+  float* red = hs + MR * LDSL;      // [4 tiles][NWV][4][64] head partial tiles
+  constexpr int RNT = 4;            // head-output tiles in `red`
   if (bx & ((1u << A.xs) - 1u)) return;   // XCD confinement: the dispatcher deals workgroups round-robin to the 8 XCDs
   if ((int)(bx >> A.xs) * (A.rt > 0 ? A.rt : 1) * MR >= A.rows) return;   // grid.x is padded to a multiple of 8
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
@@ -65,7 +64,7 @@
   float bias1 = 0.0f;
   float4 whf[4];
   float4 wreg[NC];
-  constexpr bool LATEW = GRP == 3 && MT == 1 && PH == 0;
+  constexpr bool LATEW = GRP == 3 && PH == 0;
   if constexpr (PH != 1) {
     bias1 = (N.base + N.off_b[1])[col1];
     // head weights of this slice as MFMA B fragments: wave w owns k16 chunk w of the slice, rows j = 16t + li
@@ -90,14 +89,14 @@
   for (int rt = 0; rt < RT; ++rt) {
   const int r0 = ((bx >> A.xs) * RT + rt) * MR;
   if (r0 >= rows) break;   // workgroup-uniform
-  const bool full_tile = r0 + MR <= rows;   // workgroup-uniform: every row of the (macro) tile is a batch row
+  const bool full_tile = r0 + MR <= rows;   // workgroup-uniform: every row of the tile is a batch row
   bool fin_logp = false;
   int sf_a = 0; float* sf_logp = nullptr;   // FINS: the epilogue's action count and (publishing slice) log-pi destination
   if constexpr (PH != 2) {
 #pragma unroll
   for (int i = 0; i < NT0; ++i) b0[i] = b0first[i];
   if constexpr (FINS) {
-    static_assert(PH == 0 && MT == 1 && GRP == 0 && XCH, "the static epilogue is phase A's target-critic stage");
+    static_assert(PH == 0 && GRP == 0 && XCH, "the static epilogue is phase A's target-critic stage");
     const PolicyFinishArgs& FP = A.fin;   // (`P` is the phase kernel's own block, which the hook names)
     const bool pub = lead && first_task;
     int sf_d0 = T.d0, sf_s0 = T.s0, sf_ps = FP.part_stride;
@@ -186,7 +185,7 @@
   XCH_HOOK_STAGE
   if constexpr (PH == 0) {   // narrow inputs (the one-launch form): one element per thread, the row's index drawn where it is used
     long long* ridx0 = reinterpret_cast<long long*>(hs);   // hs is not live before layer 1
-    if constexpr (MT > 1 || GRP != 0) {   // grouped launches (throughput: every issued instruction counts) and macro tiles: the row's index is drawn ONCE, by 16 MT lanes, not per element by every thread
+    if constexpr (GRP != 0) {   // grouped launches (throughput: every issued instruction counts): the row's index is drawn ONCE, by 16 lanes, not per element by every thread
       if (G.on) {
         if (tid < MR) ridx0[tid] = r0 + tid < rows ? replay_draw(G.seed, scal->gather_step, G.stream, (uint32_t)(r0 + tid), G.st->size) : 0;
         lds_barrier();
@@ -200,7 +199,7 @@
       if (gr < rows) {
         if (G.on) {   // fused sample+index (simple_replay_buffer.py:239-293): row gr of the batch is record idx
           long long idx;
-          if constexpr (MT > 1 || GRP != 0) idx = ridx0[r];
+          if constexpr (GRP != 0) idx = ridx0[r];
           else idx = replay_draw(G.seed, scal->gather_step, G.stream, (uint32_t)gr, G.st->size);
           const float* rec = G.records + (size_t)idx * G.rec;
           if (k < T.d0) v = rec[T.g0_off + k];
@@ -258,7 +257,7 @@
       constexpr int RW = 16 / NWV, U = 8;
       const bool acts = T.d1 > 0 && !fin;
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {   // one 16-row tile of the macro tile at a time (RW rows per wave in flight)
+      for (int mt = 0; mt < MT; ++mt) {   // one 16-row tile at a time (RW rows per wave in flight)
       float vo[RW][U], va[RW];
 #pragma unroll
       for (int rr = 0; rr < RW; ++rr) {
@@ -318,7 +317,7 @@
     const bool pub = lead && (GRP ? T.first != 0 : first_task);
     float* lp3 = red;   // [MR][LPS][3] log-prob contributions (quad, log_std, jacobian)
     const unsigned long long fstep = P.scal ? (P.use_gather_step ? P.scal->gather_step : P.scal->step) : P.step_host;   // requested with the partials, not after them
-    const int LPS = MT == 1 ? 32 : a;   // row stride of lp3 (MT > 1: packed, the region is shared with the head partial tiles)
+    constexpr int LPS = 32;   // row stride of lp3
     for (int e = tid; e < MR * a; e += NTH) {
       const int row = e / a, j = e - row * a, gr = r0 + row;
       float act = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
@@ -386,7 +385,7 @@
     const PolicyFinishArgs& P = GRP ? GP->fin : A.fin;   // barrier instead of behind a barrier of its own (`red` is next written two
     float q = 0.f, l = 0.f, jc = 0.f;                    // barriers from here)
     const int pa = FINS ? sf_a : P.a;
-    const int LPS = MT == 1 ? 32 : pa;
+    constexpr int LPS = 32;
     for (int j = 0; j < pa; ++j) { q += red[(tid * LPS + j) * 3]; l += red[(tid * LPS + j) * 3 + 1]; jc += red[(tid * LPS + j) * 3 + 2]; }
     stx<XCH>(xg<FINS>((FINS ? sf_logp : P.logp) + r0 + tid), -0.5f * q - (l + HALF_LOG_2PI) - jc);
   }
@@ -394,9 +393,7 @@
   if constexpr (PH == 1) {
     // a wide layer 0 is a long K loop (25 k16 chunks for Humanoid): with the next chunk requested one step ahead every trip waited
     // for an L2 round trip (24 us per launch); here L0D chunks are in flight while the previous L0D are consumed
-    f32x4 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
     const float* ap = xs + li * LDX + 4 * g;
     float4 cur[L0D], nxt[L0D];
 #pragma unroll
@@ -410,12 +407,9 @@
 #pragma unroll
       for (int d = 0; d < L0D; ++d) {
         if (cb + d < NCH0) {   // uniform
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            const float4 a = *reinterpret_cast<const float4*>(ap + m * 16 * LDX + 16 * (cb + d));
-            acc[m] = MFMA16(a.x, cur[d].x, acc[m]); acc[m] = MFMA16(a.y, cur[d].y, acc[m]);
-            acc[m] = MFMA16(a.z, cur[d].z, acc[m]); acc[m] = MFMA16(a.w, cur[d].w, acc[m]);
-          }
+          const float4 a = *reinterpret_cast<const float4*>(ap + 16 * (cb + d));
+          acc = MFMA16(a.x, cur[d].x, acc); acc = MFMA16(a.y, cur[d].y, acc);
+          acc = MFMA16(a.z, cur[d].z, acc); acc = MFMA16(a.w, cur[d].w, acc);
         }
       }
 #pragma unroll
@@ -424,23 +418,15 @@
     float* hsv = T.hsave[0];
     const int col = ct0 * 16 + li;
 #pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int row = 16 * m + 4 * g + v;
-        if (r0 + row < rows) hsv[(size_t)(r0 + row) * H + col] = act_fn<ACT>(acc[m][v] + bias0[0]);
-      }
+    for (int v = 0; v < 4; ++v) {
+      const int row = 4 * g + v;
+      if (r0 + row < rows) hsv[(size_t)(r0 + row) * H + col] = act_fn<ACT>(acc[v] + bias0[0]);
+    }
   } else if constexpr (PH != 2) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {   // row tiles one after the other: the layer-0 weights are a few KB (first chunk in registers, the rest re-read from the L1)
     f32x4 acc[NT0];
 #pragma unroll
     for (int i = 0; i < NT0; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (m > 0) {
-#pragma unroll
-      for (int i = 0; i < NT0; ++i) b0[i] = b0first[i];
-    }
-    const float* ap = xs + (16 * m + li) * LDX + 4 * g;
+    const float* ap = xs + li * LDX + 4 * g;
     for (int kc = 0; kc < KP; kc += 16) {
       float4 bn[NT0];
 #pragma unroll
@@ -464,13 +450,13 @@
     // saved activations: one 64-bit address per row tile (rows 4g + v and column tiles i are immediate offsets from it), and no row
     // guards when the whole tile is inside the batch (workgroup-uniform): the guarded form was a compare, an EXEC branch and three address
     // instructions per stored element
-    float* const hrow = hsv ? hsv + (size_t)(r0 + 16 * m + 4 * g) * H + ct0 * 16 + li : nullptr;
+    float* const hrow = hsv ? hsv + (size_t)(r0 + 4 * g) * H + ct0 * 16 + li : nullptr;
 #pragma unroll
     for (int i = 0; i < NT0; ++i) {
       const int col = (ct0 + i) * 16 + li;
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int row = 16 * m + 4 * g + v;
+        const int row = 4 * g + v;
         const float h = act_fn<ACT>(acc[i][v] + bias0[i]);
         if constexpr (PH == 0) h0[row * LDH + col] = h;
         acc[i][v] = h;
@@ -487,10 +473,9 @@
         for (int i = 0; i < NT0; ++i)
 #pragma unroll
           for (int v = 0; v < 4; ++v)
-            if (r0 + 16 * m + 4 * g + v < rows) stx<XCH>(hrow + v * H + i * 16, acc[i][v]);
+            if (r0 + 4 * g + v < rows) stx<XCH>(hrow + v * H + i * 16, acc[i][v]);
       }
     }
-    }   // m
   }
   if constexpr (PH == 1) {
     lds_barrier();   // the next row tile restages xs

@@ -324,7 +324,6 @@ static int kernels_init_once() {
   HIPCHK(hipFuncSetAttribute((const void*)k_mlp_bwd_dw_low<true, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
   HIPCHK(hipFuncSetAttribute((const void*)k_mlp_bwd_dw<true, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
   HIPCHK(hipFuncSetAttribute((const void*)k_mlp_bwd_dw<true, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-  HIPCHK(hipFuncSetAttribute((const void*)k_mlp_bwd_dw<true, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
   HIPCHK(hipFuncSetAttribute((const void*)k_mlp_bwd_dw<false, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
   HIPCHK(hipFuncSetAttribute((const void*)k_mlp_bwd_dw<false, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
 #define SET_G(HH, AA, CC, GG) HIPCHK(hipFuncSetAttribute((const void*)k_mlp2_fwd_split<HH, AA, CC, GG>, hipFuncAttributeMaxDynamicSharedMemorySize, cap))
@@ -335,12 +334,6 @@ static int kernels_init_once() {
 #undef SET_PH
   SET_G(128, ACT_RELU, 2, 0); SET_G(128, ACT_RELU, 2, 1); SET_G(128, ACT_RELU, 2, 2); SET_G(128, ACT_RELU, 2, 3); SET_G(128, ACT_TANH, 2, 0); SET_G(128, ACT_TANH, 2, 1); SET_G(128, ACT_TANH, 2, 2); SET_G(128, ACT_TANH, 2, 3);
 #undef SET_G
-#define SET_MT(AA, MM) HIPCHK(hipFuncSetAttribute((const void*)k_mlp2_fwd_split<256, AA, 4, true, 0, MM>, hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
-  HIPCHK(hipFuncSetAttribute((const void*)k_mlp2_fwd_split<256, AA, 4, true, 1, MM>, hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
-  HIPCHK(hipFuncSetAttribute((const void*)k_mlp2_fwd_split<256, AA, 4, true, 2, MM>, hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
-  HIPCHK(hipFuncSetAttribute((const void*)k_mlp2_bwd_split<256, AA, 4, true, MM>, hipFuncAttributeMaxDynamicSharedMemorySize, cap))
-  SET_MT(ACT_RELU, 2); SET_MT(ACT_RELU, 4); SET_MT(ACT_TANH, 2); SET_MT(ACT_TANH, 4);
-#undef SET_MT
 #define SET_PHASE(HH, AA, CC) HIPCHK(hipFuncSetAttribute((const void*)k_sac_phase_a<HH, AA, CC>, hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
   HIPCHK(hipFuncSetAttribute((const void*)k_sac_phase_a<HH, AA, CC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
   HIPCHK(hipFuncSetAttribute((const void*)k_sac_phase_c<HH, AA, CC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
@@ -412,52 +405,14 @@ static size_t fwd_split_lds_bytes(int H, int KP, int cs) {
   return sizeof(float) * (16 * (KP + ILSX_LDS_PAD) + 16 * (H + ILSX_LDS_PAD) + 16 * (H / cs + ILSX_LDS_PAD) +
                           4 * (4 * H / cs / 64) * 4 * 64);
 }
-static size_t bwd_split_lds_bytes(int H, int cs, int mt = 1) {
-  return sizeof(float) * mt * (16 * (H + ILSX_LDS_PAD) + 16 * (H / cs + ILSX_LDS_PAD) + 16 * ILSX_MAX_NO);
+static size_t bwd_split_lds_bytes(int H, int cs) {
+  return sizeof(float) * (16 * (H + ILSX_LDS_PAD) + 16 * (H / cs + ILSX_LDS_PAD) + 16 * ILSX_MAX_NO);
 }
-// macro tiles (fwd_split_tile.inc, MT > 1): mt row tiles per workgroup; ph = the forward's phase (0 whole, 1 layer 0 only, 2 layer 1 + heads);
-// not_max = the widest head of the launch in 16-output tiles, a_max = the widest finished policy (log-prob staging shares the partial-tile region)
-static size_t fwd_split_lds_bytes_mt(int H, int KP, int cs, int mt, int ph, int not_max, int a_max) {
-  const size_t mr = 16 * (size_t)mt, nwv = 4 * H / cs / 64;
-  size_t fl = mr * (H / cs + ILSX_LDS_PAD);                       // hs
-  if (ph != 2) fl += mr * (KP + ILSX_LDS_PAD);                    // xs
-  if (ph != 1) fl += mr * (H + ILSX_LDS_PAD);                     // h0
-  const size_t part = ph == 1 ? 0 : (size_t)mt * std::max(not_max, 1) * nwv * 256, lp3 = ph == 2 ? 0 : mr * std::max(a_max, 1) * 3;
-  fl += std::max(part, lp3);
-  return sizeof(float) * fl;
-}
-// the grouped macro-tile launches run on a 1-D grid (GrpSwizzle, kernels.h)
-static int grp_swizzle_fill(GrpSwizzle* S, int ntasks, int agents, int rows, int mt) {
-  if (agents < 1 || ntasks % agents) ILSX_FAIL(ILSX_ERR_ARG, "grouped launch: %d tasks do not divide over %d agents", ntasks, agents);
-  S->agents = agents; S->tpa = ntasks / agents; S->tiles = (rows + 16 * mt - 1) / (16 * mt);
-  S->np8 = (agents * S->tiles + 7) / 8;
-  return ILSX_OK;
-}
-
 int launch_fwd(ilsx_ctx* ctx, const FwdArgs& A0, int H, int act, int KPmax, int cs) {
   if (A0.rows <= 0) return ILSX_OK;
   FwdArgs A = A0;
   A.dbg = ctx->dbg_next();
   ProfScope ps(ctx, ILSX_K_MLP_FWD);
-  if (cs > 1 && A.tasks && A.mt > 1) {   // grouped launch on macro tiles: 1-D grid, (agent, tile) -> XCD fixed across the lock-step's launches
-    if (!(H == 256 && cs == 4) || (A.mt != 2 && A.mt != 4)) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "macro-tile forward: H=%d cs=%d mt=%d", H, cs, A.mt);
-    A.xs = 0; A.rt = 1; A.ctab = 0;
-    ILSX_TRY(grp_swizzle_fill(&A.swz, A.ntasks, A.swz.agents, A.rows, A.mt));
-    const unsigned nwork = 8u * A.swz.np8 * A.swz.tpa * cs;
-    if (A.tail_mode && (!A.tail || A.tail_n < 1)) ILSX_FAIL(ILSX_ERR_ARG, "deferred tail: bad record table");
-    const dim3 grid(nwork + (A.tail_mode ? A.tail_n : 0)), gridw(nwork), block(4 * H / cs);
-#define MT_CALL(AA, PP, MM, GR, AR) do { const size_t lds = fwd_split_lds_bytes_mt(H, KPmax, cs, MM, PP, A.mt_not, A.mt_a); \
-      if (lds > 160 * 1024) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "forward macro tile needs %zu B of LDS (> 160 KiB)", lds); \
-      ILSX_LAUNCH(ps, (k_mlp2_fwd_split<256, AA, 4, true, PP, MM>), GR, block, lds, ctx->stream, AR); } while (0)
-#define MT_CALL_PH(AA, MM) do { if (A.l0_split) { FwdArgs A2 = A; A2.tail_mode = 0; A2.tail = nullptr; A2.tail_n = 0; A2.dbg = ctx->dbg_next(); \
-      MT_CALL(AA, 1, MM, grid, A); MT_CALL(AA, 2, MM, gridw, A2); } else { MT_CALL(AA, 0, MM, grid, A); } } while (0)
-    if (act == ILSX_ACT_RELU) { if (A.mt == 2) MT_CALL_PH(ACT_RELU, 2); else MT_CALL_PH(ACT_RELU, 4); }
-    else { if (A.mt == 2) MT_CALL_PH(ACT_TANH, 2); else MT_CALL_PH(ACT_TANH, 4); }
-#undef MT_CALL_PH
-#undef MT_CALL
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
   if (cs > 1) {
     const size_t lds = fwd_split_lds_bytes(H, KPmax, cs);
     if (lds > 160 * 1024) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "forward tile needs %zu B of LDS (> 160 KiB)", lds);
@@ -716,18 +671,6 @@ int launch_bwd_dx(ilsx_ctx* ctx, const BwdArgs& A0, int H, int act, int cs) {
   A.dbg = ctx->dbg_next();
   if (A.ga_parts < 1) A.ga_parts = 1;
   ProfScope ps(ctx, ILSX_K_MLP_BWD_DX);
-  if (cs > 1 && A.tasks && A.mt > 1) {   // grouped launch on macro tiles (see launch_fwd)
-    if (!(H == 256 && cs == 4) || (A.mt != 2 && A.mt != 4)) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "macro-tile backward: H=%d cs=%d mt=%d", H, cs, A.mt);
-    A.xs = 0; A.ctab = 0;
-    ILSX_TRY(grp_swizzle_fill(&A.swz, A.ntasks, A.swz.agents, A.rows, A.mt));
-    const dim3 grid(8u * A.swz.np8 * A.swz.tpa * cs), block(4 * H / cs);
-    const size_t lds = bwd_split_lds_bytes(H, cs, A.mt);
-    if (lds > 160 * 1024) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "backward macro tile needs %zu B of LDS (> 160 KiB)", lds);
-    if (act == ILSX_ACT_RELU) { if (A.mt == 2) ILSX_LAUNCH(ps, (k_mlp2_bwd_split<256, ACT_RELU, 4, true, 2>), grid, block, lds, ctx->stream, A); else ILSX_LAUNCH(ps, (k_mlp2_bwd_split<256, ACT_RELU, 4, true, 4>), grid, block, lds, ctx->stream, A); }
-    else { if (A.mt == 2) ILSX_LAUNCH(ps, (k_mlp2_bwd_split<256, ACT_TANH, 4, true, 2>), grid, block, lds, ctx->stream, A); else ILSX_LAUNCH(ps, (k_mlp2_bwd_split<256, ACT_TANH, 4, true, 4>), grid, block, lds, ctx->stream, A); }
-    HIPCHK(hipGetLastError());
-    return ILSX_OK;
-  }
   if (cs > 1) {
     const size_t lds = bwd_split_lds_bytes(H, cs);
     A.xs = ctx->xcd_shift;
@@ -832,11 +775,7 @@ int launch_bwd_dw(ilsx_ctx* ctx, DevOwner& owner, const DwArgs& table, int rows,
     return ILSX_OK;
   }
   ProfScope ps(ctx, ILSX_K_MLP_BWD_DW);
-  if (D.gtiles && D.strip) {
-    bool whole = (rows & 255) == 0;   // whole 256-row trips, and every matrix contracts over the batch rows (grouped tables hold no row-stacked jobs: group_build)
-    if (whole) ILSX_LAUNCH(ps, (k_dw_strip<true, true>), dim3(D.ntiles), dim3(64), 0, ctx->stream, D);
-    else ILSX_LAUNCH(ps, (k_dw_strip<true, false>), dim3(D.ntiles), dim3(64), 0, ctx->stream, D);
-  } else if (D.gtiles) {
+  if (D.gtiles) {
     const int gnh = D.tile_nh ? D.tile_nh : 2, gkt = D.tile_kt ? D.tile_kt : 4;
     // two 16-wave workgroups per CU (the <= 64-register instance) once the launch has more tiles than CUs: ILSX_DW_GRP_LOW = 0 / 1 pins it
     const char* low_e = getenv("ILSX_DW_GRP_LOW");   // read per launch: tests switch it
@@ -846,7 +785,6 @@ int launch_bwd_dw(ilsx_ctx* ctx, DevOwner& owner, const DwArgs& table, int rows,
     else if (gnh == 2 && gkt == 4) ILSX_LAUNCH(ps, (k_mlp_bwd_dw<true, 2, 4>), dim3(D.ntiles << D.xs), dim3(1024), DW_LDS_BYTES_OF(2, 4), ctx->stream, D);
     else if (gnh == 1 && gkt == 2) ILSX_LAUNCH(ps, (k_mlp_bwd_dw<true, 1, 2>), dim3(D.ntiles << D.xs), dim3(512), DW_LDS_BYTES_OF(1, 2), ctx->stream, D);
     else if (gnh == 1 && gkt == 1) ILSX_LAUNCH(ps, (k_mlp_bwd_dw<true, 1, 1>), dim3(D.ntiles << D.xs), dim3(512), DW_LDS_BYTES_OF(1, 1), ctx->stream, D);
-    else if (gnh == 1 && gkt == 4) ILSX_LAUNCH(ps, (k_mlp_bwd_dw<true, 1, 4>), dim3(D.ntiles << D.xs), dim3(512), DW_LDS_BYTES_OF(1, 4), ctx->stream, D);
     else ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "grouped dW tile %d x %d", gnh, gkt);
   } else {
     // small batches (one 256-row trip per wave): the table's 32 x 64 tiles are a few dozen 16-wave workgroups, each CU's 4 waves per

@@ -4,9 +4,8 @@
 // (NormalizedBoxEnv action map) and the MuJoCo call under gym's HopperEnv/Walker2dEnv.step
 // (reward / termination formulas as restated in rlkit/envs/mujoco/hopper.py:11-40, walker2d.py:11-36).
 //
-// One lane per env.  State is SoA float64 in HBM (qpos[d][env], qvel[d][env]) so a wave's loads are
-// coalesced; the per-env matrices (mass matrix / Cholesky factor, constraint Jacobian, M^-1 J^T, the
-// constraint-space matrix A) live in LDS as [element][lane] slices, everything else in registers.
+// Sixteen lanes per env (env2d_group.h).  State is SoA float64 in HBM (qpos[d][env], qvel[d][env]); the per-env
+// matrices (mass matrix / Cholesky factor, constraint Jacobian, the constraint-space matrix A) live in LDS.
 // The model and its solver are stated in oracle/planar_env.py (the CPU oracle); physics parity with
 // MuJoCo is UNPINNED (no MuJoCo here) — see DESIGN.md.
 // Not a roofline kernel: ~160 B of HBM traffic and O(1e4) fp64 FLOP per env-step on a serial chain.
@@ -68,15 +67,14 @@ struct ilsx_vecenv {
   // run 0 of a lock-step group (ilsx_rollout_steps_lockstep): ONE array of episode-end flags for all K runs, so that a lock-step reads them back
   // with one copy instead of K (each a serialised 8 us on the stream)
   int* grp_flush_dev = nullptr; int* grp_flush_host = nullptr; int grp_flush_n = 0;
-  // 3-D engine (Ant / Humanoid, env3d.h): model, its device copy, and the per-env working set [E3Off::TOTAL][n_env]
+  // 3-D engine (Ant / Humanoid, env3d_wave.h): model and its device copy (the per-env working set lives in the stepping wave's LDS)
   int engine = 0, nq = 0, nv = 0;   // engine: 0 planar, 1 3-D, 2 classic control (classic_env.h)
   int classic = -1, discrete_n = 0;  // engine 2: ILSX_CLASSIC_* task and the size of its Discrete action space (0 = Box actions)
   struct CartChainDev* cc = nullptr; // engine 2, InvertedPendulum / InvertedDoublePendulum: the constants k_cartchain_step takes by value
   struct SwimmerDev* sw = nullptr;   // engine 2, classic == ILSX_SWIMMER_TASK: the constants k_swimmer_step takes by value (swimmer_env.h)
   struct LunarDev* ln = nullptr;     // engine 2, classic == ILSX_LUNAR_TASK: the constants k_lunar_step takes by value (lunar_env.h)
   bool step_draws = false;           // the task draws random numbers on every step: ilsx_vecenv_step gives each step stream coordinates of its own
-  bool wave3 = true;   // wave-per-env kernels (env3d_wave.h); ILSX_ENV3D_LANE=1 selects the lane-per-env form (env3d.h) for A/B runs
-  Spatial3Dev* hm3 = nullptr; Spatial3Dev* dm3 = nullptr; double* scr3 = nullptr;
+  Spatial3Dev* hm3 = nullptr; Spatial3Dev* dm3 = nullptr;
   // exploration strategy of a deterministic policy (ilsx_vecenv_set_exploration): one process per env, float64
   ilsx_explore_cfg explore = {0, 0, 0.0, 0.0, 0.0, 0.0, 1.0, -1.0, 1.0};
   double *ou_state = nullptr, *ou_sigma = nullptr;   // [n_env][a]: the OU state, and the sigma its next evolve uses (the previous call's)
@@ -140,303 +138,6 @@ __device__ __forceinline__ double impedance_d(double r_abs, const double* solimp
   double x = width > 0.0 ? fmin(r_abs / width, 1.0) : 1.0;
   const double y = x < 0.5 ? 2.0 * x * x : 1.0 - 2.0 * (1.0 - x) * (1.0 - x);
   return d0 + y * (dmax - d0);
-}
-
-// LDS slice accessor: element i of this lane's scratch array starting at `base`
-#define SL(base, i) sm[((base) + (i)) * BLOCK + lane_in_block]
-
-template <int NB, int MR, int BLOCK>
-struct EnvScratch {
-  static constexpr int N = NB + 2;
-  static constexpr int OFF_M = 0;               // N*N   (becomes the Cholesky factor L)
-  static constexpr int OFF_J = OFF_M + N * N;   // MR*N  (row r becomes z_r = L^-1 j_r in place)
-  static constexpr int OFF_A = OFF_J + MR * N;  // MR*(MR+1)/2: A = J M^-1 J^T = Z Z^T, lower triangle packed
-  static constexpr int TOTAL = OFF_A + MR * (MR + 1) / 2;
-  static constexpr int a_idx(int r, int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
-};
-
-// Forward dynamics with soft constraints: qacc = f(q, v, ctrl).  See oracle/planar_env.py::dynamics.
-template <int NB, int MR, int BLOCK>
-__device__ void env_dynamics(const PlanarModelDev& m, const double (&q)[NB + 2], const double (&v)[NB + 2],
-                             const double* ctrl, double (&qacc)[NB + 2], double* sm, int lane_in_block) {
-  constexpr int N = NB + 2;
-  using S = EnvScratch<NB, MR, BLOCK>;
-  double phi[NB], phid[NB], ox[NB], oz[NB], aox[NB], aoz[NB];
-  // cos / sin of every body angle, ONCE per evaluation (one sincos each: a shared range reduction): the kinematics of a child, the
-  // mass-matrix loop and the contact geometry all use the same values (the first form called cos and sin separately at each of the
-  // three places: ~11 pairs per evaluation of the 4-body model, a sixth of its instructions)
-  double cb[NB], sb[NB];
-  // ---- kinematics
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const int p = m.parent[b];
-    if (p < 0) {
-      phi[b] = m.jsign[b] * q[2]; phid[b] = m.jsign[b] * v[2];
-      ox[b] = q[0]; oz[b] = q[1]; aox[b] = 0.0; aoz[b] = 0.0;
-    } else {
-      // parent index is data: select with a small unrolled scan (keeps the arrays in registers)
-      double pphi = 0, pphid = 0, pox = 0, poz = 0, paox = 0, paoz = 0, c = 1.0, s = 0.0;
-#pragma unroll
-      for (int j = 0; j < NB; ++j)
-        if (j == p) { pphi = phi[j]; pphid = phid[j]; pox = ox[j]; poz = oz[j]; paox = aox[j]; paoz = aoz[j]; c = cb[j]; s = sb[j]; }
-      phi[b] = pphi + m.jsign[b] * q[2 + b]; phid[b] = pphid + m.jsign[b] * v[2 + b];
-      const double wx = c * m.anchor[b][0] - s * m.anchor[b][1], wz = s * m.anchor[b][0] + c * m.anchor[b][1];
-      ox[b] = pox + wx; oz[b] = poz + wz;
-      aox[b] = paox - pphid * pphid * wx; aoz[b] = paoz - pphid * pphid * wz;
-    }
-    sincos(phi[b], &sb[b], &cb[b]);
-  }
-  // ---- mass matrix + right-hand side
-#pragma unroll
-  for (int i = 0; i < N * N; ++i) SL(S::OFF_M, i) = 0.0;
-  double rhs[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) rhs[i] = 0.0;
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const double c = cb[b], s = sb[b];
-    const double cwx = c * m.com[b][0] - s * m.com[b][1], cwz = s * m.com[b][0] + c * m.com[b][1];
-    const double cx = ox[b] + cwx, cz = oz[b] + cwz;
-    const double acx = aox[b] - phid[b] * phid[b] * cwx, acz = aoz[b] - phid[b] * phid[b] * cwz;
-    double jx[N], jz[N], jp[N];  // COM Jacobian rows and angular Jacobian
-    jx[0] = 1.0; jz[0] = 0.0; jp[0] = 0.0; jx[1] = 0.0; jz[1] = 1.0; jp[1] = 0.0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const bool anc = (m.ancmask[b] >> j) & 1;
-      const double sg = anc ? m.jsign[j] : 0.0;
-      jx[2 + j] = -sg * (cz - oz[j]); jz[2 + j] = sg * (cx - ox[j]); jp[2 + j] = sg;
-    }
-    const double mb = m.mass[b], ib = m.inertia[b];
-    const double fx = mb * (0.0 - acx), fz = mb * (-m.gravity - acz);
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      rhs[i] += jx[i] * fx + jz[i] * fz;
-#pragma unroll
-      for (int k = 0; k <= i; ++k) SL(S::OFF_M, i * N + k) += mb * (jx[i] * jx[k] + jz[i] * jz[k]) + ib * jp[i] * jp[k];
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    SL(S::OFF_M, (2 + b) * N + 2 + b) += m.armature[b];
-    rhs[2 + b] -= m.damping[b] * v[2 + b] + m.stiffness[b] * q[2 + b];   // joint damper + spring towards 0
-  }
-  for (int k = 0; k < m.n_act; ++k) {
-    const int b = m.act_body[k];
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-      if (j == b) rhs[2 + j] += m.gear[j] * ctrl[k];
-  }
-  // ---- Cholesky M = L L^T (lower triangle in place).  Every division by a pivot is a multiplication by its reciprocal, taken once
-  // (an fp64 division is ~40 instructions on this pipe; the factorisation, the two solves, one forward substitution per constraint
-  // row and the final back-substitution held 30 + 6 per row of them per evaluation).  1 ulp away from the oracle's quotients.
-  double invd[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int k = 0; k <= i; ++k) {
-      double sum = SL(S::OFF_M, i * N + k);
-#pragma unroll
-      for (int t = 0; t < k; ++t) sum -= SL(S::OFF_M, i * N + t) * SL(S::OFF_M, k * N + t);
-      if (i == k) { const double d = sqrt(sum); SL(S::OFF_M, i * N + k) = d; invd[i] = 1.0 / d; }
-      else SL(S::OFF_M, i * N + k) = sum * invd[k];
-    }
-  }
-  auto chol_solve = [&](double (&x)[N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      double sum = x[i];
-#pragma unroll
-      for (int t = 0; t < i; ++t) sum -= SL(S::OFF_M, i * N + t) * x[t];
-      x[i] = sum * invd[i];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-      double sum = x[i];
-#pragma unroll
-      for (int t = i + 1; t < N; ++t) sum -= SL(S::OFF_M, t * N + i) * x[t];
-      x[i] = sum * invd[i];
-    }
-  };
-  double qacc0[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) qacc0[i] = rhs[i];
-  chol_solve(qacc0);
-
-  // ---- constraint rows: contacts (distal geoms first, p1 then p2), then joint limits
-  int nr = 0;
-  double rr[MR], rmu[MR], rd[MR], rb_[MR], rk[MR];
-  int rkind[MR];  // 0 normal, 1 tangent, 2 limit
-#pragma unroll
-  for (int t = 0; t < MR; ++t) { rr[t] = 0.0; rmu[t] = 0.0; rd[t] = 1.0; rb_[t] = 0.0; rk[t] = 0.0; rkind[t] = 0; }
-  auto add_row = [&](const double (&jrow)[N], double r, int kind, double mu, double d, double bdamp, double kstiff) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) SL(S::OFF_J, nr * N + i) = jrow[i];
-#pragma unroll
-    for (int t = 0; t < MR; ++t)
-      if (t == nr) { rr[t] = r; rkind[t] = kind; rmu[t] = mu; rd[t] = d; rb_[t] = bdamp; rk[t] = kstiff; }
-    ++nr;
-  };
-  {
-    const double tc = m.c_solref[0], dr = m.c_solref[1], dmax = m.c_solimp[1];
-    const double bdamp = 2.0 / (dmax * tc), kstiff = 1.0 / (dmax * dmax * tc * tc * dr * dr);
-    for (int gi = m.ng - 1; gi >= 0; --gi) {
-      const int b = m.geom_body[gi];
-      double box = 0, boz = 0, c = 1.0, s = 0.0;
-#pragma unroll
-      for (int j = 0; j < NB; ++j)
-        if (j == b) { box = ox[j]; boz = oz[j]; c = cb[j]; s = sb[j]; }
-      const double rad = m.grad[gi];
-      for (int e = 0; e < 2; ++e) {
-        const double ex = e == 0 ? m.gp1[gi][0] : m.gp2[gi][0], ez = e == 0 ? m.gp1[gi][1] : m.gp2[gi][1];
-        const double wx = c * ex - s * ez, wz = s * ex + c * ez;
-        const double dist = boz + wz - rad;
-        if (dist < m.margin && nr + 2 <= m.max_rows) {
-          const double px = box + wx, pz = boz + wz - (rad + 0.5 * dist);  // contact point
-          double jn[N], jt[N];
-          jn[0] = 0.0; jn[1] = 1.0; jt[0] = 1.0; jt[1] = 0.0;
-#pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            const bool anc = (m.ancmask[b] >> j) & 1;
-            const double sg = anc ? m.jsign[j] : 0.0;
-            jn[2 + j] = sg * (px - ox[j]); jt[2 + j] = -sg * (pz - oz[j]);
-          }
-          const double d = impedance_d(fabs(dist), m.c_solimp);
-          add_row(jn, dist, 0, m.gfric[gi], d, bdamp, kstiff);
-          add_row(jt, 0.0, 1, m.gfric[gi], d, bdamp, kstiff);
-        }
-      }
-    }
-  }
-  {
-    const double tc = m.l_solref[0], dr = m.l_solref[1], dmax = m.l_solimp[1];
-    const double bdamp = 2.0 / (dmax * tc), kstiff = 1.0 / (dmax * dmax * tc * tc * dr * dr);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (!m.limited[b] || nr + 1 > m.max_rows) continue;
-      const double lo = m.range[b][0], hi = m.range[b][1], qq = q[2 + b];
-      double r = 0.0, sgn = 0.0;
-      if (qq - lo < 0.0) { r = qq - lo; sgn = 1.0; }
-      else if (hi - qq < 0.0) { r = hi - qq; sgn = -1.0; }
-      if (sgn != 0.0) {
-        double je[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) je[i] = (i == 2 + b) ? sgn : 0.0;
-        add_row(je, r, 2, 0.0, impedance_d(fabs(r), m.l_solimp), bdamp, kstiff);
-      }
-    }
-  }
-  if (nr == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) qacc[i] = qacc0[i];
-    return;
-  }
-  // ---- z_r = L^-1 j_r (forward substitution only, in place), A = Z Z^T (symmetric, packed), PGS on (A + R) f = aref - J qacc0.
-  // M^-1 J^T itself is never formed: the constraint acceleration is L^-T (Z^T f), one back-substitution at the end.
-  double rhs_c[MR], Rd[MR], f[MR];
-#pragma unroll
-  for (int t = 0; t < MR; ++t) { rhs_c[t] = 0.0; Rd[t] = 0.0; f[t] = 0.0; }
-  for (int r = 0; r < nr; ++r) {
-    double x[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) x[i] = SL(S::OFF_J, r * N + i);
-    double jv = 0.0, ja = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) { jv += x[i] * v[i]; ja += x[i] * qacc0[i]; }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      double sum = x[i];
-#pragma unroll
-      for (int t = 0; t < i; ++t) sum -= SL(S::OFF_M, i * N + t) * x[t];
-      x[i] = sum * invd[i];
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) SL(S::OFF_J, r * N + i) = x[i];
-#pragma unroll
-    for (int t = 0; t < MR; ++t)
-      if (t == r) rhs_c[t] = (-rb_[t] * jv - rk[t] * rd[t] * rr[t]) - ja;
-    for (int c2 = 0; c2 <= r; ++c2) {
-      double sum = 0.0;
-#pragma unroll
-      for (int i = 0; i < N; ++i) sum += x[i] * SL(S::OFF_J, c2 * N + i);
-      SL(S::OFF_A, r * (r + 1) / 2 + c2) = sum;
-    }
-  }
-  // Rd is reused for 1 / (a_tt + R_t): the 30 sweeps divide by it once per row instead of once per row per sweep
-#pragma unroll
-  for (int t = 0; t < MR; ++t)
-    if (t < nr) { const double att = SL(S::OFF_A, S::a_idx(t, t)); Rd[t] = 1.0 / (att + (1.0 - rd[t]) / rd[t] * att); }
-  for (int it = 0; it < m.pgs_iters; ++it) {
-#pragma unroll
-    for (int t = 0; t < MR; ++t) {
-      if (t >= nr) continue;
-      const double aii = SL(S::OFF_A, S::a_idx(t, t));
-      double res = rhs_c[t] + aii * f[t];
-#pragma unroll
-      for (int u = 0; u < MR; ++u)
-        if (u < nr) res -= SL(S::OFF_A, S::a_idx(t, u)) * f[u];
-      double fi = res * Rd[t];
-      if (rkind[t] == 1) {
-        const double lim = rmu[t] * f[t > 0 ? t - 1 : 0];
-        fi = fmin(fmax(fi, -lim), lim);
-      } else {
-        fi = fmax(fi, 0.0);
-      }
-      f[t] = fi;
-    }
-  }
-  double w[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) w[i] = 0.0;
-  for (int r = 0; r < nr; ++r) {
-    double fr = 0.0;
-#pragma unroll
-    for (int t = 0; t < MR; ++t)
-      if (t == r) fr = f[t];
-#pragma unroll
-    for (int i = 0; i < N; ++i) w[i] += SL(S::OFF_J, r * N + i) * fr;
-  }
-#pragma unroll
-  for (int i = N - 1; i >= 0; --i) {
-    double sum = w[i];
-#pragma unroll
-    for (int t = i + 1; t < N; ++t) sum -= SL(S::OFF_M, t * N + i) * w[t];
-    w[i] = sum * invd[i];
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) qacc[i] = qacc0[i] + w[i];
-}
-
-template <int NB, int MR, int BLOCK>
-__device__ void env_substep(const PlanarModelDev& m, double (&q)[NB + 2], double (&v)[NB + 2], const double* ctrl,
-                            double* sm, int lane_in_block) {
-  constexpr int N = NB + 2;
-  const double h = m.timestep;
-  // classic RK4 as ONE dynamics call site in a 4-trip loop (stage weights 1,2,2,1; stage offsets h/2, h/2, h): the sums
-  // accumulate in the order the oracle writes them, so the result is bit-identical to the unrolled form at a quarter of
-  // the code size and without the ten stage arrays
-  double qs[N], vs[N], qsum[N], vsum[N], a[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) { qs[i] = q[i]; vs[i] = v[i]; qsum[i] = 0.0; vsum[i] = 0.0; }
-#pragma unroll 1
-  for (int stage = 0; stage < 4; ++stage) {
-    env_dynamics<NB, MR, BLOCK>(m, qs, vs, ctrl, a, sm, lane_in_block);
-    const double w = (stage == 1 || stage == 2) ? 2.0 : 1.0;
-    const double ch = (stage == 2) ? h : 0.5 * h;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      qsum[i] = stage == 0 ? vs[i] : qsum[i] + w * vs[i];
-      vsum[i] = stage == 0 ? a[i] : vsum[i] + w * a[i];
-      const double vn = v[i] + ch * a[i];
-      qs[i] = q[i] + ch * vs[i];
-      vs[i] = vn;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const double qn = q[i] + h / 6.0 * qsum[i];
-    const double vn = v[i] + h / 6.0 * vsum[i];
-    q[i] = qn; v[i] = vn;
-  }
 }
 
 struct EnvStepArgs {
@@ -506,98 +207,6 @@ extern "C" int ilsx_debug_eg_prof(unsigned long long* out16, int reset) {   // m
   return 0;
 }
 #endif
-
-template <int NB, int MR, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_env_step(const EnvStepArgs A) {
-  constexpr int N = NB + 2;
-  extern __shared__ __attribute__((aligned(16))) double smd_all[];
-  // The model record (2 KB of constants every phase of the dynamics reads, many of them under run-time indices: geom -> body, actuator
-  // -> body) is copied into LDS once per workgroup.  Read in place from global memory it cost ~100 vector loads per dynamics evaluation,
-  // each waited for on the spot by the one wave of its SIMD (rocprofv3: 1546 VMEM reads per wave per env step, SQ_WAIT_ANY 54 % of
-  // the wave's cycles): a broadcast LDS read is a tenth of that latency.
-  constexpr int MODEL_DOUBLES = (sizeof(PlanarModelDev) + 7) / 8;
-  {
-    const double* src = reinterpret_cast<const double*>(A.m);
-    for (int i = threadIdx.x; i < MODEL_DOUBLES; i += BLOCK) smd_all[i] = src[i];
-    __syncthreads();
-  }
-  const PlanarModelDev& m = *reinterpret_cast<const PlanarModelDev*>(smd_all);
-  double* smd = smd_all + MODEL_DOUBLES;
-  const int lane_in_block = threadIdx.x;
-  const int t = blockIdx.x * BLOCK + threadIdx.x;
-  if (t >= A.n_ids) return;
-  const int env = A.ids ? A.ids[t] : t;
-  if (A.frozen && A.frozen[env]) return;
-  const int o = m.obs_dim, na = m.n_act;
-  double q[N], v[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) { q[i] = A.qpos[(size_t)i * A.n_env + env]; v[i] = A.qvel[(size_t)i * A.n_env + env]; }
-  double ctrl[ENV_MAXB];
-  double ctrl_sq = 0.0;
-  for (int k = 0; k < na; ++k) {  // NormalizedBoxEnv: lb + (a+1)/2*(ub-lb), clip; ctrlrange is [-1,1] (wrappers.py:343-346)
-    const double a = fmin(fmax((double)A.act[(size_t)t * na + k], -1.0), 1.0);
-    ctrl[k] = a; ctrl_sq += a * a;
-  }
-  float obs_before[2 * N - 1];
-  if (A.replay) env_write_obs<NB>(m, q, v, obs_before);
-  const double x0 = q[0];
-  for (int s = 0; s < m.frame_skip; ++s) env_substep<NB, MR, BLOCK>(m, q, v, ctrl, smd, lane_in_block);
-  const double dt = m.timestep * m.frame_skip;
-  const double reward = (q[0] - x0) / dt + m.alive - m.ctrl_cost * ctrl_sq;  // hopper.py:16-18
-  bool ok;
-  if (m.task == 0) {  // hopper.py:19-25
-    ok = isfinite(q[0]) && isfinite(q[1]) && q[1] > m.z_min && fabs(q[2]) < m.ang_max;
-#pragma unroll
-    for (int i = 2; i < N; ++i) ok = ok && isfinite(q[i]) && fabs(q[i]) < m.state_max;
-#pragma unroll
-    for (int i = 0; i < N; ++i) ok = ok && isfinite(v[i]) && fabs(v[i]) < m.state_max;
-  } else if (m.task == 1) {   // walker2d.py:17-20
-    ok = q[1] > m.z_min && q[1] < m.z_max && q[2] > -m.ang_max && q[2] < m.ang_max;
-  } else {                    // HalfCheetah: done = False always
-    ok = true;
-  }
-  const bool done = !ok;
-  float ob[2 * N - 1];
-  env_write_obs<NB>(m, q, v, ob);
-  if (A.obs) for (int i = 0; i < o; ++i) A.obs[(size_t)t * o + i] = ob[i];
-  if (A.rew) A.rew[t] = (float)reward;
-  if (A.done) A.done[t] = done ? 1 : 0;
-  if (A.replay) {  // fused replay insert: one 128-byte-aligned record per transition
-    long long slot = A.top + env;
-    if (slot >= A.cap) slot -= A.cap;
-    float* rec = A.stage ? A.stage + ((size_t)env * A.stage_len + A.ep_len[env]) * A.rec : A.replay + (size_t)slot * A.rec;
-    for (int i = 0; i < o; ++i) rec[i] = obs_before[i];
-    const float* ra = A.rec_act ? A.rec_act : A.act;   // DAgger stores the expert's label, not the executed action
-    for (int k = 0; k < na; ++k) rec[o + k] = ra[(size_t)t * na + k];
-    rec[o + na] = (float)reward;
-    rec[o + na + 1] = (done && !A.no_terminal) ? 1.0f : 0.0f;   // base_algorithm.py:195-196,208-210
-    for (int i = 0; i < o; ++i) rec[o + na + 2 + i] = ob[i];
-    rec[2 * o + na + 2] = 0.0f; rec[2 * o + na + 3] = 0.0f;   // absorbing = [0, 0] (base_algorithm.py:211-213)
-  }
-  if (A.auto_reset) {
-    const int len = A.ep_len[env] + 1;
-    const double ret = A.ep_ret[env] + reward;
-    // time-limit ends are NOT terminal (base_algorithm.py:264-277).  With no_terminal the reference overwrites `terminals` BEFORE it
-    // decides to reset (:195-196 ahead of :215), so an unhealthy env is stepped on until the time limit: the fallen states are visited
-    // and rewarded, which is what grounds their values in adversarial IRL.  A state that is no longer finite always resets.
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) finite = finite && isfinite(q[i]) && isfinite(v[i]);
-    const bool end = (done && !A.no_terminal) || len >= A.max_path_length || !finite;
-    if (end) {
-      atomicAdd(&A.stats[0], 1.0);
-      atomicAdd(&A.stats[1], ret);
-      env_reset_state<NB>(m, A.seed, A.stream, A.step, (uint32_t)env, q, v);
-      env_write_obs<NB>(m, q, v, ob);
-    }
-    A.ep_len[env] = end ? 0 : len;
-    A.ep_ret[env] = end ? 0.0 : ret;
-    if (A.flush_len) A.flush_len[env] = end ? (len | ((done && !A.no_terminal) ? (1 << 30) : 0)) : 0;
-  }
-  if (A.obs_cur) for (int i = 0; i < o; ++i) A.obs_cur[(size_t)env * o + i] = ob[i];
-#pragma unroll
-  for (int i = 0; i < N; ++i) { A.qpos[(size_t)i * A.n_env + env] = q[i]; A.qvel[(size_t)i * A.n_env + env] = v[i]; }
-}
 
 template <int NB>
 __global__ void k_env_reset(const PlanarModelDev* mp, double* qpos, double* qvel, int n_env, const int* ids, int n_ids,
@@ -669,33 +278,11 @@ __global__ __launch_bounds__(256) void k_explore(const ExploreArgs X, float* __r
 }
 
 // ================================================================================================ 3-D engine kernels
-__device__ void e3_reset_state(const E3Ctx& C, uint64_t seed, uint32_t stream, unsigned long long step, uint32_t envu) {
-  const Spatial3Dev& m = *C.m;
-  double* scr = C.scr; const int n_env = C.n_env, env = C.env;
-  // humanoid.py:62-73 / ant.py:36-43: init + U(+-c) on every qpos component (the quaternion is re-normalised, as MuJoCo does
-  // before it uses it); qvel = U(+-c) (Humanoid) or 0.1 * randn (Ant)
-  for (int i = 0; i < m.nq; ++i) E3S(E3St::Q0 + i) = m.init_qpos[i] + m.reset_noise * (2.0 * env_uniform(seed, stream, step, envu, i) - 1.0);
-  {
-    double qw = E3S(E3St::Q0 + 3), qx = E3S(E3St::Q0 + 4), qy = E3S(E3St::Q0 + 5), qz = E3S(E3St::Q0 + 6);
-    const double nrm = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-    E3S(E3St::Q0 + 3) = qw * nrm; E3S(E3St::Q0 + 4) = qx * nrm; E3S(E3St::Q0 + 5) = qy * nrm; E3S(E3St::Q0 + 6) = qz * nrm;
-  }
-  for (int i = 0; i < m.nv; ++i) {
-    if (m.reset_noise_vel_std > 0.0) {
-      const double u1 = env_uniform(seed, stream, step, envu, m.nq + 2 * i), u2 = env_uniform(seed, stream, step, envu, m.nq + 2 * i + 1);
-      E3S(E3St::V0 + i) = m.reset_noise_vel_std * sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-    } else {
-      E3S(E3St::V0 + i) = m.reset_noise * (2.0 * env_uniform(seed, stream, step, envu, m.nq + i) - 1.0);
-    }
-  }
-  for (int k = 0; k < m.n_act; ++k) E3S(E3St::CTRL + k) = 0.0;   // qfrc_actuator of a freshly reset model is zero
-}
-
-// ---- wave-per-env form (env3d_wave.h): one 64-lane workgroup per env, working set in that wave's LDS (its reset draws; the kernels of
-// both forms are in env3d_kernels.inc)
+// ---- wave-per-env form (env3d_wave.h): one 64-lane workgroup per env, working set in that wave's LDS (its reset draws; the kernels are
+// in env3d_kernels.inc)
 __device__ __forceinline__ void e3w_reset_state(e3w_lds* S, const Spatial3Dev& m, int lane, uint64_t seed, uint32_t stream, unsigned long long step,
                                                 uint32_t envu) {
-  // same draws as e3_reset_state: component i of qpos uses counter i, qvel nq + i (uniform) or nq + 2i, nq + 2i + 1 (Box-Muller)
+  // component i of qpos uses counter i, qvel nq + i (uniform) or nq + 2i, nq + 2i + 1 (Box-Muller)
   E3W_FOR(i, m.nq) S[E3WOff::Q0 + i] = m.init_qpos[i] + m.reset_noise * (2.0 * env_uniform(seed, stream, step, envu, i) - 1.0);
   E3W_FOR(i, m.nv) {
     if (m.reset_noise_vel_std > 0.0) {
@@ -728,18 +315,6 @@ __device__ __forceinline__ void e3w_reset_state(e3w_lds* S, const Spatial3Dev& m
 // ------------------------------------------------------------------------------------------------ host
 // One launcher per kernel; a handle's two (step_fn, reset_fn) are chosen once, when it is created, by its engine's env_select_* below.
 // launch_env_step / launch_env_reset own what is common: the empty call, the ProfScope, the step counter, the launch error.
-template <int NB, int MR, int BLOCK>
-static int step_planar_lane(ilsx_vecenv* e, ProfScope& ps, const EnvStepArgs& A) {
-  using S = EnvScratch<NB, MR, BLOCK>;
-  const size_t lds = (size_t)S::TOTAL * BLOCK * sizeof(double) + ((sizeof(PlanarModelDev) + 7) / 8) * sizeof(double);   // per-env scratch + the model record
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIPCHK(hipFuncSetAttribute((const void*)k_env_step<NB, MR, BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done = true;
-  }
-  ILSX_LAUNCH(ps, (k_env_step<NB, MR, BLOCK>), dim3((A.n_ids + BLOCK - 1) / BLOCK), dim3(BLOCK), lds, e->ctx->stream, A);
-  return ILSX_OK;
-}
 // 16 lanes per env (env2d_group.h): one wavefront = one workgroup = 4 envs
 template <int NB, int MR>
 static int step_planar_group(ilsx_vecenv* e, ProfScope& ps, const EnvStepArgs& A) {
@@ -763,42 +338,31 @@ static int step_planar_group(ilsx_vecenv* e, ProfScope& ps, const EnvStepArgs& A
 ENV_RESET_FN(reset_planar4, k_env_reset<4>, LANES(n_ids, 256), 256, 0, e->dm, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL)
 ENV_RESET_FN(reset_planar7, k_env_reset<7>, LANES(n_ids, 256), 256, 0, e->dm, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL)
 static int env_select_planar(ilsx_vecenv* e) {
-  static const bool lane_form = getenv("ILSX_ENV2D_LANE") != nullptr;   // A/B: the first form, one lane per env
   const int nb = e->hm.nb;
   const bool wide = e->hm.max_rows > 12;
   if (nb == 4) {
-    e->step_fn = lane_form ? step_planar_lane<4, 8, 64> : step_planar_group<4, 8>;
+    e->step_fn = step_planar_group<4, 8>;
     e->reset_fn = reset_planar4;
   } else if (nb == 7) {
-    if (lane_form) e->step_fn = wide ? step_planar_lane<7, 16, 32> : step_planar_lane<7, 12, 64>;
-    else e->step_fn = wide ? step_planar_group<7, 16> : step_planar_group<7, 12>;
+    e->step_fn = wide ? step_planar_group<7, 16> : step_planar_group<7, 12>;
     e->reset_fn = reset_planar7;
   } else {
     ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "vec-env kernels are instantiated for 4 (Hopper) and 7 (Walker2d) bodies, got %d", nb);
   }
   return ILSX_OK;
 }
-// ---- 3-D engine: wave per env (env3d_wave.h), or the lane-per-env form (ILSX_ENV3D_LANE); *_trunc: the observation ends after qvel
+// ---- 3-D engine: wave per env (env3d_wave.h); *_trunc: the observation ends after qvel
 #define E3W_LDS ((size_t)E3WOff::TOTAL * 8)
 #define E3_DM (const Spatial3Dev*)e->dm3
 ENV_STEP_FN(step_3dw_23, k_env3dw_step<23>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)   // Humanoid
 ENV_STEP_FN(step_3dw_14, k_env3dw_step<14>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)   // Ant
 ENV_STEP_FN(step_3dw_any, k_env3dw_step<0>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)   // any other tree: run-time dof count
-ENV_STEP_FN(step_3d_lane, k_env3d_step, LANES(A.n_ids, 64), 64, 0, E3_DM, e->scr3)
 ENV_STEP_FN(step_3dw_23_trunc, k_env3dw_step_trunc<23>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)
 ENV_STEP_FN(step_3dw_14_trunc, k_env3dw_step_trunc<14>, dim3(A.n_ids), 64, E3W_LDS, E3_DM)
-ENV_STEP_FN(step_3d_lane_trunc, k_env3d_step_trunc, LANES(A.n_ids, 64), 64, 0, E3_DM, e->scr3)
 ENV_RESET_FN(reset_3dw, k_env3dw_reset, dim3(n_ids), 64, E3W_LDS, E3_DM, e->qpos, e->qvel, e->n_env, ids_dev, ENV_RESET_TAIL)
 ENV_RESET_FN(reset_3dw_trunc, k_env3dw_reset_trunc, dim3(n_ids), 64, E3W_LDS, E3_DM, e->qpos, e->qvel, e->n_env, ids_dev, ENV_RESET_TAIL)
-ENV_RESET_FN(reset_3d_lane, k_env3d_reset, LANES(n_ids, 64), 64, 0, E3_DM, e->scr3, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL)
-ENV_RESET_FN(reset_3d_lane_trunc, k_env3d_reset_trunc, LANES(n_ids, 64), 64, 0, E3_DM, e->scr3, e->qpos, e->qvel, e->n_env, ids_dev, n_ids, ENV_RESET_TAIL)
 static void env_select_spatial(ilsx_vecenv* e) {   // obs_trunc comes with 14 or 23 dofs only (ilsx_vecenv_create_spatial)
   const bool trunc = e->hm3->obs_trunc != 0;
-  if (!e->wave3) {
-    e->step_fn = trunc ? step_3d_lane_trunc : step_3d_lane;
-    e->reset_fn = trunc ? reset_3d_lane_trunc : reset_3d_lane;
-    return;
-  }
   if (e->nv == 23) e->step_fn = trunc ? step_3dw_23_trunc : step_3dw_23;
   else if (e->nv == 14) e->step_fn = trunc ? step_3dw_14_trunc : step_3dw_14;
   else e->step_fn = step_3dw_any;
@@ -963,22 +527,19 @@ extern "C" int ilsx_vecenv_create(ilsx_ctx* ctx, const ilsx_planar_model* pm, in
   return env_create_finish(guard, out);
 }
 
-// 3-D models (Ant / Humanoid): same handle type, same protocol entry points; the engine behind step / reset is env3d.h
+// 3-D models (Ant / Humanoid): same handle type, same protocol entry points; the engine behind step / reset is env3d_wave.h
 extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_model* sm, int n_env, uint64_t seed, ilsx_vecenv** out) {
   if (!ctx || !sm || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_spatial: bad argument");
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_vecenv* e = env_new(ctx, 1, n_env, seed);
   EnvGuard guard{e};
-  e->wave3 = !(getenv("ILSX_ENV3D_LANE") && atoi(getenv("ILSX_ENV3D_LANE")) != 0);
-  if (e->wave3) {
-    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<23>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
-    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<14>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
-    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<0>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
-    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_reset, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
-    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step_trunc<23>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
-    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step_trunc<14>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
-    HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_reset_trunc, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
-  }
+  HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<23>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+  HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<14>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+  HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step<0>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+  HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_reset, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+  HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step_trunc<23>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+  HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_step_trunc<14>, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
+  HIPCHK(hipFuncSetAttribute((const void*)k_env3dw_reset_trunc, hipFuncAttributeMaxDynamicSharedMemorySize, E3WOff::TOTAL * 8));
   e->hm3 = new Spatial3Dev();
   Spatial3Dev& m = *e->hm3;
   if (const char* why = e3_build_model(sm, m)) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_spatial: %s", why);
@@ -987,7 +548,6 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
   e->n = m.nq; e->nq = m.nq; e->nv = m.nv; e->o = m.obs_dim; e->a = m.n_act;
   env_select_spatial(e);
   ILSX_TRY(e->own.alloc_bytes(&e->dm3, sizeof m));
-  ILSX_TRY(e->own.alloc_bytes(&e->scr3, (size_t)E3Off::TOTAL * n_env * 8));
   HIPCHK(hipMemcpyAsync(e->dm3, &m, sizeof m, hipMemcpyHostToDevice, ctx->stream));
   return env_create_finish(guard, out);
 }
@@ -1590,7 +1150,7 @@ extern "C" int ilsx_rollout_step_end(ilsx_vecenv* e) {
 // Can the K runs' steps go out as ONE launch per stage?  Planar steppers of one kernel instantiation with the same env count, plain
 // observations, policies of one shape (the generic forward takes up to four tasks per launch), everything on one device.
 static bool rollout_runs_groupable(ilsx_vecenv* const* envs, ilsx_net* const* pis, int n_runs) {
-  static const bool off = getenv("ILSX_ROLLOUT_NO_GROUP") != nullptr || getenv("ILSX_ENV2D_LANE") != nullptr;
+  static const bool off = getenv("ILSX_ROLLOUT_NO_GROUP") != nullptr;
   if (off || n_runs < 2) return false;
   const ilsx_vecenv* e0 = envs[0];
   const ilsx_net* p0 = pis[0];

@@ -77,10 +77,6 @@ struct ilsx_sac {
   ilsx_replay* graph_rb = nullptr;
   int graph_B = 0;
   bool graph_defer = false, graph_phase = false, graph_own = false;
-  // split runs: the step as three captured segments with the two all-reduces between them (sac_split_segments)
-  hipGraphExec_t seg_graph[3] = {nullptr, nullptr, nullptr};
-  ilsx_replay* seg_rb = nullptr;
-  int seg_B = 0;
   // deferred tail (TailLite, kernels.h): active inside ilsx_sac_train_from_replay on the column-split path
   bool defer_tail = false;
   TailLite* tail_dev = nullptr;
@@ -92,7 +88,6 @@ struct ilsx_sac {
   int* phase_err = nullptr;          // set by a workgroup whose wait timed out
   PhaseConst pct;                    // the phase kernels' descriptor blocks in constant memory (host_common.h)
   bool phase_args_only = false;      // dry pass: build the two blocks, upload them, launch nothing (sac_phase_const_prime)
-  bool no_ct = false;                // this launch sequence must not depend on the slots' contents (captures that are replayed without a re-prime)
   bool phase_now = false;            // this step runs on the phase kernels
   bool phase_broken = false;         // a timeout was seen once: stay on the 8-launch path
   bool phase_last = false;           // the last window of steps ran on the phase kernels
@@ -357,7 +352,6 @@ extern "C" int ilsx_sac_destroy(ilsx_sac* s) {
   hipSetDevice(s->ctx->device);
   hipStreamSynchronize(s->ctx->stream);
   if (s->graph) hipGraphExecDestroy(s->graph);
-  for (hipGraphExec_t& g : s->seg_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
   if (s->pct.slot >= 0) {
     phase_const_free(s->pct.device, s->pct.slot);
     auto& v = s->ctx->phase_slots;
@@ -530,7 +524,7 @@ static int sac_critic_backward(ilsx_sac* s) {
         sac_policy_fin(s, Fz, eps2, s->rng_stream + 1, true, w.an, w.logp, w.ppart2);
         PA.fin_pi = Fz.fin; PA.fin_pi.use_gather_step = 1; PA.fin_pi_on = 1;
       }
-      ILSX_TRY(launch_phase_a(s->ctx, PA, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, (s->no_ct || s->phase_check_only) ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
+      ILSX_TRY(launch_phase_a(s->ctx, PA, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, s->phase_check_only ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
       if (s->phase_args_only) return ILSX_OK;
     } else {
       ILSX_TRY(sac_bwd(s, A, H, act, cs));
@@ -607,7 +601,7 @@ static int sac_actor_backward(ilsx_sac* s) {
       else {   // split run: this rank's alpha-gradient partial lands in the arena's slot before the actor all-reduce (the tail is deferred)
         PC.aslot = s->G + 2 * s->nq + s->np; PC.aslot_logp = w.logp; PC.aslot_B = B; PC.aslot_te = s->target_entropy; PC.aslot_invB = sac_inv_B(s);
       }
-      ILSX_TRY(launch_phase_c(s->ctx, PC, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, (s->no_ct || s->phase_check_only) ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
+      ILSX_TRY(launch_phase_c(s->ctx, PC, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, s->phase_check_only ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
       if (s->phase_args_only) return ILSX_OK;
     } else {
       ILSX_TRY(sac_bwd(s, A, H, act, cs));
@@ -706,7 +700,7 @@ static TailLite sac_tail_lite(ilsx_sac* s, int B) {
 // A split run (gradient all-reduce between backward and update) defers its tail only when the step runs on the merged phase kernels
 //   A , dW{Q} , all-reduce , Adam{Q} + Polyak , C (+ this rank's alpha-gradient partial) , dW{pi} , all-reduce , Adam{pi}
 // (6 launches + 2 collectives; the tail rides in the next step's A and applies the all-reduced alpha gradient, TailLite::slot_given).
-// Without the phase kernels (ILSX_NO_PHASE, ILSX_SPLIT_NO_PHASE, graph segments, a grid that does not fit) it keeps the un-deferred
+// Without the phase kernels (ILSX_NO_PHASE, ILSX_SPLIT_NO_PHASE, a grid that does not fit) it keeps the un-deferred
 // one-launch-per-stage sequence with k_sac_stats / k_sac_finish.
 // Above one rank the phase-kernel form is OPT-IN (ILSX_SPLIT_PHASE=1): its deferred tail fed from the all-reduced alpha slot and its
 // per-window roll-back vote have only ever run on a one-rank communicator (ILSX_SPLIT_FORCE), so a multi-rank run takes the plain
@@ -714,8 +708,7 @@ static TailLite sac_tail_lite(ilsx_sac* s, int B) {
 // occupancy and environment variables, which need not match across ranks, and one rank deciding differently would deadlock the job inside
 // RCCL: every rank contributes "I cannot" (0 / 1) to a one-float all-reduce and the window runs on the phase kernels only if nobody said so.
 static int sac_split_on_phase(ilsx_sac* s, int B, bool* on) {
-  static const bool segments = []() { const char* e = getenv("ILSX_SPLIT_SEGMENTS"); return e && atoi(e) != 0; }();
-  const bool mine = getenv("ILSX_SPLIT_NO_PHASE") == nullptr && !segments && sac_window_may_use_phase(s, B);
+  const bool mine = getenv("ILSX_SPLIT_NO_PHASE") == nullptr && sac_window_may_use_phase(s, B);
   *on = mine;
   if (!(s->ctx->comm && s->ctx->comm_n > 1)) return ILSX_OK;
   if (getenv("ILSX_SPLIT_PHASE") == nullptr) { *on = false; return ILSX_OK; }
@@ -1041,52 +1034,6 @@ static int sac_sample_and_step(ilsx_sac* s, ilsx_replay* rb, int B) {
 }
 
 static int sac_train_from_replay_once(ilsx_sac* s, ilsx_replay* rb, int n_steps, int B, ilsx_sac_stats* stats);
-// Split run (one run over G GPUs): the step's launches between the two gradient all-reduces are captured ONCE as three graph segments
-//   [draw + critic backward]  all-reduce(critic gradients)  [critic Adam + Polyak ; actor backward]  all-reduce(actor | alpha)  [actor Adam ; tail]
-// and replayed with the two ncclAllReduce calls enqueued directly between them: ~13 kernel launches per step become 3 graph launches,
-// while the collective itself stays OUT of the capture (RCCL inside a stream capture is the one thing a single-GPU box cannot exercise
-// with more than one rank; ILSX_SPLIT_GRAPH=1 captures the whole step including it).  OPT-IN (ILSX_SPLIT_SEGMENTS=1): measured at one rank
-// (profiles/r04_split_run_1rank.jsonl) the three small graphs are SLOWER than launching the 13 kernels directly — 107 us against 90 us per
-// step: a hipGraphLaunch costs more than the four launches it replaces — so the default stays direct launches.
-static int sac_split_segment(ilsx_sac* s, ilsx_replay* rb, int B, int seg) {
-  s->fuse_now = false;
-  if (seg == 0) {
-    if (s->cs > 1) s->gather_rb = rb;   // rows drawn inside the first forward launch
-    else { const SacWs& w = s->ws; ILSX_TRY(replay_launch_sample(rb, B, nullptr, s->scal, 0, w.s, w.a, w.r, w.d, w.s2, nullptr)); }
-    const int rc = sac_critic_backward(s);
-    s->gather_rb = nullptr;
-    return rc;
-  }
-  if (seg == 1) { ILSX_TRY(sac_critic_update(s)); return sac_actor_backward(s); }
-  return sac_actor_update(s);
-}
-static int sac_split_segments_step(ilsx_sac* s, ilsx_replay* rb, int B) {
-  hipStream_t st = s->ctx->stream;
-  if (s->seg_rb != rb || s->seg_B != B || !s->seg_graph[0]) {
-    for (hipGraphExec_t& g : s->seg_graph) if (g) { hipGraphExecDestroy(g); g = nullptr; }
-    for (int seg = 0; seg < 3; ++seg) {
-      hipGraph_t g = nullptr;
-      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      s->no_ct = true;   // these cached segments are not re-primed before their replays: their phase launches keep the argument segment
-      const int rc = sac_split_segment(s, rb, B, seg);
-      s->no_ct = false;
-      const hipError_t e = hipStreamEndCapture(st, &g);
-      if (rc != ILSX_OK) { if (g) hipGraphDestroy(g); return rc; }
-      if (e != hipSuccess) ILSX_FAIL(ILSX_ERR_HIP, "hipStreamEndCapture (split segment %d) failed: %s", seg, hipGetErrorString(e));
-      const hipError_t e2 = hipGraphInstantiate(&s->seg_graph[seg], g, nullptr, nullptr, 0);
-      hipGraphDestroy(g);
-      if (e2 != hipSuccess) { s->seg_graph[seg] = nullptr; ILSX_FAIL(ILSX_ERR_HIP, "hipGraphInstantiate (split segment %d) failed: %s", seg, hipGetErrorString(e2)); }
-    }
-    s->seg_rb = rb; s->seg_B = B;
-  }
-  HIPCHK(hipGraphLaunch(s->seg_graph[0], st));
-  ILSX_TRY(sac_allreduce(s, 0));
-  HIPCHK(hipGraphLaunch(s->seg_graph[1], st));
-  ILSX_TRY(sac_allreduce(s, 1));
-  HIPCHK(hipGraphLaunch(s->seg_graph[2], st));
-  return ILSX_OK;
-}
-
 extern "C" int ilsx_sac_train_from_replay(ilsx_sac* s, ilsx_replay* rb, int n_steps, int B, ilsx_sac_stats* stats) {
   // The reference records eval_statistics on the FIRST train_step after end_epoch (sac_alpha.py:185-190: `if self.eval_statistics is
   // None`), i.e. on the first batch of the call that asks for them.  The deferred tail has no statistics branch, so the call is cut there:
@@ -1147,13 +1094,7 @@ static int sac_train_from_replay_once(ilsx_sac* s, ilsx_replay* rb, int n_steps,
   struct DeferGuard { ilsx_sac* s; ~DeferGuard() { s->defer_tail = false; } } guard{s};   // never left on, whatever path returns
   const bool deferred = s->defer_tail;
   if (deferred && sac_window_may_use_phase(s, B)) ILSX_TRY(sac_snapshot_take(s));   // the roll-back point of this window
-  static const bool segments = []() { const char* e = getenv("ILSX_SPLIT_SEGMENTS"); return e && atoi(e) != 0; }();   // measured slower: see sac_split_segments_step
-  if (sac_is_split(s) && !split_graph && !no_graph_env && segments && !s->ctx->prof_on) {
-    for (int i = 0; i < n_steps; ++i) {
-      if (stats && i == n_steps - 1) ILSX_TRY(sac_request_stats(s));
-      ILSX_TRY(sac_split_segments_step(s, rb, B));
-    }
-  } else if (no_graph || s->ctx->prof_on) {
+  if (no_graph || s->ctx->prof_on) {
     for (int i = 0; i < n_steps; ++i) {
       if (stats && i == n_steps - 1) ILSX_TRY(sac_request_stats(s));
       const int rc = sac_sample_and_step(s, rb, B);
@@ -1396,9 +1337,8 @@ struct ilsx_sac_group {
   TailLite* tails_lite = nullptr;   // deferred tail: one record per agent (see TailLite, kernels.h)
   // agents living in contexts with a stream of their own (one per co-resident run: their rollouts overlap): the grouped launches go on
   // ctx->stream, fenced against every such stream at both ends of a train call (group_fence_in / group_fence_out)
-  std::vector<hipStream_t> peer_streams; std::vector<hipEvent_t> peer_events; hipEvent_t done_event = nullptr;
+  std::vector<hipStream_t> peer_streams;
   bool defer = false;
-  int mt = 1;                       // 16-row tiles per workgroup of the forward / backward launches (macro tiles, fwd_split_tile.inc)
   int late = -1;                    // "late weights" launch shape of the forward / backward launches: -1 per launch by size, 0 / 1 pinned (ILSX_GRP_LATE)
 };
 
@@ -1418,7 +1358,6 @@ static void group_release_tables(ilsx_sac_group* g) {
   if (g->graph) { hipGraphExecDestroy(g->graph); g->graph = nullptr; }
 }
 
-static int group_pick_mt(const ilsx_sac_group* g, int B);
 // collect every agent's launch list for one fused step on (rbs, B) and merge stage by stage
 static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
   const int K = (int)g->agents.size();
@@ -1484,16 +1423,10 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
       int tiles = 0, nmat = 0;
       // tile shape: as for single launches (launch_bwd_dw) the smallest that keeps the launch within ~3 workgroups per CU — it only
       // matters for small groups (K = 1, 2: +4 %); at K >= 4 the launch is bound elsewhere and every shape measures the same
-      const char* gse = getenv("ILSX_DW_TILE_GRP");   // "NH KT" digits (24, 14, 12, 11), unset / 0 = by size; read per group build
+      const char* gse = getenv("ILSX_DW_TILE_GRP");   // "NH KT" digits (24, 12, 11), unset / 0 = by size; read per group build
       const int gshape = gse ? atoi(gse) : 0;
       int gnh = 2, gkt = 4;
-      // ILSX_DW_GRP_STRIP = 1: the strip shape (k_dw_strip: one wavefront per 16 x 64 output strip, no cross-wave reduction).  Measured
-      // (K = 8 Hopper runs): 42 us per launch against 23 us for the 8-wave tiles — one wave walking 8 row-eighths and 8 optimiser
-      // epilogues in sequence is a longer dependent chain than eight waves and one LDS reduction; off by default, bit-identical, under test
-      const char* se = getenv("ILSX_DW_GRP_STRIP");
-      const bool strip = se ? atoi(se) != 0 : false;
-      if (strip) { gnh = 1; gkt = 4; }
-      else if (gshape) { gnh = gshape / 10; gkt = gshape % 10; }
+      if (gshape) { gnh = gshape / 10; gkt = gshape % 10; }
       else {
         auto count = [&](int nh, int kt) {
           long long n = 0;
@@ -1507,7 +1440,7 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
         if (count(1, 1) <= cap) { gnh = 1; gkt = 1; }
         else if (count(1, 2) <= cap) { gnh = 1; gkt = 2; }
       }
-      st.d.tile_nh = gnh; st.d.tile_kt = gkt; st.d.strip = strip ? 1 : 0;
+      st.d.tile_nh = gnh; st.d.tile_kt = gkt;
       for (int k = 0; k < K; ++k) {
         const DwArgs& D = cols[k].L[i].d;
         for (int m = 0; m < D.nmat; ++m, ++nmat) {
@@ -1540,7 +1473,6 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
   HIPCHK(hipStreamSynchronize(g->ctx->stream));
   g->rbs.assign(rbs, rbs + K);
   g->B = B;
-  g->mt = group_pick_mt(g, B);
   // ILSX_GRP_LATE = 0 | 1 pins the "late weights" launch shape off / on (kernels.h GRP == 3); by default each launch decides from its size
   if (const char* e = getenv("ILSX_GRP_LATE")) g->late = atoi(e) ? 1 : 0; else g->late = -1;
   return ILSX_OK;
@@ -1552,20 +1484,6 @@ static int group_launch_tail(ilsx_sac_group* g, const void* tails, int deferred)
   HIPCHK(hipGetLastError());
   return ILSX_OK;
 }
-// Row tiles per workgroup of the grouped forward / backward launches (macro tiles, fwd_split_tile.inc MT): ILSX_GRP_MT = 2 | 4 selects
-// them, the default is ONE.  Measured on MI355X (tools/grp_sweep.sh, profiles/r04_grp_sweep.txt; K = 8 Hopper runs, forward / backward
-// launch averages): 1 row tile 29.8 / 25.3 us, 2: 35.9 / 29.2, 4: 45.7 / 51.0 — sharing a wave's weight fragments over more rows does
-// not pay, because these kernels are not bound by fetching weights but by the instructions a wave issues PER ROW TILE (gather, Philox,
-// head epilogues, activation stores: ~1.5k of the ~2.6k a 16-row workgroup executes) at one or two waves per SIMD; a macro tile keeps
-// that per-row count, halves or quarters the workgroups in flight and (4 tiles: 105 KB of LDS) the waves per SIMD.  Kept, bit-identical
-// and under test (test_sac_group_lockstep_is_bitwise_the_independent_runs), as the measured answer to VERDICT r3 item 1.
-static int group_pick_mt(const ilsx_sac_group* g, int B) {
-  const ilsx_sac* s0 = g->agents[0];
-  (void)B;
-  if (!(s0->Lq.cfg.hidden == 256 && s0->cs == 4)) return 1;
-  if (const char* e = getenv("ILSX_GRP_MT")) { const int v = atoi(e); return (v == 2 || v == 4) ? v : 1; }
-  return 1;
-}
 static int group_launch_step(ilsx_sac_group* g) {
   ilsx_sac* s0 = g->agents[0];
   const int H = s0->Lq.cfg.hidden, act = s0->Lq.cfg.act, cs = s0->cs;
@@ -1576,11 +1494,10 @@ static int group_launch_step(ilsx_sac_group* g) {
       FwdArgs A = st.f;
       if (g->defer && nfwd < 2) { A.tail = g->tails_lite; A.tail_mode = nfwd + 1; A.tail_n = K; }   // tail of the previous step / gather_step
       ++nfwd;
-      A.mt = g->mt; A.swz.agents = K; A.mt_a = s0->a; A.late = g->late;
-      A.mt_not = std::max((s0->Lp.NO + 15) / 16, (s0->Lq.NO + 15) / 16);
+      A.late = g->late;
       ILSX_TRY(launch_fwd(g->ctx, A, H, act, st.KP, cs));
     }
-    else if (st.kind == 1) { BwdArgs A = st.b; A.mt = g->mt; A.swz.agents = K; A.late = g->late; ILSX_TRY(launch_bwd_dx(g->ctx, A, H, act, cs)); }
+    else if (st.kind == 1) { BwdArgs A = st.b; A.late = g->late; ILSX_TRY(launch_bwd_dx(g->ctx, A, H, act, cs)); }
     else if (st.kind == 2) { AdamFuse on; memset(&on, 0, sizeof on); on.on = 1; ILSX_TRY(launch_bwd_dw(g->ctx, g->own, st.d, g->B, &on)); }
     else if (!g->defer) ILSX_TRY(group_launch_tail(g, st.tails, 0));
   }
@@ -1608,36 +1525,22 @@ extern "C" int ilsx_sac_group_create(ilsx_ctx* ctx, ilsx_sac* const* agents, int
   for (int k = 0; k < n_agents; ++k) {
     hipStream_t st = agents[k]->ctx->stream;
     if (st == ctx->stream || std::find(g->peer_streams.begin(), g->peer_streams.end(), st) != g->peer_streams.end()) continue;
-    hipEvent_t ev = nullptr;
-    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    g->peer_streams.push_back(st); g->peer_events.push_back(ev);
+    g->peer_streams.push_back(st);
   }
-  if (!g->peer_streams.empty()) HIPCHK(hipEventCreateWithFlags(&g->done_event, hipEventDisableTiming));
   *out = g;
   return ILSX_OK;
 }
 // everything the agents' own streams have enqueued (rollout records in the rings, parameter uploads) happens before the grouped launches ...
-// HOST fences by default (ILSX_GROUP_FENCE unset / 2): wait for the peer streams before the first grouped launch, for the group stream after
-// the last.  Event fences (ILSX_GROUP_FENCE=1: hipEventRecord on each peer + hipStreamWaitEvent on the group stream, and the reverse at the
-// end — no host wait) were measured and rejected: a stream that has waited on another stream's event runs every LATER graph launch slower on
-// this stack — K = 10 Hopper runs, B = 512, 1000 steps per call: 275 us per lock-step with host fences or one shared stream, 284-320 us with
-// event fences (tools/grp_streams_ab.py, profiles/r06_grp_streams.txt).  The lock-step loop waits for every stream around a train call anyway.
-static int group_fence_mode() { static const int m = []() { const char* e = getenv("ILSX_GROUP_FENCE"); return e ? atoi(e) : 2; }(); return m; }
+// HOST fences: wait for the peer streams before the first grouped launch, for the group stream after the last.  The lock-step loop waits
+// for every stream around a train call anyway.  (Event fences between the streams were measured 3-16 % slower and removed: DESIGN §27.)
 static int group_fence_in(ilsx_sac_group* g) {
-  if (group_fence_mode() == 0) return ILSX_OK;
-  if (group_fence_mode() == 2) { for (hipStream_t st : g->peer_streams) HIPCHK(hipStreamSynchronize(st)); return ILSX_OK; }
-  for (size_t i = 0; i < g->peer_streams.size(); ++i) {
-    HIPCHK(hipEventRecord(g->peer_events[i], g->peer_streams[i]));
-    HIPCHK(hipStreamWaitEvent(g->ctx->stream, g->peer_events[i], 0));
-  }
+  for (hipStream_t st : g->peer_streams) HIPCHK(hipStreamSynchronize(st));
   return ILSX_OK;
 }
 // ... and whatever they enqueue next (rollout inference on the updated policy) happens after them
 static int group_fence_out(ilsx_sac_group* g) {
-  if (g->peer_streams.empty() || group_fence_mode() == 0) return ILSX_OK;
-  if (group_fence_mode() == 2) { HIPCHK(hipStreamSynchronize(g->ctx->stream)); return ILSX_OK; }
-  HIPCHK(hipEventRecord(g->done_event, g->ctx->stream));
-  for (hipStream_t st : g->peer_streams) HIPCHK(hipStreamWaitEvent(st, g->done_event, 0));
+  if (g->peer_streams.empty()) return ILSX_OK;
+  HIPCHK(hipStreamSynchronize(g->ctx->stream));
   return ILSX_OK;
 }
 
@@ -1647,8 +1550,6 @@ extern "C" int ilsx_sac_group_destroy(ilsx_sac_group* g) {
   hipStreamSynchronize(g->ctx->stream);
   group_release_tables(g);   // (the constant-table slots and the graph go with them)
   g->own.release();
-  for (hipEvent_t ev : g->peer_events) hipEventDestroy(ev);
-  if (g->done_event) hipEventDestroy(g->done_event);
   delete g;
   return ILSX_OK;
 }

@@ -23,9 +23,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #ifndef ILSX_LATE_WAVES
 #define ILSX_LATE_WAVES 4   // waves per SIMD the "late weights" grouped instantiations (GRP == 3) are compiled for
 #endif
-#ifndef ILSX_MT_WAVES
-#define ILSX_MT_WAVES 2   // waves per SIMD the macro-tile instantiations are compiled for (register budget 512 / this)
-#endif
 #define ILSX_MAX_HID 3
 #define ILSX_MAX_NO 64   // max total head outputs (n_heads*out_dim)
 
@@ -379,25 +376,6 @@ struct PolicyFinishArgs {
   float noise, noise_clip, max_act;   // head == HEAD_DET_TANH_NOISE (TD3): raw = pre-activation [rows][a]
   int use_gather_step;                // phase kernels: the Philox step is scal->gather_step (== the step counter once the pending tail has run)
 };
-// Grouped launches on a 1-D grid: workgroup -> (macro tile, task, column slice) such that the XCD a workgroup lands on (the dispatcher deals
-// workgroups to the 8 XCDs round-robin in linear order) depends on (agent, macro tile) ONLY — the same in every forward / backward launch
-// of the lock-step whatever its task count, so the activations of a row range stay in ONE XCD's L2 from the launch that writes them to the
-// launches that read them, and every XCD gets the same number of (agent, tile) pairs.  (With a (tiles, tasks, slices) grid padded to 8 in x,
-// four macro tiles per agent would put all work on XCDs 0-3.)   tpa = 0: off (3-D grid).
-struct GrpSwizzle { int tpa, tiles, agents, np8; };   // tasks per agent in this launch, macro tiles per agent, agents, ceil(agents*tiles/8)
-// decode: false = padding workgroup
-__device__ __forceinline__ bool grp_swizzle(const GrpSwizzle& S, int ncs, unsigned lin, int* bx, int* task, int* cs) {
-  const int xcd = lin & 7, q = lin >> 3;
-  const int pidx = q % S.np8, rest = q / S.np8;
-  const int p = pidx * 8 + xcd;
-  *cs = rest % ncs;
-  const int tk = rest / ncs;
-  if (p >= S.agents * S.tiles || tk >= S.tpa) return false;
-  const int ag = p / S.tiles;
-  *bx = p - ag * S.tiles;
-  *task = ag * S.tpa + tk;
-  return true;
-}
 struct FwdGroup;
 struct FwdArgs {
   FwdTask t[4];
@@ -418,12 +396,11 @@ struct FwdArgs {
   const struct TailLite* tail;   // column-split kernels, tail_mode != 0: the launch carries one extra y row whose first
   int tail_mode, tail_n;         //   workgroups (one per agent, tail_n of them) run the deferred tail (1) or advance gather_step (2)
   int l0_split;                  // wide inputs: layer 0 in a launch of its own, column-split like layer 1 (every task then has hsave[0])
-  int mt;                        // grouped launches: 16-row tiles per workgroup processed together (macro tile; 0 / 1 = one) — host side: picks the instantiation
-  int mt_not, mt_a;              //   host side (LDS sizing): the widest head of the launch's tasks in 16-output tiles, the widest finished policy
-  GrpSwizzle swz;                // grouped launches with a 1-D grid (see GrpSwizzle)
+  int reserved_mt[7];            // holds the layout (the removed macro-tile fields): may go in a change that measures it
   int ctab;                      // grouped launches, descriptor records in CONSTANT memory (g_fwd_tab, below): 1 + first slot of this launch's table; 0 = device table `tasks`
   int late;                      // with ctab: the GRP == 3 instantiation (layer-1 weight slice fetched right before its MFMA phase, 4 waves per SIMD)
 };
+static_assert(sizeof(FwdArgs) == 1456 && offsetof(FwdArgs, ctab) == 1448, "FwdArgs keeps the layout it had with the macro-tile fields (reserved_mt)");
 struct FwdGroup { PolicyFinishArgs fin; GatherSpec gather; const DevScalars* scal; int fin_on; };
 // one self-contained record per grid row: the task and its agent's per-launch state side by side, so a workgroup reaches
 // every pointer it needs with ONE dependent load level (a task -> group -> scalars chain cost ~2 us per level)
@@ -722,11 +699,11 @@ struct BwdArgs {
   int part_stride;          // column-split kernels: rows of one dx partial slab
   int xs;                   // XCD confinement (see FwdArgs)
   const BwdTask* tasks;     // grouped launch: descriptor table in device memory, indexed by blockIdx.y
-  int mt;                   // grouped launches: row tiles per workgroup (see FwdArgs::mt)
-  GrpSwizzle swz;
+  int reserved_mt[5];       // holds the layout (the removed macro-tile fields): may go in a change that measures it
   int ctab;                 // grouped launches: 1 + first slot in g_bwd_tab, 0 = device table `tasks` (see FwdArgs::ctab)
   int late;                 // see FwdArgs::late
 };
+static_assert(sizeof(BwdArgs) == 920 && offsetof(BwdArgs, ctab) == 908, "BwdArgs keeps the layout it had with the macro-tile fields (reserved_mt)");
 
 // dL/d(head output j) of row gr for the loss functor of task T (shared by the generic and the column-split
 // backward kernels).
@@ -1018,24 +995,9 @@ __constant__ BwdTask g_bwd_tab[GRP_CONST_SLOTS];
 // (Humanoid: KP = 396) that recomputation is 6x the slice's own layer-1 work, so the forward runs as two launches of the same grid:
 // PH = 1 stages x (gather / policy epilogue as in PH 0) and computes THIS slice's 64 columns of layer 0 into hsave[0];
 // PH = 2 starts from hsave[0] (16 KB per tile, L2-resident) and does layer 1 + heads.
-template <int H, int ACT, int CS, int GRP, int PH = 0, int MT = 1>   // GRP: 0 = tasks in the kernel arguments, 1 = device table, 2 = constant table
-__global__ __launch_bounds__(4 * H / CS, (MT > 1 ? ILSX_MT_WAVES : GRP == 3 ? ILSX_LATE_WAVES : 1)) void k_mlp2_fwd_split(const FwdArgs A) {
+template <int H, int ACT, int CS, int GRP, int PH = 0>   // GRP: 0 = tasks in the kernel arguments, 1 = device table, 2 = constant table
+__global__ __launch_bounds__(4 * H / CS, (GRP == 3 ? ILSX_LATE_WAVES : 1)) void k_mlp2_fwd_split(const FwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  static_assert(MT == 1 || GRP, "macro tiles are a grouped-launch shape");
-  int sw_bx = 0, sw_task = 0, sw_cs = 0;
-  if constexpr (GRP && MT > 1) {   // 1-D grid (GrpSwizzle); the deferred-tail workgroups follow the working ones
-    const unsigned nwork = 8u * A.swz.np8 * A.swz.tpa * CS;
-    if (blockIdx.x >= nwork) {
-      const int ag = blockIdx.x - nwork;
-      if (A.tail_mode && ag < A.tail_n) {
-        const TailLite& TL = A.tail[ag];
-        if (A.tail_mode == 1) tail_lite_run(TL, smem);
-        else if (threadIdx.x == 0) TL.scal->gather_step += 1;
-      }
-      return;
-    }
-    if (!grp_swizzle(A.swz, CS, blockIdx.x, &sw_bx, &sw_task, &sw_cs)) return;
-  } else {
   if (A.tail_mode && (int)blockIdx.y == A.ntasks) {   // the extra y row of a deferred-tail launch (an extra x column would shift
     const int ag = blockIdx.x + gridDim.x * blockIdx.z;  // the tile -> XCD mapping of every other workgroup, see launch_fwd)
     if (ag < A.tail_n) {
@@ -1045,21 +1007,20 @@ __global__ __launch_bounds__(4 * H / CS, (MT > 1 ? ILSX_MT_WAVES : GRP == 3 ? IL
     }
     return;
   }
-  }
   // GRP: descriptor records in device memory, copied by value at entry (before any store) so that their fields are
   // loaded once with scalar loads; a reference would be re-read with vector loads after every store
   // !GRP: the record stays where it is, in the kernel-argument segment (constant address space): a field is a scalar load at its
   // use and, when registers run short, is loaded again instead of being parked in a VGPR lane.  Copying the record by value here
   // made ~100 scalars live at once: 196 v_writelane + 369 v_readlane in this kernel (a quarter of a wave's issue slots in the prologue).
   FwdTaskG Rg;
-  const int ty = (GRP && MT > 1) ? sw_task : (int)blockIdx.y;
+  const int ty = (int)blockIdx.y;
   if (GRP == 1) Rg = A.tasks[ty];
   const FwdTaskG& Rc = g_fwd_tab[GRP >= 2 ? A.ctab - 1 + ty : 0];
   const FwdTask& T = GRP >= 2 ? Rc.t : GRP == 1 ? Rg.t : A.t[ty];
   const FwdGroup* GP = GRP >= 2 ? &Rc.g : GRP == 1 ? &Rg.g : nullptr;
   // the body is shared as TEXT with the merged phase kernels (see fwd_split_tile.inc for why it is not a device function)
   constexpr bool XCH = false;
-  const int bx = (GRP && MT > 1) ? sw_bx : (int)blockIdx.x, cs = (GRP && MT > 1) ? sw_cs : (int)blockIdx.z;
+  const int bx = (int)blockIdx.x, cs = (int)blockIdx.z;
   const bool first_task = ty == 0;
   constexpr int FIN_CT = 0;
 #define XCH_HOOK_STAGE
@@ -1113,20 +1074,15 @@ __global__ __launch_bounds__(64) void k_policy_finish(const PolicyFinishArgs P) 
   if (P.logp) P.logp[gr] = -0.5f * lp_quad - (lp_ls + HALF_LOG_2PI) - lp_jac;
 }
 
-template <int H, int ACT, int CS, int GRP, int MT = 1>
-__global__ __launch_bounds__(4 * H / CS, (MT > 1 ? ILSX_MT_WAVES : GRP == 3 ? ILSX_LATE_WAVES : 1)) void k_mlp2_bwd_split(const BwdArgs A) {
+template <int H, int ACT, int CS, int GRP>
+__global__ __launch_bounds__(4 * H / CS, (GRP == 3 ? ILSX_LATE_WAVES : 1)) void k_mlp2_bwd_split(const BwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  static_assert(MT == 1 || GRP, "macro tiles are a grouped-launch shape");
-  int sw_bx = 0, sw_task = 0, sw_cs = 0;
-  if constexpr (GRP && MT > 1) {
-    if (!grp_swizzle(A.swz, CS, blockIdx.x, &sw_bx, &sw_task, &sw_cs)) return;
-  }
-  const int ty = (GRP && MT > 1) ? sw_task : (int)blockIdx.y;
+  const int ty = (int)blockIdx.y;
   BwdTask Tg;
   if (GRP == 1) Tg = A.tasks[ty];   // by value at entry (see k_mlp2_fwd_split)
   const BwdTask& T = GRP >= 2 ? g_bwd_tab[A.ctab - 1 + ty] : GRP == 1 ? Tg : A.t[ty];   // GRP 0 / 2: read in place (kernel arguments / constant table)
   constexpr bool XCH = false;
-  const int bx = (GRP && MT > 1) ? sw_bx : (int)blockIdx.x, cs = (GRP && MT > 1) ? sw_cs : (int)blockIdx.z;
+  const int bx = (int)blockIdx.x, cs = (int)blockIdx.z;
   constexpr int LOSS_CT = -1, NO_CT = 0;   // run time: T.loss, N.NO
 #define XCH_HOOK_ACT
 #define XCH_HOOK_HEAD
@@ -1182,6 +1138,7 @@ struct PhaseCArgs {
   float* aslot; const float* aslot_logp; int aslot_B; float aslot_te, aslot_invB;
 };
 
+static_assert(sizeof(PhaseAArgs) == 3984 && sizeof(PhaseCArgs) == 3376, "the phase descriptors embed FwdArgs / BwdArgs: same layout as with the macro-tile fields");
 static_assert(sizeof(PhaseAArgs) <= 4096 && sizeof(PhaseCArgs) <= 4096, "phase-kernel descriptors travel in the kernel-argument segment (4 KB)");
 #define PHASE_CONST_SLOTS 64
 #ifdef ILSX_KERNEL_IMPL
@@ -1294,7 +1251,7 @@ template <int H, int ACT, int CS, bool CT = false>
 __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_a(const PhaseAArgs Pk, int slot) {
   const PhaseAArgs& P = CT ? g_phase_a_tab[slot] : Pk;
   constexpr int GRP = 0; constexpr bool XCH = true;
-  constexpr int PH = 0, MT = 1;
+  constexpr int PH = 0;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const FwdGroup* GP = nullptr;
   const int bx = blockIdx.x, cs = blockIdx.z, y = blockIdx.y;
@@ -1411,7 +1368,7 @@ template <int H, int ACT, int CS, bool CT = false>
 __global__ __launch_bounds__(4 * H / CS) void k_sac_phase_c(const PhaseCArgs Pk, int slot) {
   const PhaseCArgs& P = CT ? g_phase_c_tab[slot] : Pk;
   constexpr int GRP = 0; constexpr bool XCH = true;
-  constexpr int PH = 0, MT = 1;
+  constexpr int PH = 0;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const FwdGroup* GP = nullptr;
   const int bx = blockIdx.x, cs = blockIdx.z, y = blockIdx.y;
@@ -1526,8 +1483,9 @@ struct DwArgs {
   unsigned* zero_flags;   // non-null: workgroup 0 zeroes the PHASE_NFLAGS arrival counters of the phase kernel that follows this launch
   const int* zero_err;    //   ... or arms them satisfied (PHASE_FLAG_DEAD) when *zero_err says a wait of this window already gave up
   int tile_nh, tile_kt;   // grouped launches: the tile shape the gtiles table was built for (0 = 2 x 4); host-side only
-  int strip;              // grouped launches: the table is one record per 16 x 64 output strip of k_dw_strip (one wavefront each); host-side only
+  int reserved_strip;     // holds the layout (the removed strip shape's flag): may go in a change that measures it
 };
+static_assert(sizeof(DwArgs) == 1072 && offsetof(DwArgs, reserved_strip) == 1064, "DwArgs keeps the layout it had with the strip flag (reserved_strip)");
 struct DwTileG { DwMat J; AdamFuse F; };
 #define DW_SPLIT_MIN_ROWS 1024
 #define DW_BIG_MIN_ROWS 4096
@@ -1957,212 +1915,6 @@ __global__ __launch_bounds__(256, 2) void k_dw_big(const DwArgs D) {
       b += __shfl_xor(b, 32, 64);
       const int n = nw0 + 16 * i + li;
       if (g == 0 && n < J.NA) slab[off_b + n] = b;
-    }
-  }
-}
-
-// ---- the weight gradients in throughput shape (grouped launches: K co-resident runs).  ONE wavefront (a 64-thread workgroup) owns a
-// 16 (n) x 64 (k) output strip completely: it runs all eight row-eighth contractions k_mlp_bwd_dw spreads over eight waves — eight
-// accumulator sets, the same MFMA chain per row-eighth (rows rc + 128 u + 4 g + s, u = 0..1, s = 0..3, per 256-row trip) — and adds
-// the eight partial tiles in the order that kernel's LDS reduction adds them (r8 = 0..7), so every gradient, moment and parameter
-// is bit-identical to the tiled kernel's.  What goes away: the 16-wave workgroup whose barrier waits for its slowest wave, the 8-way
-// reduction through LDS, and 15 of 16 descriptor reads; what stays in LDS is one wave-private 16 x 16 transpose per output block
-// (accumulator order -> address order of the packed layouts: every optimiser stream of the epilogue then moves whole 16-byte words
-// per lane, 1 KiB per instruction).  The second packing of a hidden -> hidden matrix is updated from ITS OWN copies of P / M / V / T
-// (identical to the first packing's by construction: both are written with the same values by every kernel) instead of from values
-// carried across lanes.  256 MFMAs per strip.
-#define DW_STRIP_LDS_FLOATS (4 * 16 * 20)
-template <bool GRP, bool WHOLE>   // WHOLE: the contraction is whole 256-row trips (host-checked), no row guards
-__global__ __launch_bounds__(64, 2) void k_dw_strip(const DwArgs D) {
-  __shared__ __attribute__((aligned(16))) float tile[DW_STRIP_LDS_FLOATS];   // [4 k tiles][16 n][20: 16 k + pad]
-  static_assert(GRP, "the strip shape is a grouped-launch shape");
-  const DwTileG Rg = D.gtiles[blockIdx.x];   // by value at entry: scalar loads (blockIdx is uniform)
-  const DwMat& J = Rg.J;
-  const AdamFuse& F = Rg.F;
-  const int local = blockIdx.x - J.tile0;
-  const int n0 = (local / J.ktiles) * 16, k0 = (local % J.ktiles) * 64;
-  const int rows = J.rows > 0 ? J.rows : D.rows_all, brows = J.rows > 0 ? J.bias_rows : D.rows_all;
-  const int lane = threadIdx.x, li = lane & 15, g = lane >> 4;
-  const bool n_ok = n0 + li < J.NA;
-  int ntk = (J.NB - k0 + 15) / 16;
-  if (ntk > 4) ntk = 4;
-  bool k_ok[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) k_ok[t] = k0 + 16 * t + li < J.NB;
-  float ad_step = 0.f, ad_bc2s = 1.f;
-  if (F.on) { ad_step = *F.step_size; ad_bc2s = *F.bc2_sqrt; }
-  f32x4 acc[8][4];
-  float bs[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) {
-    bs[w] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[w][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  const bool want_bias = J.db != nullptr && k0 == 0;
-  // operand addresses: one pointer per lane and operand column (columns past the matrix are clamped onto its last one and the value
-  // dropped by a select, so that no load sits under a branch: a predicated load costs ~8 instructions of mask handling, and this kernel
-  // lives on instruction issue); rows need no clamp when the batch is whole 256-row trips (the SAC batch), else the guarded form below
-  // (the table's pointers come out of memory, so the compiler knows no address space for them and would emit FLAT loads, which count on
-  //  both memory counters and force full waits between batches; they are global memory)
-  typedef const float __attribute__((address_space(1)))* gfptr;
-  const gfptr pa = (gfptr)(J.A + (size_t)(4 * g) * J.lda + (n_ok ? n0 + li : J.NA - 1));
-  gfptr pb[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) pb[t] = (gfptr)(J.Bm + (size_t)(4 * g) * J.ldb + (k_ok[t] ? k0 + 16 * t + li : J.NB - 1));
-  for (int rc0 = 0; rc0 < rows; rc0 += 256) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {   // row-eighth w of this 256-row trip: rows rc0 + 16 w + {0..15} and + 128
-      const int rc = rc0 + 16 * w;
-      if (rc >= rows) continue;   // uniform (the tiled kernel's wave w does not take this trip either)
-      float a[2][4], b[2][4][4];
-      if constexpr (WHOLE) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) {
-            const size_t ro = (size_t)(rc + 128 * u + s4);   // uniform part of the row index (the lane's 4 g is in the pointers)
-            const float av = pa[ro * J.lda];
-            a[u][s4] = n_ok ? av : 0.0f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { const float bv = pb[t][ro * J.ldb]; b[u][t][s4] = k_ok[t] ? bv : 0.0f; }
-          }
-      } else {
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-          const int r = rc + 128 * u + 4 * g + s4;
-          const bool r_ok = r < rows;
-          a[u][s4] = (r_ok && n_ok) ? J.A[(size_t)r * J.lda + n0 + li] : 0.0f;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) b[u][t][s4] = (r_ok && k_ok[t]) ? J.Bm[(size_t)r * J.ldb + k0 + 16 * t + li] : 0.0f;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) acc[w][t] = MFMA16(a[u][s4], b[u][t][s4], acc[w][t]);   // k tiles past the matrix contract zeros and are not stored
-        }
-      if (want_bias) {   // uniform; same order of additions as the tiled kernel (u, then s)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) {
-            if constexpr (WHOLE) bs[w] += a[u][s4];   // whole trips and no row-stacked jobs (host-checked): every row feeds the bias
-            else bs[w] += (rc + 128 * u + 4 * g + s4 < brows) ? a[u][s4] : 0.0f;
-          }
-      }
-    }
-  }
-  // ---- the eight partial tiles in r8 order (k_mlp_bwd_dw: s = 0; s += part[r8])
-  f32x4 out[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    out[t] = (f32x4){0.f, 0.f, 0.f, 0.f};   // (0 + part[0] like the tiled kernel: a -0 partial ends as +0 there too)
-#pragma unroll
-    for (int w = 0; w < 8; ++w) { out[t][0] += acc[w][t][0]; out[t][1] += acc[w][t][1]; out[t][2] += acc[w][t][2]; out[t][3] += acc[w][t][3]; }
-  }
-  // accumulator order (lane = column k, register = row n = 4 g + v) -> LDS [t][n][k]
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) tile[(t * 16 + 4 * g + v) * 20 + li] = out[t][v];
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // one wavefront: its LDS operations execute in order, this only keeps the compiler from moving the reads up
-  const int nl = lane & 15, q4 = lane >> 4;   // address order of a forward-packed / natural block: lane <-> (n = lane % 16, k = 4 (lane / 16) .. + 3)
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    if (t >= ntk) continue;   // uniform
-    const int n = n0 + nl, k = k0 + 16 * t + 4 * q4;
-    const float4 gv = *reinterpret_cast<const float4*>(tile + (t * 16 + nl) * 20 + 4 * q4);
-    const float gs[4] = {gv.x, gv.y, gv.z, gv.w};
-    if (J.mode == DW_OUT_NATURAL) {   // row-major [NA][ldw]: heads (NB = H: k + 3 < NB whenever k < NB, H is a multiple of 16)
-      if (n < J.NA && k < J.NB) {
-        float* gp = J.dW + (size_t)n * J.ldw + k;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          if (k + c < J.NB) {
-            gp[c] = gs[c];
-            if (F.on) { const AdamOperands o = adam_prefetch(F, (size_t)(gp + c - F.Gbase)); adam_apply(F, ad_step, ad_bc2s, o, (size_t)(gp + c - F.Gbase), 0, false, gs[c]); }
-          }
-        }
-      }
-    } else if (n < J.NA && k < J.NB) {   // forward-packed block: 4 consecutive floats per lane (k % 4 = 0..3).  NA, NB are multiples of 16 for packed matrices
-      float* gp = J.dW + pack_f(n, k, J.ldw);
-      const size_t i0 = (size_t)(gp - F.Gbase);
-      float4 p4, m4, v4, t4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (F.on) {
-        p4 = *reinterpret_cast<const float4*>(F.P + i0); m4 = *reinterpret_cast<const float4*>(F.M + i0); v4 = *reinterpret_cast<const float4*>(F.V + i0);
-        if (F.T) t4 = *reinterpret_cast<const float4*>(F.T + i0);
-      }
-      *reinterpret_cast<float4*>(gp) = gv;
-      if (F.on) {
-        float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w}, tt[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {   // adam_apply's expressions, in its order
-          const float gg = gs[c] + F.l2x2 * pp[c];
-          const float m = mm[c] * F.b1 + (1.0f - F.b1) * gg;
-          const float v = vv[c] * F.b2 + (1.0f - F.b2) * gg * gg;
-          const float pn = pp[c] - ad_step * (m / (sqrtf(v) / ad_bc2s + F.eps));
-          mm[c] = m; vv[c] = v; pp[c] = pn;
-          if (F.T) tt[c] = tt[c] * (1.0f - F.tau) + pn * F.tau;
-        }
-        *reinterpret_cast<float4*>(F.M + i0) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        *reinterpret_cast<float4*>(F.V + i0) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        *reinterpret_cast<float4*>(F.P + i0) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        if (F.T) *reinterpret_cast<float4*>(F.T + i0) = make_float4(tt[0], tt[1], tt[2], tt[3]);
-      }
-    }
-    if (J.mode == DW_OUT_PACK_FB) {   // second packing: lane <-> (k = lane % 16, n = 4 (lane / 16) .. + 3); its own P / M / V / T copies
-      const int kb = k0 + 16 * t + nl, nb = n0 + 4 * q4;
-      if (nb < J.NA && kb < J.NB) {
-        float gb[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) gb[c] = tile[(t * 16 + 4 * q4 + c) * 20 + nl];
-        float* gp = J.dWb + pack_b(nb, kb, J.NA);
-        const size_t i1 = (size_t)(gp - F.Gbase);
-        float4 p4, m4, v4, t4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (F.on) {
-          p4 = *reinterpret_cast<const float4*>(F.P + i1); m4 = *reinterpret_cast<const float4*>(F.M + i1); v4 = *reinterpret_cast<const float4*>(F.V + i1);
-          if (F.T) t4 = *reinterpret_cast<const float4*>(F.T + i1);
-        }
-        *reinterpret_cast<float4*>(gp) = make_float4(gb[0], gb[1], gb[2], gb[3]);
-        if (F.on) {
-          float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w}, tt[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const float gg = gb[c] + F.l2x2 * pp[c];
-            const float m = mm[c] * F.b1 + (1.0f - F.b1) * gg;
-            const float v = vv[c] * F.b2 + (1.0f - F.b2) * gg * gg;
-            const float pn = pp[c] - ad_step * (m / (sqrtf(v) / ad_bc2s + F.eps));
-            mm[c] = m; vv[c] = v; pp[c] = pn;
-            if (F.T) tt[c] = tt[c] * (1.0f - F.tau) + pn * F.tau;
-          }
-          *reinterpret_cast<float4*>(F.M + i1) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-          *reinterpret_cast<float4*>(F.V + i1) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-          *reinterpret_cast<float4*>(F.P + i1) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-          if (F.T) *reinterpret_cast<float4*>(F.T + i1) = make_float4(tt[0], tt[1], tt[2], tt[3]);
-        }
-      }
-    }
-  }
-  // ---- bias gradients (strips with k0 == 0): per row-eighth the sum over the four lane groups as the tiled kernel's two shuffles form it,
-  //      then the eighths in r8 order
-  if (want_bias) {   // uniform
-    float sb = 0.0f;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-      float x = bs[w];
-      x += __shfl_xor(x, 16, 64);
-      x += __shfl_xor(x, 32, 64);
-      sb += x;
-    }
-    if (g == 0 && n_ok) {
-      float* gbp = J.db + n0 + li;
-      *gbp = sb;
-      if (F.on) { const AdamOperands o = adam_prefetch(F, (size_t)(gbp - F.Gbase)); adam_apply(F, ad_step, ad_bc2s, o, (size_t)(gbp - F.Gbase), 0, false, sb); }
     }
   }
 }

@@ -1,5 +1,5 @@
 /* TEST INFRASTRUCTURE, not product: a scalar C restatement of oracle/planar_env.py (the planar articulated-body stepper the HIP
- * kernel k_env_step must reproduce), for ONE purpose — the CPU leg of bench.py's `cpu_baseline` for env-steps/s (SURVEY section 8d asks
+ * kernel k_envg_step must reproduce), for ONE purpose — the CPU leg of bench.py's `cpu_baseline` for env-steps/s (SURVEY section 8d asks
  * for a scalar compiled env stepper on the host's cores; the numpy statement is ~1000x slower than compiled code and would say nothing
  * about a CPU).  Same dense formulation as the numpy file, line for line: dense Jacobians, M = sum m Jc^T Jc + I Jphi^T Jphi, Gaussian
  * elimination, constraint rows (capsule ends within the margin: normal + tangent; violated joint limits), projected Gauss-Seidel, RK4

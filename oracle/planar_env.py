@@ -1,4 +1,4 @@
-"""CPU statement of the planar articulated-body stepper (the thing the HIP kernel k_env_step must
+"""CPU statement of the planar articulated-body stepper (the thing the HIP kernel k_envg_step must
 reproduce).  numpy float64, one env at a time, generic linear algebra — written independently of the
 HIP code (which uses explicit recursions and a hand-rolled Cholesky) so that agreement means something.
 Test infrastructure.

@@ -1,5 +1,5 @@
 /* TEST INFRASTRUCTURE, not product: a scalar C restatement of oracle/spatial_env.py (the 3-D articulated-body stepper the HIP kernels
- * k_env3dw_step / k_env3d_step must reproduce: Ant-v2, Humanoid-v2), for ONE purpose — the CPU leg of bench.py's `cpu_baseline` for the
+ * k_env3dw_step must reproduce: Ant-v2, Humanoid-v2), for ONE purpose — the CPU leg of bench.py's `cpu_baseline` for the
  * Humanoid env-steps/s of BASELINE config 5 ("env-step CPU baseline: the build's scalar C++ stepper, 1 thread and all
  * cores"; the numpy statement is ~1000x slower than compiled code and says nothing about a CPU).  Same DENSE formulation as the numpy
  * file, function for function — per-link 3 x nv Jacobians, M = sum m Jc^T Jc + Jw^T Iw Jw, bias from the velocity-product accelerations,

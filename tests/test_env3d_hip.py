@@ -1,4 +1,4 @@
-"""GPU suite: the 3-D stepper (k_env3d_step / k_env3d_reset, Ant-v2 and Humanoid-v2) through the C ABI against
+"""GPU suite: the 3-D stepper (k_env3dw_step / k_env3dw_reset, Ant-v2 and Humanoid-v2) through the C ABI against
 oracle/spatial_env.py (float64), plus the fused rollout step writing 376-wide Humanoid records into the replay ring."""
 import numpy as np
 import pytest

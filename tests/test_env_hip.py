@@ -1,4 +1,4 @@
-"""GPU suite: k_env_step / k_env_reset / the fused rollout step against the CPU oracle (float64)."""
+"""GPU suite: k_envg_step / k_env_reset / the fused rollout step against the CPU oracle (float64)."""
 import numpy as np
 import pytest
 

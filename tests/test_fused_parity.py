@@ -255,23 +255,21 @@ def test_split_run_phases_with_rccl_on_the_ctx_stream_equal_the_fused_step():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = {}
-    # split: the default form — every launch direct; split_segments: three captured segments with the two all-reduces enqueued between them;
+    # split: the default form — every launch direct;
     # split_graph: the whole step, collective included, in one capture
     # (round 5: the default split step runs on the merged phase kernels — A, dW, all-reduce, Adam, C, dW, all-reduce, Adam, the tail deferred
     #  and fed the all-reduced alpha gradient; split_nophase keeps one launch per stage with k_sac_stats / k_sac_finish)
     on_phase = {}
     for tag, extra in (("fused", {}), ("split", {"ILSX_SPLIT_FORCE": "1"}), ("split_nophase", {"ILSX_SPLIT_FORCE": "1", "ILSX_SPLIT_NO_PHASE": "1"}),
-                       ("split_segments", {"ILSX_SPLIT_FORCE": "1", "ILSX_SPLIT_SEGMENTS": "1"}),
                        ("split_graph", {"ILSX_SPLIT_FORCE": "1", "ILSX_SPLIT_GRAPH": "1"})):
         env = dict(os.environ, **extra)
         r = subprocess.run([sys.executable, "-c", _SPLIT_SCRIPT], cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, (tag, r.stderr[-3000:])
         outs[tag] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])   # RCCL prints its own banner lines
         on_phase[tag] = [l for l in r.stderr.splitlines() if l.startswith("PHASE")][-1] == "PHASE 1"
-    assert on_phase["fused"] and on_phase["split"] and on_phase["split_graph"] and not on_phase["split_nophase"] and not on_phase["split_segments"], on_phase
+    assert on_phase["fused"] and on_phase["split"] and on_phase["split_graph"] and not on_phase["split_nophase"], on_phase
     assert outs["split"] == outs["fused"], outs
     assert outs["split_nophase"] == outs["fused"], outs
-    assert outs["split_segments"] == outs["fused"], outs
     assert outs["split_graph"] == outs["fused"], outs
 
 

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
-"""Grouped (co-resident seeds) SAC lock-step: time and per-kernel averages for one setting of the macro-tile knobs.
+"""Grouped (co-resident seeds) SAC lock-step: time and per-kernel averages for one setting of the launch-shape knobs.
 
-    ILSX_GRP_MT=4 [ILSX_LIB=ilswiss_amd/libilsx_<variant>.so] python tools/grp_sweep.py hopper 8 [n_steps]
+    ILSX_GRP_LATE=1 [ILSX_LIB=ilswiss_amd/libilsx_<variant>.so] python tools/grp_sweep.py hopper 8 [n_steps]
     python tools/grp_sweep.py humanoid 4
 
 One JSON line: K, dims, us per lock-step, aggregate grad-steps/s, and the HIP-event average of every kernel class of the step
 (ilsx_prof_*: the dispatch's own begin / end stamps).  Synthetic replay contents of the task's widths (no env stepping).
-tools/grp_sweep.sh runs the grid of settings in separate processes (the group's launch shape is fixed when it is built).
+Run one process per setting (the group's launch shape is fixed when it is built): tools/grp_latew.sh, tools/ab_dw_low.sh.
 """
 import json
 import os
@@ -59,7 +59,7 @@ def main():
             kern[name]["tflops"] = K * npf * sf[kid] / (ms * 1e-3) / 1e12
             kern[name]["frac"] = kern[name]["tflops"] / PEAK_F32_MFMA_TFLOPS
     finite = all(np.isfinite(t.get_params("policy")).all() for t in trs)
-    print(json.dumps(dict(task=task, K=K, mt=os.environ.get("ILSX_GRP_MT", "default"), lib=os.path.basename(os.environ.get("ILSX_LIB", "libilsx.so")),
+    print(json.dumps(dict(task=task, K=K, lib=os.path.basename(os.environ.get("ILSX_LIB", "libilsx.so")),
                           us_per_lockstep=1e6 * dt / n, aggregate_grad_steps_per_s=K * n / dt, finite=finite, kernels=kern)), flush=True)
     grp.close()
     c.close()

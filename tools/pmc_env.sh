@@ -1,5 +1,5 @@
 #!/bin/bash
-# Dynamic instruction mix and wait fractions of the planar stepper (k_env_step) — rocprofv3 counter passes over tools/rollout_overhead.py.
+# Dynamic instruction mix and wait fractions of the planar stepper (k_envg_step) — rocprofv3 counter passes over tools/rollout_overhead.py.
 #   bash tools/pmc_env.sh <tag>    (on the GPU box, from the repo root)
 set -u
 TAG=${1:-r03}

@@ -15,10 +15,10 @@ timeout 200 python tools/phase_gantt.py > $OUT/phase_gantt.txt 2>&1
 timeout 200 python tools/rollout_overhead.py 4096 > $OUT/rollout_overhead.txt 2>&1
 timeout 100 python tools/rollout_overhead.py 8192 >> $OUT/rollout_overhead.txt 2>&1
 (cd tools/ubench && timeout 60 ./tilesync) > $OUT/tilesync.txt 2>&1
-# the split-run leg on a one-rank communicator in its four forms: merged phase kernels (default since round 5), one launch per stage, graph
-# segments between the two all-reduces, the whole step with the collective in one capture
+# the split-run leg on a one-rank communicator in its three forms: merged phase kernels (default since round 5), one launch per stage,
+# the whole step with the collective in one capture
 : > $OUT/split_run_1rank.jsonl
-for form in "phase_kernels:ILSX_SPLIT_SEGMENTS=0" "one_launch_per_stage:ILSX_SPLIT_NO_PHASE=1" "graph_segments:ILSX_SPLIT_SEGMENTS=1" "whole_step_graph:ILSX_SPLIT_GRAPH=1"; do
+for form in "phase_kernels:ILSX_BENCH_FORCE_DIST=1" "one_launch_per_stage:ILSX_SPLIT_NO_PHASE=1" "whole_step_graph:ILSX_SPLIT_GRAPH=1"; do
   label=${form%%:*}; kv=${form#*:}
   env $kv ILSX_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --no-aux --no-cpu-baseline --no-seeds --steps 5 --warmup 2 2> /dev/null | grep '^{' | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps(dict(form='$label', **(d.get('split_run') or {}))))" >> $OUT/split_run_1rank.jsonl 2>&1
 done
