@@ -96,6 +96,11 @@ class LunarModel(C.Structure):  # ilsx_lunar_model
                 ("sleep_lin_tol", C.c_double), ("sleep_ang_tol", C.c_double), ("sleep_time", C.c_double)]
 
 
+class GoalModel(C.Structure):  # ilsx_goal_model
+    _fields_ = [("tol", C.c_double), ("step_scale", C.c_double), ("p_range", C.c_double), ("g_range", C.c_double),
+                ("reward_kind", C.c_int32), ("pad", C.c_int32)]
+
+
 class SpatialModel(C.Structure):  # ilsx_spatial_model
     _fields_ = [("task", C.c_int32), ("n_link", C.c_int32), ("n_act", C.c_int32), ("n_contact", C.c_int32),
                 ("n_body", C.c_int32), ("frame_skip", C.c_int32), ("pgs_iters", C.c_int32), ("max_rows", C.c_int32),
@@ -244,6 +249,8 @@ PROTOTYPES = {
     "ilsx_vecenv_set_exploration": (C.c_int, [vp, C.POINTER(ExploreCfg)]),
     "ilsx_vecenv_set_exploration_t": (C.c_int, [vp, C.c_int64]),
     "ilsx_vecenv_explore": (C.c_int, [vp, vp, vp, C.c_int64]),
+    "ilsx_vecenv_set_exploration_epsilon": (C.c_int, [vp, C.c_double]),
+    "ilsx_vecenv_explore_u": (C.c_int, [vp, vp, vp, vp, C.c_int64]),
     "ilsx_sacv_create": (C.c_int, [vp, C.POINTER(SacvCfg), vp, vp, vp, vp, C.POINTER(vp)]),
     "ilsx_sacv_destroy": (C.c_int, [vp]),
     "ilsx_sacv_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(SacvStats)]),
@@ -276,6 +283,7 @@ PROTOTYPES = {
     "ilsx_disc_create": (C.c_int, [vp, C.POINTER(DiscCfg), C.POINTER(vp)]),
     "ilsx_advirl_set_policy_batch_from_expert": (C.c_int, [vp, C.c_int]),
     "ilsx_her_gather": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]),
+    "ilsx_her_sample": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ilsx_debug_rng_stream": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "ilsx_debug_philox": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, vp, vp]),
     "ilsx_debug_ctx_allocs": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
@@ -405,6 +413,8 @@ PROTOTYPES = {
     "ilsx_vecenv_create_cartchain": (C.c_int, [vp, C.POINTER(CartChainModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
     "ilsx_vecenv_create_swimmer": (C.c_int, [vp, C.POINTER(SwimmerModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
     "ilsx_vecenv_create_lunar": (C.c_int, [vp, C.POINTER(LunarModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "ilsx_vecenv_create_goal": (C.c_int, [vp, C.POINTER(GoalModel), C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "ilsx_vecenv_goal_dims": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ilsx_vecenv_action_space": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "ilsx_dsac_create": (C.c_int, [vp, C.POINTER(DsacCfg), vp, vp, vp, C.POINTER(vp)]),
     "ilsx_dsac_destroy": (C.c_int, [vp]),

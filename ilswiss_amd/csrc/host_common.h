@@ -128,6 +128,8 @@ int launch_categorical_act(ilsx_ctx* ctx, const float* z, int rows, int n, int d
 // the epsilon-greedy argmax over raw head outputs z[rows][n] (dqn.h k_egreedy_act; ilsx_ac.hip)
 int launch_egreedy_act(ilsx_ctx* ctx, const float* z, int rows, int n, int deterministic, float epsilon, unsigned long long step, float* act);
 
+// ilsx_policy_act on rows `stride` floats apart (the network reads the first in_dim columns of each row; ilsx_core.hip)
+int policy_act_strided(ilsx_net* pi, const float* obs, int stride, int nrows, int deterministic, const float* eps, float* act, float* logp);
 int net_adopt(ilsx_net* n, float* arena);   // an agent takes the network into its parameter arena (ilsx_core.hip)
 void net_give_back(ilsx_net* n);            // the agent's destroy: private storage back; no-op on a network that owns its storage
 
@@ -202,6 +204,11 @@ struct ilsx_replay {
   int64_t top = 0, size = 0, cur_start = 0;
   std::deque<std::pair<int64_t, int64_t>> trajs;  // insertion-ordered (start,end)
   std::vector<uint8_t> start_flag;                // slot is a key of `trajs`
+  // device mirror of `trajs` as (start, length) pairs, read by the kernel that draws hindsight samples (ilsx_her_sample).  The ring owns it;
+  // every push, pop or edit of `trajs` sets trajs_dirty, and the next sampler call uploads the table again (replay_flush_trajs)
+  long long* dtrajs = nullptr;   // [dtrajs_cap][2]
+  int64_t dtrajs_cap = 0, dtrajs_n = 0;
+  bool trajs_dirty = true;
 };
 // bring the device copy of {size, top} up to date (enqueued on the ring's stream) before a kernel that draws from the ring reads it
 int replay_flush_state(ilsx_replay* rb);

@@ -981,8 +981,17 @@ extern "C" int ilsx_mlp_forward(ilsx_net* n, const float* x, int rows, float* y)
 
 extern "C" int ilsx_policy_act(ilsx_net* pi, const float* obs, int nrows, int deterministic, const float* eps,
                                float* act, float* logp) {
+  if (!pi) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: bad argument");
+  return policy_act_strided(pi, obs, pi->lay.cfg.in_dim, nrows, deterministic, eps, act, logp);
+}
+// ilsx_policy_act on rows that are `stride` floats apart, the network reading the first in_dim columns of each (FwdTask separates the
+// width d0 from the row stride s0, and every forward instance indexes its input as x0[row * s0 + k]): a goal env's policy reads the
+// observation | desired_goal prefix of the env's wider rows in place.
+int policy_act_strided(ilsx_net* pi, const float* obs, int stride, int nrows, int deterministic, const float* eps, float* act, float* logp) {
   if (!pi || !obs || !act || nrows < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: bad argument");
+  if (stride < pi->lay.cfg.in_dim) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: row stride %d < in_dim %d", stride, pi->lay.cfg.in_dim);
   if (pi->discrete()) {   // DiscretePolicy / epsilon-greedy argmax: raw head outputs through the trunk, then the head's own launch
+    if (stride != pi->lay.cfg.in_dim) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_policy_act: a discrete policy reads dense rows");
     if (eps) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: a %s policy takes no explicit noise", pi->categorical ? "categorical" : "epsilon-greedy");
     if (pi->egreedy && logp) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: an epsilon-greedy policy has no log-probability");
     HIPCHK(hipSetDevice(pi->ctx->device));
@@ -1005,7 +1014,7 @@ extern "C" int ilsx_policy_act(ilsx_net* pi, const float* obs, int nrows, int de
   memset(&A, 0, sizeof A);
   FwdTask& t = A.t[0];
   t.net = net_view(pi->lay, pi->base);
-  t.x0 = obs; t.d0 = pi->lay.cfg.in_dim; t.s0 = pi->lay.cfg.in_dim;
+  t.x0 = obs; t.d0 = pi->lay.cfg.in_dim; t.s0 = stride;
   t.head = deterministic ? HEAD_TANH_DET : HEAD_TANH_SAMPLE;
   if (pi->noise_policy) {
     if (logp) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_policy_act: a noise policy has no log-probability");

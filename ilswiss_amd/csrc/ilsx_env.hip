@@ -73,11 +73,15 @@ struct ilsx_vecenv {
   struct CartChainDev* cc = nullptr; // engine 2, InvertedPendulum / InvertedDoublePendulum: the constants k_cartchain_step takes by value
   struct SwimmerDev* sw = nullptr;   // engine 2, classic == ILSX_SWIMMER_TASK: the constants k_swimmer_step takes by value (swimmer_env.h)
   struct LunarDev* ln = nullptr;     // engine 2, classic == ILSX_LUNAR_TASK: the constants k_lunar_step takes by value (lunar_env.h)
+  struct GoalDev* gl = nullptr;      // engine 2, classic == ILSX_GOAL_TASK: the constants k_goal_step takes by value (goal_env.h)
+  int goal_dobs = 0, goal_dg = 0;    // a goal env (> 0): the row is observation (goal_dobs) | desired_goal (goal_dg) | achieved_goal (goal_dg) and a
+                                     // policy reads its first goal_dobs + goal_dg columns (env_policy_act)
   bool step_draws = false;           // the task draws random numbers on every step: ilsx_vecenv_step gives each step stream coordinates of its own
   Spatial3Dev* hm3 = nullptr; Spatial3Dev* dm3 = nullptr;
   // exploration strategy of a deterministic policy (ilsx_vecenv_set_exploration): one process per env, float64
   ilsx_explore_cfg explore = {0, 0, 0.0, 0.0, 0.0, 0.0, 1.0, -1.0, 1.0};
   double *ou_state = nullptr, *ou_sigma = nullptr;   // [n_env][a]: the OU state, and the sigma its next evolve uses (the previous call's)
+  double explore_eps = 0.0;               // Gaussian kind: probability of a uniform action instead (ilsx_vecenv_set_exploration_epsilon)
   long long explore_t = 0;                // the t of the rollout's next steps (PolicyWrappedWithExplorationStrategy.set_num_steps_total)
   unsigned long long explore_calls = 0;   // Philox counter of k_explore (one draw per call)
   const float* policy_obs() const { return norm_obs ? obs_n : obs_cur; }
@@ -200,6 +204,7 @@ __device__ __forceinline__ void env_reset_state(const PlanarModelDev& m, uint64_
 #include "classic_env.h"
 #include "swimmer_env.h"
 #include "lunar_env.h"
+#include "goal_env.h"
 #ifdef ILSX_EG_PROFILE
 extern "C" int ilsx_debug_eg_prof(unsigned long long* out16, int reset) {   // measurement build only
   if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_eg_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
@@ -243,17 +248,30 @@ __global__ void k_random_actions(float* act, int n, uint64_t seed, uint32_t stre
 //   Gaussian: act = clip(act + N(0,1) * sigma(t), low, high)
 //   OU      : x = state (mu at the first step of an episode: OUStrategy.reset) ; state = x + (theta * (mu - x) + sigma_prev * N(0,1)) ;
 //             sigma_prev = sigma(t) — annealed AFTER the evolve, so a call uses the sigma of the call before it ; act = clip(act + state)
+//   Gaussian with epsilon > 0 (MlpGaussianAndEpsilonPolicy, policies.py:537-552): an env whose uniform u0 < epsilon takes a uniform action
+//             act_j = (float)(low + (high - low) * u_{1+j}) instead; u = the caller's [n_env][1 + a] or counters 0..a of a Philox stream of
+//             its own.  One draw of u0 per ENV (the reference draws once per call for its whole batch: the same thing at one env).
 struct ExploreArgs {
   int kind, n_env, a;
   double mu, theta, max_sigma, min_sigma, decay_period, low, high;
   long long t;
+  double epsilon;
 };
 __global__ __launch_bounds__(256) void k_explore(const ExploreArgs X, float* __restrict__ act, const double* __restrict__ eps,
-                                                 double* __restrict__ state, double* __restrict__ sigma, const int* __restrict__ ep_len,
+                                                 const double* __restrict__ u, double* __restrict__ state, double* __restrict__ sigma, const int* __restrict__ ep_len,
                                                  uint64_t seed, uint32_t stream, unsigned long long step) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= X.n_env * X.a) return;
   const int env = i / X.a, j = i - env * X.a;
+  if (X.kind == 1 && X.epsilon > 0.0) {
+    const uint32_t ustream = stream ^ 0x00554E49u;   // 'UNI': apart from the stream of the normals
+    const double u0 = u ? u[(size_t)env * (1 + X.a)] : env_uniform(seed, ustream, step, (uint32_t)env, 0);
+    if (u0 < X.epsilon) {
+      const double uj = u ? u[(size_t)env * (1 + X.a) + 1 + j] : env_uniform(seed, ustream, step, (uint32_t)env, (uint32_t)(1 + j));
+      act[i] = (float)(X.low + (X.high - X.low) * uj);
+      return;
+    }
+  }
   double e;
   if (eps) {
     e = eps[i];
@@ -376,6 +394,7 @@ ENV_STEP_FN(step_cartchain1, k_cartchain_step<1>, LANES(A.n_ids, 256), 256, 0, *
 ENV_STEP_FN(step_cartchain2, k_cartchain_step<2>, LANES(A.n_ids, 256), 256, 0, *e->cc)
 ENV_STEP_FN(step_swimmer, k_swimmer_step<3>, LANES(A.n_ids, 256), 256, 0, *e->sw)
 ENV_STEP_FN(step_lunar, k_lunar_step, LANES(A.n_ids, 256), 256, 0, *e->ln)
+ENV_STEP_FN(step_goal, k_goal_step, LANES(A.n_ids, 256), 256, 0, *e->gl)
 ENV_STEP_FN(step_mountaincar_cont, k_mountaincar_cont_step, LANES(A.n_ids, 256), 256, 0)
 ENV_STEP_FN(step_mountaincar, k_mountaincar_step, LANES(A.n_ids, 256), 256, 0)
 ENV_STEP_FN(step_acrobot, k_acrobot_step, LANES(A.n_ids, 256), 256, 0)
@@ -385,6 +404,7 @@ ENV_RESET_FN(reset_cartchain1, k_cartchain_reset<1>, LANES(n_ids, 256), 256, 0, 
 ENV_RESET_FN(reset_cartchain2, k_cartchain_reset<2>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_swimmer, k_swimmer_reset<3>, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS, *e->sw)
 ENV_RESET_FN(reset_lunar, k_lunar_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS, *e->ln)
+ENV_RESET_FN(reset_goal, k_goal_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS, *e->gl)
 ENV_RESET_FN(reset_mountaincar_cont, k_mountaincar_cont_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_mountaincar, k_mountaincar_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
 ENV_RESET_FN(reset_acrobot, k_acrobot_reset, LANES(n_ids, 256), 256, 0, LANE_RESET_ARGS)
@@ -403,6 +423,7 @@ static const struct ClassicTask {
     {ILSX_CLASSIC_ACROBOT, 2, 6, 1, 3, step_acrobot, reset_acrobot},
     {ILSX_SWIMMER_TASK, 5, 8, 2, 0, step_swimmer, reset_swimmer},
     {ILSX_LUNAR_TASK, 3, 8, 2, 0, step_lunar, reset_lunar, 14, 4},   // qpos carries the terrain, qvel the sleep clock
+    {ILSX_GOAL_TASK, 2, 8, 2, 0, step_goal, reset_goal, 4, 2},       // qpos carries the goal; the row is observation | desired_goal | achieved_goal
 };
 #undef ENV_STEP_FN
 #undef ENV_RESET_FN
@@ -553,9 +574,9 @@ extern "C" int ilsx_vecenv_create_spatial(ilsx_ctx* ctx, const ilsx_spatial_mode
 }
 // Classic control (classic_env.h): CartPole, Pendulum and the cart-and-poles tasks, one lane per env, the same handle and protocol entry
 // points as the other engines.  cc != null: InvertedPendulum / InvertedDoublePendulum with these constants; sw != null: Swimmer with these;
-// ln != null: the lander with these.
+// ln != null: the lander with these; gl != null: the goal env with these.
 static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n_env, uint64_t seed, ilsx_vecenv** out,
-                          const SwimmerDev* sw = nullptr, const LunarDev* ln = nullptr) {
+                          const SwimmerDev* sw = nullptr, const LunarDev* ln = nullptr, const GoalDev* gl = nullptr) {
   HIPCHK(hipSetDevice(ctx->device));
   ilsx_vecenv* e = env_new(ctx, 2, n_env, seed);
   EnvGuard guard{e};
@@ -569,6 +590,7 @@ static int create_classic(ilsx_ctx* ctx, int kind, const CartChainDev* cc, int n
   if (cc) e->cc = new CartChainDev(*cc);
   if (sw) e->sw = new SwimmerDev(*sw);
   if (ln) { e->ln = new LunarDev(*ln); e->step_draws = true; }
+  if (gl) { e->gl = new GoalDev(*gl); e->goal_dobs = PointReachTask::D_OBS; e->goal_dg = PointReachTask::D_GOAL; }
   return env_create_finish(guard, out);
 }
 
@@ -747,6 +769,27 @@ extern "C" int ilsx_vecenv_create_lunar(ilsx_ctx* ctx, const ilsx_lunar_model* p
   return create_classic(ctx, ILSX_LUNAR_TASK, nullptr, n_env, seed, out, nullptr, &d);
 }
 
+// The goal env (goal_env.h): the caller's model is the one source of the constants, refused before anything is allocated unless every one
+// is finite and positive.
+extern "C" int ilsx_vecenv_create_goal(ilsx_ctx* ctx, const ilsx_goal_model* pm, int n_env, uint64_t seed, ilsx_vecenv** out) {
+  if (!ctx || !pm || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_goal: bad argument");
+  for (double x : {pm->tol, pm->step_scale, pm->p_range, pm->g_range})
+    if (!std::isfinite(x) || !(x > 0.0)) ILSX_FAIL(ILSX_ERR_ARG, "goal env: tol, step_scale, p_range and g_range must be finite and positive");
+  if (pm->p_range > 1.0 || pm->g_range > 1.0) ILSX_FAIL(ILSX_ERR_ARG, "goal env: p_range and g_range lie inside the arena [-1, 1]");
+  if (pm->reward_kind < 0 || pm->reward_kind > 1) ILSX_FAIL(ILSX_ERR_ARG, "goal env: reward_kind must be 0 (sparse) or 1 (dense)");
+  GoalDev d;
+  memset(&d, 0, sizeof d);
+  d.tol = pm->tol; d.p_range = pm->p_range; d.g_range = pm->g_range; d.step_scale = (float)pm->step_scale; d.reward_kind = pm->reward_kind;
+  return create_classic(ctx, ILSX_GOAL_TASK, nullptr, n_env, seed, out, nullptr, nullptr, &d);
+}
+extern "C" int ilsx_vecenv_goal_dims(const ilsx_vecenv* e, int* d_obs, int* d_goal) {
+  if (!e) ILSX_FAIL(ILSX_ERR_ARG, "env is NULL");
+  if (e->goal_dobs <= 0) ILSX_FAIL(ILSX_ERR_STATE, "ilsx_vecenv_goal_dims: not a goal env");
+  if (d_obs) *d_obs = e->goal_dobs;
+  if (d_goal) *d_goal = e->goal_dg;
+  return ILSX_OK;
+}
+
 extern "C" int ilsx_vecenv_create_classic(ilsx_ctx* ctx, int kind, int n_env, uint64_t seed, ilsx_vecenv** out) {
   if (!ctx || !out || n_env < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_create_classic: bad argument");
   if (kind == ILSX_CLASSIC_INVERTED_PENDULUM || kind == ILSX_CLASSIC_INVERTED_DOUBLE_PENDULUM) {
@@ -787,6 +830,7 @@ extern "C" int ilsx_vecenv_destroy(ilsx_vecenv* e) {
   delete e->cc;
   delete e->sw;
   delete e->ln;
+  delete e->gl;
   delete e;
   return ILSX_OK;
 }
@@ -932,6 +976,7 @@ extern "C" int ilsx_is_terminal(ilsx_ctx* ctx, int kind, const float* next_obs, 
 // The envs are reset so that the observations they currently show follow the new map.
 extern "C" int ilsx_vecenv_set_obs_affine(ilsx_vecenv* e, const double* shift_host, const double* scale_host) {
   if (!e || !shift_host || !scale_host) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_set_obs_affine: NULL argument");
+  if (e->goal_dobs > 0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_set_obs_affine: not available for goal envs (dictionary observations)");
   if (e->engine == 2) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_set_obs_affine: not available for classic-control envs");
   HIPCHK(hipSetDevice(e->ctx->device));
   for (int i = 0; i < e->o; ++i) {
@@ -950,6 +995,8 @@ extern "C" int ilsx_vecenv_set_obs_affine(ilsx_vecenv* e, const double* shift_ho
 extern "C" int ilsx_vecenv_obs_norm(ilsx_vecenv* e, int norm_obs, int update_obs_rms) {
   if (!e) ILSX_FAIL(ILSX_ERR_ARG, "env is NULL");
   if (e->o > ENV_MAX_OBS) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "obs_dim %d > %d", e->o, ENV_MAX_OBS);
+  if (norm_obs && e->goal_dobs > 0)
+    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_vecenv_obs_norm: norm_obs=1 is not available for goal envs (the reference's RunningMeanStd takes flat observations)");
   HIPCHK(hipSetDevice(e->ctx->device));
   e->norm_obs = norm_obs != 0; e->update_rms = update_obs_rms != 0;
   // the observations the envs currently show become the first batch, like the reset() that follows construction
@@ -1026,14 +1073,14 @@ static int rollout_paths_finish(ilsx_vecenv* e, bool synced = false, const int* 
   return replay_insert_paths(rb, e->stage, e->stage_len, envs.data(), lens.data(), term.data(), (int)envs.size());
 }
 // ---- exploration strategies (k_explore)
-static int env_explore(ilsx_vecenv* e, float* act, const double* eps, long long t) {
+static int env_explore(ilsx_vecenv* e, float* act, const double* eps, long long t, const double* u = nullptr) {
   const ilsx_explore_cfg& c = e->explore;
   ExploreArgs X;
   X.kind = c.kind; X.n_env = e->n_env; X.a = e->a;
   X.mu = c.mu; X.theta = c.theta; X.max_sigma = c.max_sigma; X.min_sigma = c.min_sigma; X.decay_period = c.decay_period;
-  X.low = c.low; X.high = c.high; X.t = t;
+  X.low = c.low; X.high = c.high; X.t = t; X.epsilon = c.kind == 1 ? e->explore_eps : 0.0;
   const int tot = e->n_env * e->a;
-  hipLaunchKernelGGL(k_explore, dim3((tot + 255) / 256), dim3(256), 0, e->ctx->stream, X, act, eps, e->ou_state, e->ou_sigma, (const int*)e->ep_len,
+  hipLaunchKernelGGL(k_explore, dim3((tot + 255) / 256), dim3(256), 0, e->ctx->stream, X, act, eps, u, e->ou_state, e->ou_sigma, (const int*)e->ep_len,
                      e->seed, e->rng_stream ^ 0x45585000u, ++e->explore_calls);   // 'EXP': a Philox stream of its own
   HIPCHK(hipGetLastError());
   return ILSX_OK;
@@ -1045,6 +1092,7 @@ extern "C" int ilsx_vecenv_set_exploration(ilsx_vecenv* e, const ilsx_explore_cf
   if (cfg->kind && (!(cfg->decay_period > 0.0) || !(cfg->low <= cfg->high))) ILSX_FAIL(ILSX_ERR_ARG, "exploration: decay_period must be > 0 and low <= high");
   HIPCHK(hipSetDevice(e->ctx->device));
   e->explore = *cfg;
+  e->explore_eps = 0.0;   // a strategy starts without the epsilon branch (ilsx_vecenv_set_exploration_epsilon)
   if (!cfg->kind) return ILSX_OK;
   const size_t n = (size_t)e->n_env * e->a;
   if (!e->ou_state) { ILSX_TRY(e->own.alloc_bytes(&e->ou_state, n * 8)); ILSX_TRY(e->own.alloc_bytes(&e->ou_sigma, n * 8)); }
@@ -1061,6 +1109,19 @@ extern "C" int ilsx_vecenv_set_exploration_t(ilsx_vecenv* e, int64_t t) {
   e->explore_t = (long long)t;
   return ILSX_OK;
 }
+extern "C" int ilsx_vecenv_set_exploration_epsilon(ilsx_vecenv* e, double epsilon) {
+  if (!e) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_set_exploration_epsilon: NULL env");
+  if (!(epsilon >= 0.0 && epsilon <= 1.0)) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_set_exploration_epsilon: epsilon %g is not in [0, 1]", epsilon);
+  if (e->explore.kind != 1) ILSX_FAIL(ILSX_ERR_STATE, "ilsx_vecenv_set_exploration_epsilon: the epsilon branch belongs to the Gaussian strategy (kind 1)");
+  e->explore_eps = epsilon;
+  return ILSX_OK;
+}
+extern "C" int ilsx_vecenv_explore_u(ilsx_vecenv* e, float* act, const double* eps, const double* u, int64_t t) {
+  if (!e || !act) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_explore_u: NULL argument");
+  if (!e->explore.kind) ILSX_FAIL(ILSX_ERR_STATE, "ilsx_vecenv_explore_u: no exploration strategy set (ilsx_vecenv_set_exploration)");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  return env_explore(e, act, eps, (long long)t, u);
+}
 extern "C" int ilsx_vecenv_explore(ilsx_vecenv* e, float* act, const double* eps, int64_t t) {
   if (!e || !act) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_vecenv_explore: NULL argument");
   if (!e->explore.kind) ILSX_FAIL(ILSX_ERR_STATE, "ilsx_vecenv_explore: no exploration strategy set (ilsx_vecenv_set_exploration)");
@@ -1076,6 +1137,17 @@ static int env_policy_kind_check(const ilsx_vecenv* e, const ilsx_net* pi, const
               pi->categorical ? "categorical" : pi->egreedy ? "epsilon-greedy" : "continuous",
               e->discrete_n > 0 ? "Discrete" : "Box");
   return ILSX_OK;
+}
+// The env's policy acts on what the env shows.  A goal env's rows are observation | desired_goal | achieved_goal and its networks take the
+// first two segments: the forward reads that prefix of obs_cur in place (row stride o, width in_dim); any other width is refused.
+static int env_policy_act(ilsx_vecenv* e, ilsx_net* pi, int deterministic, float* act) {
+  if (e->goal_dobs > 0) {
+    if (pi->lay.cfg.in_dim != e->goal_dobs + e->goal_dg)
+      ILSX_FAIL(ILSX_ERR_ARG, "a goal env's policy reads observation | desired_goal = %d columns, this one takes %d", e->goal_dobs + e->goal_dg,
+                pi->lay.cfg.in_dim);
+    return policy_act_strided(pi, e->obs_cur, e->o, e->n_env, deterministic, nullptr, act, nullptr);
+  }
+  return ilsx_policy_act(pi, e->policy_obs(), e->n_env, deterministic, nullptr, act, nullptr);
 }
 static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, int label_deterministic, ilsx_replay* rb,
                              int max_path_length, int random_actions, int deterministic, int no_terminal, bool defer_paths = false) {
@@ -1104,14 +1176,14 @@ static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, i
                        e->rng_stream ^ 0x5A5A5A5Au, step, e->a);
     HIPCHK(hipGetLastError());
   } else {
-    ILSX_TRY(ilsx_policy_act(pi, e->policy_obs(), e->n_env, deterministic, nullptr, e->act, nullptr));
+    ILSX_TRY(env_policy_act(e, pi, deterministic, e->act));
     if (e->explore.kind && !deterministic) ILSX_TRY(env_explore(e, e->act, nullptr, e->explore_t));
   }
   EnvStepArgs A;
   ILSX_TRY(rollout_env_args(e, rb, max_path_length, no_terminal, step, &A));
   if (label_pi) {   // DAgger._handle_step (dagger.py:45-71): the stored action is the expert's for the observation acted on
     if (!e->act_label) ILSX_TRY(e->own.alloc_bytes(&e->act_label, (size_t)e->n_env * e->a * 4));
-    ILSX_TRY(ilsx_policy_act(label_pi, e->policy_obs(), e->n_env, label_deterministic, nullptr, e->act_label, nullptr));
+    ILSX_TRY(env_policy_act(e, label_pi, label_deterministic, e->act_label));
     A.rec_act = e->act_label;
   }
   const bool paths = rb && e->path_mode;
@@ -1273,6 +1345,8 @@ extern "C" int ilsx_rollout_steps_lockstep(ilsx_vecenv* const* envs, ilsx_net* c
   if (!envs || !pis || !rbs || !min_steps_before_training || n_runs < 1 || n_steps < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_rollout_steps_lockstep: bad argument");
   for (int k = 0; k < n_runs; ++k)
     if (!envs[k] || !pis[k] || !rbs[k]) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_rollout_steps_lockstep: run %d has a NULL env / policy / replay", k);
+  for (int k = 0; k < n_runs; ++k)
+    if (envs[k]->goal_dobs > 0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_rollout_steps_lockstep: run %d is a goal env (grouped seeds are not available for goal envs)", k);
   if (rollout_runs_groupable(envs, pis, n_runs)) {
     HIPCHK(hipSetDevice(envs[0]->ctx->device));
     // everything the runs' own streams still hold (an evaluation, a train call, a ring insert) happens before the grouped launches, and they
@@ -1328,6 +1402,7 @@ extern "C" int ilsx_ppo_rollout(ilsx_ppo* ppo, ilsx_vecenv* e, int T, int max_pa
                                 uint8_t* ends, float* last_values) {
   if (!ppo || !e || !obs || !act || !rew || !ends || T < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_ppo_rollout: bad argument");
   if (e->discrete_n > 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_ppo_rollout: PPO's Gaussian policy on an env with a Discrete action space");
+  if (e->goal_dobs > 0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_ppo_rollout: not available for goal envs (dictionary observations)");
   ilsx_ctx* ctx = e->ctx;
   HIPCHK(hipSetDevice(ctx->device));
   const int n = e->n_env, w = e->o + e->a;
@@ -1418,6 +1493,7 @@ extern "C" int ilsx_eval_rollout(ilsx_vecenv* e, ilsx_net* pi, ilsx_ppo* ppo, in
   if (!e || (!pi && !ppo) || max_path_length < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_eval_rollout: bad argument");
   ILSX_TRY(env_policy_kind_check(e, pi, "ilsx_eval_rollout"));
   if (!pi && e->discrete_n > 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_eval_rollout: PPO's Gaussian policy on an env with a Discrete action space");
+  if (!pi && e->goal_dobs > 0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_eval_rollout: PPO's policy on a goal env (dictionary observations)");
   ilsx_ctx* ctx = e->ctx;
   HIPCHK(hipSetDevice(ctx->device));
   const int n = e->n_env;
@@ -1438,7 +1514,7 @@ extern "C" int ilsx_eval_rollout(ilsx_vecenv* e, ilsx_net* pi, ilsx_ppo* ppo, in
   hipLaunchKernelGGL(k_eval_begin, dim3((n + 255) / 256), dim3(256), 0, st, e->ev_frozen, e->ev_ret, e->ev_len, n, e->ev_alive);
   for (int t = 0; t < max_path_length; ++t) {
     const unsigned long long step = ++e->step_ctr;
-    if (pi) ILSX_TRY(ilsx_policy_act(pi, e->policy_obs(), n, deterministic, nullptr, e->act, nullptr));
+    if (pi) ILSX_TRY(env_policy_act(e, pi, deterministic, e->act));
     else ILSX_TRY(ilsx_ppo_policy_act(ppo, e->policy_obs(), n, deterministic, nullptr, e->act, nullptr));
     EnvStepArgs A;
     memset(&A, 0, sizeof A);
@@ -1505,6 +1581,8 @@ extern "C" int ilsx_eval_rollouts_lockstep(ilsx_vecenv* const* envs, ilsx_net* c
   if (!envs || !pis || !stats_host || n_runs < 1 || max_path_length < 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_eval_rollouts_lockstep: bad argument");
   for (int k = 0; k < n_runs; ++k)
     if (!envs[k] || !pis[k]) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_eval_rollouts_lockstep: run %d has a NULL env / policy", k);
+  for (int k = 0; k < n_runs; ++k)
+    if (envs[k]->goal_dobs > 0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_eval_rollouts_lockstep: run %d is a goal env (grouped seeds are not available for goal envs)", k);
   if (n_runs > ENVG_MAX_RUNS || !rollout_runs_groupable(envs, pis, n_runs)) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_eval_rollouts_lockstep: the runs cannot share launches");
   ilsx_vecenv* e0 = envs[0];
   ilsx_ctx* gctx = e0->ctx;

@@ -60,19 +60,18 @@ __global__ __launch_bounds__(256) void k_replay_sample(const float* __restrict__
 // record idx_rel[r] (the `future` / `final` index the host drew in the reference's RandomState order); when relabelling is on, EVERY
 // row's reward is recomputed from (next achieved goal, desired goal) (:139-147) with the goal env's sparse / dense rule.  Outputs are
 // what the goal-conditioned trainers consume (her/td3.py:95-99): obs_cat = observation | desired_goal, nobs_cat likewise.
-// One thread per (row, output column of obs_cat).
-__global__ __launch_bounds__(256) void k_her_gather(const float* __restrict__ data, int rec, const long long* __restrict__ idx,
-                                                    const long long* __restrict__ idx_rel, int B, int n_relabel, int relabel_on,
-                                                    int d_obs, int dg, int a, int reward_kind, float threshold,
-                                                    float* __restrict__ obs_cat, float* __restrict__ act, float* __restrict__ rew,
-                                                    float* __restrict__ done, float* __restrict__ nobs_cat) {
-  const int W = d_obs + dg, e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= B * W) return;
-  const int r = e / W, c = e - r * W, o = d_obs + 2 * dg;
-  const float* R = data + (size_t)idx[r] * rec;
+// One thread per (row, output column of obs_cat): her_gather_cell is that thread's work, for batch row r and column c, with the row's two
+// record indices at idx[ri] / idx_rel[ri] (k_her_gather: the caller's arrays, ri = r; k_her_sample: the block's own draws in LDS).
+__device__ __forceinline__ void her_gather_cell(const float* __restrict__ data, int rec, const long long* __restrict__ idx,
+                                                const long long* __restrict__ idx_rel, int ri, int r, int c, int n_relabel, int relabel_on,
+                                                int d_obs, int dg, int a, int reward_kind, float threshold, float* __restrict__ obs_cat,
+                                                float* __restrict__ act, float* __restrict__ rew, float* __restrict__ done,
+                                                float* __restrict__ nobs_cat) {
+  const int W = d_obs + dg, o = d_obs + 2 * dg;
+  const float* R = data + (size_t)idx[ri] * rec;
   const float* nob = R + o + a + 2;                    // next observation segment of this record
   const bool rl = relabel_on && r < n_relabel;
-  const float* gsrc = rl ? data + (size_t)idx_rel[r] * rec + o + a + 2 + d_obs + dg : nullptr;   // next achieved goal of the relabel record
+  const float* gsrc = rl ? data + (size_t)idx_rel[ri] * rec + o + a + 2 + d_obs + dg : nullptr;   // next achieved goal of the relabel record
   if (c < d_obs) {
     obs_cat[(size_t)r * W + c] = R[c];
     nobs_cat[(size_t)r * W + c] = nob[c];
@@ -96,6 +95,70 @@ __global__ __launch_bounds__(256) void k_her_gather(const float* __restrict__ da
       rv = reward_kind == 0 ? (dist > threshold ? -1.0f : 0.0f) : -dist;
     }
     rew[r] = rv;
+  }
+}
+__global__ __launch_bounds__(256) void k_her_gather(const float* __restrict__ data, int rec, const long long* __restrict__ idx,
+                                                    const long long* __restrict__ idx_rel, int B, int n_relabel, int relabel_on,
+                                                    int d_obs, int dg, int a, int reward_kind, float threshold,
+                                                    float* __restrict__ obs_cat, float* __restrict__ act, float* __restrict__ rew,
+                                                    float* __restrict__ done, float* __restrict__ nobs_cat) {
+  const int W = d_obs + dg, e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= B * W) return;
+  const int r = e / W, c = e - r * W;
+  her_gather_cell(data, rec, idx, idx_rel, r, r, c, n_relabel, relabel_on, d_obs, dg, a, reward_kind, threshold, obs_cat, act, rew, done,
+                  nobs_cat);
+}
+
+// Hindsight sampling drawn in the kernel (ilsx_her_sample): draw, gather, relabel, reward and concatenation in ONE launch.  A workgroup owns
+// `rpb` whole batch rows.  Lane l < rows draws row l ONCE — trajectory, step and relabel step from three uniforms — into LDS (and into
+// idx_out / rel_out); after the barrier the workgroup walks its rows' output cells with her_gather_cell, the indices read from LDS.
+//   t = floor(u0 n_traj), k = floor(u1 L_t), idx = (start_t + k) mod cap ; future: kf = k + floor(u2 (L_t - k)), final: kf = L_t - 1, none: kf = k ;
+//   idx_relabel = (start_t + kf) mod cap — always a step of the same trajectory at or after the sampled one, whether or not it wraps the ring.
+// floor(u n) is taken in float64 and clamped to [0, n - 1], so no u (a NaN included) gives an index outside the table or the ring.
+// u != null: the caller's uniforms [B][3]; else Philox keyed by (ring seed, ring stream, step = the ring's sample counter, row).
+__device__ __forceinline__ long long her_pick(double u, long long n) {
+  const double x = floor(u * (double)n);
+  if (!(x >= 0.0)) return 0;
+  if (x >= (double)n) return n - 1;
+  return (long long)x;
+}
+__global__ __launch_bounds__(256) void k_her_sample(const float* __restrict__ data, int rec, long long cap, const long long* __restrict__ trajs,
+                                                    long long n_traj, const double* __restrict__ u, uint64_t seed, uint32_t stream,
+                                                    unsigned long long step, int relabel_type, int rpb, int B, int n_relabel, int d_obs, int dg,
+                                                    int a, int reward_kind, float threshold, float* __restrict__ obs_cat,
+                                                    float* __restrict__ act, float* __restrict__ rew, float* __restrict__ done,
+                                                    float* __restrict__ nobs_cat, long long* __restrict__ idx_out,
+                                                    long long* __restrict__ rel_out) {
+  __shared__ long long s_idx[256], s_rel[256];
+  const int r0 = blockIdx.x * rpb, tid = threadIdx.x;
+  const int nr = B - r0 < rpb ? B - r0 : rpb;   // rpb <= 256
+  if (tid < nr) {
+    const int r = r0 + tid;
+    double u0, u1, u2;
+    if (u) {
+      u0 = u[(size_t)r * 3]; u1 = u[(size_t)r * 3 + 1]; u2 = u[(size_t)r * 3 + 2];
+    } else {
+      uint32_t c[4] = {(uint32_t)r, 0x48455253u /* 'HERS' */, (uint32_t)step, (uint32_t)(step >> 32) ^ (stream * 0x9E3779B9u)};
+      philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32) ^ stream);
+      u0 = (double)c[0] * (1.0 / 4294967296.0); u1 = (double)c[1] * (1.0 / 4294967296.0); u2 = (double)c[2] * (1.0 / 4294967296.0);
+    }
+    const long long t = her_pick(u0, n_traj);
+    const long long start = trajs[2 * t], L = trajs[2 * t + 1];
+    const long long k = her_pick(u1, L);
+    const long long kf = relabel_type == 1 ? k + her_pick(u2, L - k) : relabel_type == 2 ? L - 1 : k;
+    long long i0 = start + k, i1 = start + kf;
+    if (i0 >= cap) i0 -= cap;
+    if (i1 >= cap) i1 -= cap;
+    s_idx[tid] = i0; s_rel[tid] = i1;
+    if (idx_out) idx_out[r] = i0;
+    if (rel_out) rel_out[r] = i1;
+  }
+  __syncthreads();
+  const int W = d_obs + dg;
+  for (int e = tid; e < nr * W; e += 256) {
+    const int lr = e / W, c = e - lr * W;
+    her_gather_cell(data, rec, s_idx, s_rel, lr, r0 + lr, c, n_relabel, relabel_type != 0, d_obs, dg, a, reward_kind, threshold, obs_cat, act,
+                    rew, done, nobs_cat);
   }
 }
 
@@ -200,6 +263,7 @@ extern "C" int ilsx_replay_destroy(ilsx_replay* rb) {
   if (!rb) return ILSX_OK;
   ctx_free(rb->ctx, rb->data);
   ctx_free(rb->ctx, rb->dstate);
+  if (rb->dtrajs) ctx_free(rb->ctx, rb->dtrajs);
   delete rb;
   return ILSX_OK;
 }
@@ -210,11 +274,13 @@ static void host_advance(ilsx_replay* rb) {
     for (auto it = rb->trajs.begin(); it != rb->trajs.end(); ++it)
       if (it->first == rb->top) { rb->trajs.erase(it); break; }
     rb->start_flag[rb->top] = 0;
+    rb->trajs_dirty = true;
   }
   rb->top = (rb->top + 1) % rb->cap;
   if (rb->size < rb->cap) rb->size++;
 }
 static void host_set_endpoint(ilsx_replay* rb, int64_t start, int64_t end) {
+  rb->trajs_dirty = true;
   if (rb->start_flag[start]) {
     for (auto& p : rb->trajs)
       if (p.first == start) { p.second = end; return; }  // dict assignment keeps the original position
@@ -446,6 +512,7 @@ extern "C" int ilsx_replay_clear(ilsx_replay* rb) {
   HIPCHK(hipMemsetAsync(rb->data, 0, (size_t)rb->cap * rb->rec * sizeof(float), rb->ctx->stream));  // :397-442
   rb->top = rb->size = rb->cur_start = 0;
   rb->trajs.clear();
+  rb->trajs_dirty = true;
   std::fill(rb->start_flag.begin(), rb->start_flag.end(), 0);
   return replay_push_state(rb);
 }
@@ -476,6 +543,63 @@ extern "C" int ilsx_her_gather(ilsx_replay* rb, const int64_t* idx, const int64_
   ILSX_LAUNCH(ps, k_her_gather, dim3((total + 255) / 256), dim3(256), 0, rb->ctx->stream, rb->data, rb->rec, (const long long*)idx,
               (const long long*)idx_relabel, B, n_relabel, relabel_on, d_obs, d_goal, rb->a, reward_kind, threshold, obs_cat, act, rew,
               done, nobs_cat);
+  HIPCHK(hipGetLastError());
+  return ILSX_OK;
+}
+
+// Bring the device mirror of the trajectory table up to date: (start, length) per entry of `trajs`, in insertion order, uploaded only when
+// `trajs` changed since the last upload.  length = (end - start) mod cap; an entry of length 0 — a trajectory as long as the ring, which the
+// next insert evicts and whose step draw the reference refuses (randint(0, 0)) — is left out.
+static int replay_flush_trajs(ilsx_replay* rb) {
+  if (!rb->trajs_dirty) return ILSX_OK;
+  ilsx_ctx* ctx = rb->ctx;
+  std::vector<long long> h;
+  h.reserve(rb->trajs.size() * 2);
+  for (auto& p : rb->trajs) {
+    const long long len = (long long)(((p.second - p.first) % rb->cap + rb->cap) % rb->cap);
+    if (p.first < 0 || p.first >= rb->cap || len < 1) continue;
+    h.push_back((long long)p.first);
+    h.push_back(len);
+  }
+  const int64_t n = (int64_t)h.size() / 2;
+  if (n > rb->dtrajs_cap) {
+    if (rb->dtrajs) ILSX_TRY(ctx_free(ctx, rb->dtrajs));
+    rb->dtrajs = nullptr; rb->dtrajs_cap = 0;
+    int64_t want = rb->dtrajs_cap ? rb->dtrajs_cap : 64;
+    while (want < n) want *= 2;
+    if (want > rb->cap) want = rb->cap;   // a ring of cap rows holds at most cap trajectories
+    ILSX_TRY(ctx_alloc(ctx, (size_t)want * 2 * sizeof(long long), (void**)&rb->dtrajs, false));
+    rb->dtrajs_cap = want;
+  }
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(rb->dtrajs, h.data(), (size_t)n * 2 * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // `h` dies with this call
+  }
+  rb->dtrajs_n = n;
+  rb->trajs_dirty = false;
+  return ILSX_OK;
+}
+
+extern "C" int ilsx_her_sample(ilsx_replay* rb, int B, int n_relabel, int relabel_type, int d_obs, int d_goal, int reward_kind,
+                               float threshold, const double* u, float* obs_cat, float* act, float* rew, float* done, float* nobs_cat,
+                               int64_t* idx_out, int64_t* idx_relabel_out) {
+  if (!rb || B < 1 || !obs_cat || !act || !rew || !done || !nobs_cat) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_her_sample: bad argument");
+  if (d_obs < 1 || d_goal < 1 || d_obs + 2 * d_goal != rb->o)
+    ILSX_FAIL(ILSX_ERR_ARG, "ilsx_her_sample: ring observation width %d != d_obs %d + 2 * d_goal %d", rb->o, d_obs, d_goal);
+  if (rb->a > d_obs + d_goal) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_her_sample: act_dim %d > d_obs + d_goal %d", rb->a, d_obs + d_goal);
+  if (relabel_type < 0 || relabel_type > 2) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_her_sample: relabel_type must be 0 (none), 1 (future) or 2 (final)");
+  if (n_relabel < 0 || n_relabel > B) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_her_sample: n_relabel %d outside [0, %d]", n_relabel, B);
+  if (reward_kind < 0 || reward_kind > 1) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_her_sample: reward_kind must be 0 (sparse) or 1 (dense)");
+  HIPCHK(hipSetDevice(rb->ctx->device));
+  ILSX_TRY(replay_flush_trajs(rb));
+  if (rb->dtrajs_n < 1) ILSX_FAIL(ILSX_ERR_STATE, "ilsx_her_sample: no registered trajectory");
+  const int W = d_obs + d_goal;
+  const int rpb = W >= 256 ? 1 : 256 / W;   // whole rows per workgroup (W >= 2, so at most 128)
+  const unsigned long long step = u ? 0ull : ++rb->sample_ctr;
+  ProfScope ps(rb->ctx, ILSX_K_REPLAY_SAMPLE);
+  ILSX_LAUNCH(ps, k_her_sample, dim3((B + rpb - 1) / rpb), dim3(256), 0, rb->ctx->stream, rb->data, rb->rec, (long long)rb->cap,
+              (const long long*)rb->dtrajs, (long long)rb->dtrajs_n, u, rb->seed, rb->rng_stream, step, relabel_type, rpb, B, n_relabel, d_obs,
+              d_goal, rb->a, reward_kind, threshold, obs_cat, act, rew, done, nobs_cat, (long long*)idx_out, (long long*)idx_relabel_out);
   HIPCHK(hipGetLastError());
   return ILSX_OK;
 }

@@ -14,6 +14,7 @@ from ..device import as_dev, get_context, host_ptr
 from .models import MODELS
 from .models3d import MODELS3D
 from .models_cartchain import MODELS_CARTCHAIN
+from .models_goal import MODELS_GOAL
 from .models_lunar import MODELS_LUNAR
 from .models_swimmer import MODELS_SWIMMER
 
@@ -63,6 +64,10 @@ LUNAR = {"lunarlandercont": 17}
 # `mountaincar` and `acrobot` are MountainCar-v0's and Acrobot-v1's classes, both Discrete(3).  No model description, as for CLASSIC; a
 # dict of their own beside it.
 GYM_CLASSIC = {"mountaincarcont": 4, "mountaincar": 5, "acrobot": 6}
+# the goal env of the same frame (k_goal_step of csrc/goal_env.h; ILSX_GOAL_TASK): ilswiss_amd/her.py's PointReachEnv as a device stepper,
+# a stand-in for the reference's MuJoCo Fetch tasks.  Dictionary observations: a row is observation | desired_goal | achieved_goal.  The
+# constants come from the model description (models_goal.py), built from `env_kwargs` {tol, reward_type}.
+GOAL = {"point-reach": 18}
 
 
 def model_struct(m):
@@ -165,6 +170,28 @@ def lunar_struct(m):
     return s
 
 
+def goal_struct(m):
+    """models_goal dict -> ilsx_goal_model (include/ilsx.h)."""
+    return _lib.GoalModel(float(m["tol"]), float(m["step_scale"]), float(m["p_range"]), float(m["g_range"]), int(m["reward_kind"]), 0)
+
+
+def goal_model_checked(env_name, env_kwargs=None, model=None, norm_obs=False, obs_shift=None):
+    """The model description of a goal env, with everything that can be refused before the library is entered: observation
+    normalisation and ScaledEnv / MinmaxEnv (dictionary observations have neither here), unknown env_kwargs, a reward_type the stepper
+    does not know, a tolerance that is not a positive finite number."""
+    if norm_obs:
+        raise NotImplementedError(f"{env_name}: norm_obs is not available for goal envs (dictionary observations); set vec_env_kwargs.norm_obs: false")
+    if obs_shift is not None:
+        raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for goal envs")
+    kw = dict(env_kwargs or {})
+    unknown = sorted(set(kw) - {"tol", "reward_type"})
+    if unknown:
+        raise ValueError(f"{env_name}: unknown env_kwargs {unknown}; the stepper takes tol and reward_type")
+    if model is not None and kw:
+        raise ValueError(f"{env_name}: pass either a model description or env_kwargs")
+    return model if model is not None else MODELS_GOAL[env_name](**kw)
+
+
 def spatial_struct(m):
     """models3d dict -> ilsx_spatial_model (include/ilsx.h)."""
     s = _lib.SpatialModel()
@@ -260,12 +287,21 @@ class DeviceObsRms:
 
 class HipVectorEnv:
     def __init__(self, env_name, env_num, seed=0, ctx=None, model=None, norm_obs=False, obs_rms=None, update_obs_rms=True,
-                 obs_shift=None, obs_scale=None):
+                 obs_shift=None, obs_scale=None, env_kwargs=None):
+        self.goal_model = None
+        if env_name in GOAL:            # refused before the library is entered: what a goal env cannot do
+            self.goal_model = goal_model_checked(env_name, env_kwargs, model, norm_obs, obs_shift)
+        elif env_kwargs:
+            raise ValueError(f"{env_name}: env_kwargs are a goal env's (point-reach)")
         self.ctx = ctx or get_context()
         self.env_name = env_name
         self.env_num = int(env_num)
         self.h = C.c_void_p()
-        if env_name in SWIMMER:         # the free chain in a viscous medium: the model description is the one source of the constants
+        if self.goal_model is not None:
+            self.model = None
+            ms = goal_struct(self.goal_model)
+            _lib.check(self.ctx.lib.ilsx_vecenv_create_goal(self.ctx.h, C.byref(ms), self.env_num, C.c_uint64(seed), C.byref(self.h)))
+        elif env_name in SWIMMER:         # the free chain in a viscous medium: the model description is the one source of the constants
             if obs_shift is not None:
                 raise NotImplementedError(f"{env_name}: ScaledEnv / MinmaxEnv are not available for this task")
             self.swimmer_model = model or MODELS_SWIMMER[env_name]()
@@ -321,6 +357,15 @@ class HipVectorEnv:
         self.discrete_n = dn.value      # 0: Box actions
         ac = Discrete(dn.value) if dn.value else Box(-np.ones(self.act_dim), np.ones(self.act_dim))
         self.observation_space, self.action_space = [ob] * self.env_num, [ac] * self.env_num  # vecenvs.py:118-140
+        if self.goal_model is not None:   # gym's GoalEnv interface: a dictionary space, compute_reward and the rule's two attributes
+            from ..her import DictSpace
+            dq, dg = C.c_int(), C.c_int()
+            _lib.check(self.ctx.lib.ilsx_vecenv_goal_dims(self.h, C.byref(dq), C.byref(dg)))
+            self.d_obs, self.d_goal = dq.value, dg.value
+            ob = DictSpace(observation=Box(-np.ones(self.d_obs), np.ones(self.d_obs)), desired_goal=Box(-np.ones(self.d_goal), np.ones(self.d_goal)),
+                           achieved_goal=Box(-np.ones(self.d_goal), np.ones(self.d_goal)))
+            self.reward_type, self.distance_threshold = self.goal_model["reward_type"], float(self.goal_model["tol"])
+            self.observation_space = [ob] * self.env_num
         self.single_observation_space, self.single_action_space = ob, ac
         self.obs_shift, self.obs_scale = obs_shift, obs_scale
         if obs_shift is not None:   # ScaledEnv / MinmaxEnv folded into the stepper
@@ -393,6 +438,23 @@ class HipVectorEnv:
         infos = [{"env_id": int(i)} for i in env_ids]  # vecenvs.py:217-219
         return obs.numpy().astype(np.float64), rew.numpy().astype(np.float64), done.numpy().astype(bool), infos
 
+    # ---- goal envs
+    def compute_reward(self, achieved_goal, desired_goal, info=None):
+        """gym's GoalEnv rule on the goal distance, on the host (what the stepper and the hindsight kernels evaluate on the device)."""
+        if self.goal_model is None:
+            raise AttributeError(f"{self.env_name}: not a goal env")
+        d = np.linalg.norm(np.asarray(achieved_goal) - np.asarray(desired_goal), axis=-1)
+        return -(d > self.distance_threshold).astype(np.float32) if self.reward_type == "sparse" else -d.astype(np.float32)
+
+    def goal_success(self):
+        """|achieved - desired| <= tol per env, from the simulator state.  An evaluation round freezes ended envs, so after one this is
+        every episode's last step."""
+        if self.goal_model is None:
+            raise AttributeError(f"{self.env_name}: not a goal env")
+        q, _ = self.get_state()
+        g = self.d_goal
+        return np.linalg.norm(q[:, :g] - q[:, g:2 * g], axis=-1) <= self.distance_threshold
+
     # ---- simulator state (tests, snapshots)
     def get_state(self):
         q = np.empty((self.env_num, self.nq)); v = np.empty((self.env_num, self.nv))
@@ -457,4 +519,5 @@ def get_envs(env_specs, env_wrapper=None, wrapper_kwargs=None, ctx=None, norm_ob
     w = env_wrapper(**(wrapper_kwargs or {})) if env_wrapper is not None else ProxyEnv()
     return HipVectorEnv(env_specs["env_name"], env_specs.get("env_num", 1),
                         seed=env_specs.get("training_env_seed", env_specs.get("seed", 0)), ctx=ctx, norm_obs=norm_obs,
-                        obs_rms=obs_rms, update_obs_rms=update_obs_rms, obs_shift=w.shift, obs_scale=w.scale)
+                        obs_rms=obs_rms, update_obs_rms=update_obs_rms, obs_shift=w.shift, obs_scale=w.scale,
+                        env_kwargs=env_specs.get("env_kwargs") if env_specs["env_name"] in GOAL else None)

@@ -13,7 +13,10 @@ import random
 
 import numpy as np
 
+from . import _lib
+from .algorithm import DeviceRLAlgorithm
 from .device import host_ptr
+from .replay import SimpleReplayBuffer
 from .sac import SoftActorCritic
 from .td3 import TD3 as _TD3, MlpGaussianNoisePolicy
 
@@ -42,6 +45,13 @@ class TD3(_TD3):
     def train_step(self, batch, eps_target=None):
         super().train_step(_cat(batch), eps_target)
 
+    def train_from_replay(self, replay_buffer, n_steps, batch_size):
+        """n_steps x (hindsight batch drawn on the device, train_step) for a DeviceGoalReplayBuffer; any other ring goes to the library's
+        own uniform sampling as before."""
+        if not isinstance(replay_buffer, DeviceGoalReplayBuffer):
+            return super().train_from_replay(replay_buffer, n_steps, batch_size)
+        _train_from_goal_replay(self, replay_buffer, n_steps, batch_size, (None,))
+
 
 class SAC(SoftActorCritic):
     """her/sac.py:12-251: sac_alpha on concatenated inputs, target entropy -|A| (:52)."""
@@ -52,6 +62,22 @@ class SAC(SoftActorCritic):
 
     def train_step(self, batch, eps_next=None, eps_cur=None):
         super().train_step(_cat(batch), eps_next, eps_cur)
+
+    def train_from_replay(self, replay_buffer, n_steps, batch_size):
+        if not isinstance(replay_buffer, DeviceGoalReplayBuffer):
+            return super().train_from_replay(replay_buffer, n_steps, batch_size)
+        _train_from_goal_replay(self, replay_buffer, n_steps, batch_size, (None, None))
+
+
+def _train_from_goal_replay(trainer, rb, n_steps, batch_size, noise_args):
+    """TorchRLAlgorithm._do_training (torch_rl_algorithm.py:28-34) over a DeviceGoalReplayBuffer: sampler launch and step launches follow
+    each other on the context's stream.  The batch lives in the buffer's own device arrays, so nothing has to be kept alive and nothing
+    waits on the host — except the first step after end_epoch, whose statistics are read back as in every trainer."""
+    B = int(batch_size)
+    for _ in range(int(n_steps)):
+        b = rb.random_batch(B)
+        trainer._call("train_step", b["observations"].ptr, b["actions"].ptr, b["rewards"].ptr, b["terminals"].ptr, b["next_observations"].ptr,
+                      B, *noise_args)
 
 
 class MlpGaussianAndEpsilonPolicy(MlpGaussianNoisePolicy):
@@ -69,12 +95,35 @@ class MlpGaussianAndEpsilonPolicy(MlpGaussianNoisePolicy):
         self.sigma, self._max_sigma, self._min_sigma = max_sigma, max_sigma, (max_sigma if min_sigma is None else min_sigma)
         self._epsilon, self._decay_period, self._action_space = epsilon, decay_period, action_space
         self.min_act, self.t = min_act, 0
+        self.env = None      # the device env this policy's exploration is bound to (install)
         self.observation_key, self.desired_goal_key = observation_key, desired_goal_key
         # exploration randomness comes from the GLOBAL `random` / `np.random` streams, which set_seed(variant seed) seeds — as in the
         # reference (policies.py:537-552); a private RandomState here gave every variant seed the same exploration noise
 
     def set_num_steps_total(self, t):
         self.t = t
+        if getattr(self, "env", None) is not None:
+            _lib.check(self.env.ctx.lib.ilsx_vecenv_set_exploration_t(self.env.h, int(t)))
+
+    # ---- on a device env (HipVectorEnv): exploration runs in the fused rollout, one draw of epsilon per env
+    def install(self, env):
+        """Bind epsilon / max_sigma / min_sigma / decay_period / min_act / max_act to the device env: the Gaussian strategy of
+        ilsx_vecenv_set_exploration plus its epsilon-uniform branch, as ddpg.PolicyWrappedWithExplorationStrategy binds its strategy.
+        The uniform branch samples Box(min_act, max_act) — the env's action space for every env this policy is built with."""
+        import ctypes as C
+        if self.env is not None and self.env is not env:
+            raise RuntimeError("MlpGaussianAndEpsilonPolicy: already bound to another vec env; one exploration policy drives one training env")
+        lib = env.ctx.lib
+        cfg = _lib.ExploreCfg(1, 0, 0.0, 0.0, float(self._max_sigma), float(self._min_sigma), float(self._decay_period),
+                              float(self.min_act), float(self.max_act))
+        _lib.check(lib.ilsx_vecenv_set_exploration(env.h, C.byref(cfg)))
+        _lib.check(lib.ilsx_vecenv_set_exploration_epsilon(env.h, float(self._epsilon)))
+        self.env = env
+
+    def before_rollout_step(self, env):
+        if self.env is not env:
+            self.install(env)
+        _lib.check(env.ctx.lib.ilsx_vecenv_set_exploration_t(env.h, int(self.t)))
 
     def _flat(self, obs):
         if isinstance(obs, dict):
@@ -445,3 +494,101 @@ class HER:
             self.trainer.end_epoch()
             history.append(self.evaluate())
         return history
+
+
+RELABEL_TYPES = {None: 0, "future": 1, "final": 2}
+
+
+class DeviceGoalReplayBuffer(SimpleReplayBuffer):
+    """The hindsight buffer of the vectorised loop: a ring whose observation segment is observation | desired_goal | achieved_goal — what
+    a goal env's fused rollout records (HipVectorEnv("point-reach"), path mode: whole episodes, registered as trajectories) — and a
+    `random_batch` that is ONE launch (ilsx_her_sample): trajectory, step and relabel step are drawn in the kernel from the ring's device
+    mirror of its trajectory table, then gathered, relabelled, rewarded and concatenated.  Nothing is drawn on the host and nothing goes
+    up per batch.  The draw rule is the reference's distribution for trajectories that do not wrap the ring and stays inside the
+    trajectory for those that do; it is not the reference's RandomState stream — DeviceHindsightReplayBuffer keeps
+    that one.  Returns the `_her_cat` device batch the goal-conditioned trainers accept."""
+
+    def __init__(self, max_replay_buffer_size, env, random_seed=1995, relabel_type="future", her_ratio=0.8, observation_key="observation",
+                 desired_goal_key="desired_goal", achieved_goal_key="achieved_goal", ctx=None):
+        if relabel_type not in RELABEL_TYPES:
+            raise ValueError(f"relabel_type={relabel_type!r}: the device sampler knows 'future', 'final' and None")
+        sp = getattr(env, "single_observation_space", None) or env.observation_space
+        spaces = sp.spaces
+        act = getattr(env, "single_action_space", None) or env.action_space
+        self.observation_key, self.desired_goal_key, self.achieved_goal_key = observation_key, desired_goal_key, achieved_goal_key
+        self.d_obs, self.d_goal = int(np.prod(spaces[observation_key].shape)), int(np.prod(spaces[desired_goal_key].shape))
+        assert int(np.prod(spaces[achieved_goal_key].shape)) == self.d_goal
+        self.her_ratio, self.relabel_type = her_ratio, relabel_type
+        self.reward_kind, self.threshold = device_reward_rule(env)
+        super().__init__(max_replay_buffer_size, self.d_obs + 2 * self.d_goal, int(np.prod(act.shape)), random_seed=random_seed, ctx=ctx)
+        self._out = None
+
+    def _row(self, d):
+        return np.concatenate([np.asarray(d[k], np.float32).ravel() for k in (self.observation_key, self.desired_goal_key, self.achieved_goal_key)])
+
+    def add_sample(self, observation, action, reward, terminal, next_observation, **kwargs):
+        """Host-side insert of one dictionary transition (tests, host envs); the vectorised loop fills the ring from the fused rollout."""
+        self.add_rows(self._row(observation)[None], np.asarray(action)[None], [reward], [terminal], self._row(next_observation)[None])
+
+    def random_batch(self, batch_size, keys=None, u=None, return_indices=False):
+        """u: explicit uniforms, a device float64 [B, 3] array (tests); None = the ring's Philox stream."""
+        import ctypes as C
+        ctx, B, W, a = self.ctx, int(batch_size), self.d_obs + self.d_goal, self._action_dim
+        relabel = self.relabel_type is not None and self.her_ratio > 0        # relabel_replay_buffer.py:67
+        if self._out is None or self._out[0] != B:
+            self._out = (B, ctx.empty((B, W)), ctx.empty((B, a)), ctx.empty((B,)), ctx.empty((B,)), ctx.empty((B, W)),
+                         ctx.empty((B,), np.int64), ctx.empty((B,), np.int64))
+        _, obs, act, rew, done, nobs, di, dr = self._out
+        _lib.check(ctx.lib.ilsx_her_sample(self.h, B, int(self.her_ratio * B) if relabel else 0, RELABEL_TYPES[self.relabel_type] if relabel else 0,
+                                           self.d_obs, self.d_goal, self.reward_kind, C.c_float(self.threshold), u.ptr if u is not None else None,
+                                           obs.ptr, act.ptr, rew.ptr, done.ptr, nobs.ptr, di.ptr, dr.ptr))
+        out = dict(observations=obs, actions=act, rewards=rew, terminals=done, next_observations=nobs, _her_cat=True)
+        if return_indices:
+            out["indices"], out["indices_relabel"] = di, dr
+        return out
+
+    numpy_batch = DeviceHindsightReplayBuffer.numpy_batch
+
+    def close(self):
+        """ilsx_replay_destroy, once: the ring, its cursors and its trajectory mirror go back to the context (nothing to do when the
+        context is closed already: it has freed them with its own)."""
+        self._out = None
+        if self.h and self.ctx.h:
+            _lib.check(self.ctx.lib.ilsx_replay_destroy(self.h))
+        self.h = None
+
+
+class VecHER(DeviceRLAlgorithm):
+    """her/her.py:8-42 as a TorchRLAlgorithm over a DEVICE goal env: every env steps in the fused rollout (policy on the observation |
+    desired_goal prefix, exploration, physics, record, auto-reset in path mode — episodes enter the ring when they end, as the reference's
+    path builders hand them over), batches are drawn by ilsx_her_sample, and logging, snapshots and counters are DeviceRLAlgorithm's.
+    Each evaluation row gains `Success Rate`: the share of evaluation episodes whose LAST step is a success, over every episode the
+    evaluation played (the env's goal_success() after each evaluation round, whose ended envs stay frozen at their last state)."""
+
+    def __init__(self, trainer, env, training_env, eval_env, exploration_policy, replay_buffer=None, her_ratio=0.8, relabel_type="future",
+                 **kwargs):
+        if not hasattr(training_env, "goal_success"):
+            raise TypeError("VecHER drives a device goal env (HipVectorEnv('point-reach', ...)); her.HER walks a host env")
+        kwargs["insert_at_episode_end"] = True
+        if replay_buffer is None:
+            assert kwargs["max_path_length"] < kwargs["replay_buffer_size"]
+            replay_buffer = DeviceGoalReplayBuffer(kwargs["replay_buffer_size"], training_env, random_seed=int(np.random.randint(10000)),
+                                                   relabel_type=relabel_type, her_ratio=her_ratio, ctx=trainer.ctx)
+        super().__init__(trainer, env, training_env, eval_env, exploration_policy, replay_buffer=replay_buffer, **kwargs)
+        if not hasattr(self.eval_sampler, "_handles"):
+            raise NotImplementedError("VecHER evaluates on the device (eval_on_device)")
+
+    def _eval_collect(self):
+        import ctypes as C
+        s = self.eval_sampler
+        pi, ppo, det = s._handles()
+        st = (C.c_double * 18)()
+        first, succ, played = True, 0, 0
+        while first or st[1] < s.num_steps:
+            _lib.check(s.env.ctx.lib.ilsx_eval_rollout(s.env.h, pi, ppo, int(s.max_path_length), int(det), int(first), st))
+            first = False
+            ok = s.env.goal_success()
+            succ, played = succ + int(ok.sum()), played + ok.size
+        out = s.stats_dict(st, "Test")
+        out["Success Rate"] = succ / played
+        return out

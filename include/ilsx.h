@@ -216,6 +216,22 @@ int ilsx_replay_record_floats(const ilsx_replay* rb, int* out);
  * her/sac.py:80-84 feed the networks), act[B, a], rew[B], done[B]. */
 int ilsx_her_gather(ilsx_replay* rb, const int64_t* idx, const int64_t* idx_relabel, int B, int n_relabel, int relabel_on, int d_obs,
                     int d_goal, int reward_kind, float threshold, float* obs_cat, float* act, float* rew, float* done, float* nobs_cat);
+/* The same batch with its indices DRAWN ON THE DEVICE, in one launch: draw, gather, relabel, reward, concatenation.  The ring keeps a
+ * device mirror of its trajectory table (start, length per registered trajectory, in insertion order), uploaded again only after the table
+ * changed.  Row b takes three uniforms (u0, u1, u2) in [0, 1): u = DEVICE float64 [B, 3], or NULL = Philox keyed by (the ring's seed, its
+ * stream, its sample counter, b).  With floor(u n) taken in float64 and clamped to n - 1:
+ *   t = floor(u0 n_traj), k = floor(u1 L_t), idx = (start_t + k) mod capacity;
+ *   relabel_type 1 `future`: kf = k + floor(u2 (L_t - k)); 2 `final`: kf = L_t - 1; 0 none: kf = k (no goal is replaced, rewards stay);
+ *   idx_relabel = (start_t + kf) mod capacity.
+ * For a trajectory that does not wrap the ring this is the distribution of relabel_replay_buffer.py:71-94; for one that wraps, the
+ * reference's randint(step, traj_len + start) draws from a wrong range or raises, while here the relabel step always lies in the same
+ * trajectory at or after the sampled step.  The first n_relabel rows are relabelled (relabel_type != 0); outputs as ilsx_her_gather, bit for
+ * bit what ilsx_her_gather(idx_out, idx_relabel_out, ...) writes; idx_out / idx_relabel_out: DEVICE int64[B], nullable.
+ * ILSX_ERR_STATE: no registered trajectory.  ILSX_ERR_ARG: ring width != d_obs + 2 d_goal, n_relabel outside [0, B], relabel_type outside
+ * {0, 1, 2}, reward_kind outside {0, 1}.  ILSX_ERR_UNSUPPORTED: act_dim > d_obs + d_goal (as ilsx_her_gather). */
+int ilsx_her_sample(ilsx_replay* rb, int B, int n_relabel, int relabel_type, int d_obs, int d_goal, int reward_kind, float threshold,
+                    const double* u, float* obs_cat, float* act, float* rew, float* done, float* nobs_cat, int64_t* idx_out,
+                    int64_t* idx_relabel_out);
 int ilsx_replay_size(ilsx_replay* rb, int64_t* size, int64_t* top);
 int ilsx_replay_clear(ilsx_replay* rb);
 /* _traj_endpoints in insertion order: writes up to max pairs (start,end) to HOST arrays; *n = count. */
@@ -792,6 +808,26 @@ typedef struct {
   double sleep_lin_tol, sleep_ang_tol, sleep_time;
 } ilsx_lunar_model;
 int ilsx_vecenv_create_lunar(ilsx_ctx* ctx, const ilsx_lunar_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
+/* A goal env on the lane-per-env frame: ilswiss_amd/her.py's PointReachEnv as a device stepper (a STAND-IN for the reference's MuJoCo Fetch
+ * tasks, not one of them).  float64 state qpos = (p_x, p_y, g_x, g_y) — the goal is episode state —, qvel = (v_x, v_y); Box(-1, 1)^2 actions.
+ * An observation row is 8 float32 columns, observation (p | v) | desired_goal (g) | achieved_goal (p): the segment layout of ilsx_her_gather
+ * and ilsx_her_sample, so a ring of width 8 filled by ilsx_rollout_step (path mode) is a hindsight ring.  A policy on this env reads the
+ * first d_obs + d_goal = 6 columns of the row in place; one of any other input width is refused (ILSX_ERR_ARG).
+ *   step   v = step_scale * clip(a, -1, 1) in float32 (as numpy evaluates it for a float32 action), widened; p = clip(p + v, -1, 1) in float64;
+ *          reward_kind 0: -(|p - g| > tol), 1: -|p - g|, on float64; never done (max_path_length ends episodes)
+ *   reset  p = U(+-p_range)^2, v = 0, g = U(+-g_range)^2 from counters 0..3 of the env's Philox stream
+ * Constants must be finite and positive (ranges at most 1), else ILSX_ERR_ARG before anything is allocated.  Refused on a goal env with
+ * ILSX_ERR_UNSUPPORTED: ilsx_vecenv_obs_norm(norm_obs=1), ilsx_vecenv_set_obs_affine, ilsx_rollout_steps_lockstep,
+ * ilsx_eval_rollouts_lockstep, ilsx_ppo_rollout. */
+enum { ILSX_GOAL_TASK = 18 };   /* the task id of the handle, outside ILSX_CLASSIC_* */
+typedef struct {
+  double tol, step_scale, p_range, g_range;
+  int32_t reward_kind;   /* 0 sparse, 1 dense */
+  int32_t pad;
+} ilsx_goal_model;
+int ilsx_vecenv_create_goal(ilsx_ctx* ctx, const ilsx_goal_model* model, int n_env, uint64_t seed, ilsx_vecenv** out);
+/* widths of the observation and goal segments of a goal env's row (ILSX_ERR_STATE on any other env) */
+int ilsx_vecenv_goal_dims(const ilsx_vecenv* env, int* d_obs, int* d_goal);
 /* discrete_n = n of a Discrete(n) action space, 0 for Box actions */
 int ilsx_vecenv_action_space(const ilsx_vecenv* env, int* discrete_n);
 /* Path mode of the fused rollout (ilsx_rollout_step with a replay ring): 0 (default) = every transition enters the ring when it
@@ -859,6 +895,13 @@ int ilsx_vecenv_set_exploration(ilsx_vecenv* env, const ilsx_explore_cfg* cfg); 
 int ilsx_vecenv_set_exploration_t(ilsx_vecenv* env, int64_t t);                    /* the t of the rollout's next steps (set_num_steps_total) */
 /* one exploration step on act[n_env, a] (device, in place); eps: device float64 [n_env, a] N(0,1) draws or NULL = Philox */
 int ilsx_vecenv_explore(ilsx_vecenv* env, float* act, const double* eps, int64_t t);
+/* The epsilon-uniform branch of the Gaussian strategy — MlpGaussianAndEpsilonPolicy.get_actions (policies.py:537-552): with probability
+ * epsilon an env takes a uniform action act_j = (float)(low + (high - low) * u_{1+j}) instead of the noisy one (u_0 < epsilon decides, per
+ * env; the reference draws once per call for its whole batch, which is the same thing at one env).  epsilon in [0, 1], Gaussian kind only
+ * (ILSX_ERR_STATE otherwise); ilsx_vecenv_set_exploration puts it back to 0, and at 0 the strategy's output is bit for bit what it is
+ * without this call.  _explore_u: ilsx_vecenv_explore with explicit draws u = device float64 [n_env, 1 + a] in [0, 1) (NULL = Philox). */
+int ilsx_vecenv_set_exploration_epsilon(ilsx_vecenv* env, double epsilon);
+int ilsx_vecenv_explore_u(ilsx_vecenv* env, float* act, const double* eps, const double* u, int64_t t);
 /* Evaluation on the device — VecPathSampler.obtain_samples / rollout (samplers/vec_sampler.py:5-93,124-142): reset all envs,
  * then every env plays ONE episode with `pi` (ilsx_net: tanh-Gaussian or noise policy) or `ppo`'s Gaussian policy; envs that
  * end (terminal or max_path_length) are frozen, not reset.  stats_host[18] (nullable, float64) accumulates what
