@@ -79,6 +79,13 @@ class TabularLogger:
                 pickle.dump(obj, f)
 
 
+def sync_eval_obs_rms(alg):
+    """norm_obs: the eval env of a run was built on the training env's statistics (one shared object in the reference,
+    sac_alpha_exp_script.py:56-66) and takes their current values before an evaluation.  Nothing to do for any other env."""
+    if getattr(getattr(alg, "training_env", None), "norm_obs", False) and hasattr(getattr(alg, "eval_env", None), "sync_obs_rms"):
+        alg.eval_env.sync_obs_rms()
+
+
 class DeviceRLAlgorithm:
     """TorchRLAlgorithm(trainer, env, training_env, eval_env, exploration_policy, **rl_alg_params)."""
 
@@ -235,6 +242,7 @@ class DeviceRLAlgorithm:
                     pool = ThreadPoolExecutor(max_workers=1)
                 self._eval_async_start(pool, epoch, t0 - t_epoch, t0 - t_start)
             else:
+                sync_eval_obs_rms(self)
                 self.evaluate(epoch, time.perf_counter() - t_epoch, time.perf_counter() - t_start)
                 self._t_eval = time.perf_counter() - t0
             self.trainer.end_epoch()
@@ -289,6 +297,7 @@ class DeviceRLAlgorithm:
         """End of an epoch in the asynchronous form: log the evaluation that ran beside this epoch, freeze the policy, take what the row and
         the snapshots need, start this epoch's evaluation.  Returns after the hand-over; the training loop goes on."""
         self._eval_async_join()
+        sync_eval_obs_rms(self)    # (after the join: the evaluation that ran beside this epoch used the statistics it was started with)
         self._eval_freeze()
         pre = self._eval_begin(epoch, epoch_time, total_time)
         pre["snapshot"] = self.get_epoch_snapshot()
@@ -580,6 +589,9 @@ class DeviceRLAlgorithmGroup:
             t_eval0 = time.perf_counter()
             if use_async:
                 pending = join(pending)
+            for a in algs:
+                sync_eval_obs_rms(a)
+            if use_async:
                 pres = []
                 for a in algs:
                     a._t_sample, a._t_train = t_sample, t_train

@@ -136,6 +136,107 @@ __global__ __launch_bounds__(256) void k_obs_normalize(const float* src, float* 
   dst[t] = (float)fmin(fmax(z, -10.0), 10.0);
 }
 
+// The tail of a fused rollout step of a normalising env that records into a ring (base_algorithm.py:183-277 over vecenvs.py:158-257): the ring
+// holds what step() returned, i.e. normalised rows.  One workgroup owns observation dimension i and does, for its column, in the reference's
+// order: update(nobs of all envs) — the arithmetic and reduction order of k_obs_rms_update, so the statistics are bit for bit that kernel's —,
+// the record's observation segment = the policy input the step acted on, its next-observation segment = normalize(nobs) under the updated
+// statistics, update(reset observations of the envs whose episode just ended, ep_len == 0), and the next policy input: reset rows normalised
+// under the newest statistics, every other row THE SAME BITS as the record's next observation (never re-normalised).
+// The record of env e is where the stepper put it: ring slot (top + e) mod cap, or with `stage` the staging row of the step just taken — the
+// stepper wrote at the episode length before the step, which is ep_len - 1 now, or the flushed length - 1 when the episode ended.
+struct NormRecordArgs {
+  const float *nobs, *obs_cur;   // [n_env][o] raw: the step's observation (pre-reset), the env's current one (post auto-reset)
+  float* obs_n;                  // [n_env][o] in: what the policy read; out: what it reads next
+  const int* ep_len;             // [n_env] after the step: 0 = the episode ended in it
+  const int* flush_len;          // path mode: length | terminal << 30 of the episodes that ended
+  ObsRms* rms;
+  float *ring, *stage;           // stage != null: path mode
+  int n_env, o, a, rec, stage_len, update;
+  long long cap, top;
+};
+// REG: up to 256 * NORM_REC_K envs — a thread's rows of the column (tid, tid + 256, ...) are read once, all loads in flight together, and
+// every pass works on registers.  Otherwise every pass re-reads memory.  Both visit a thread's rows in the same order: the same sums.
+#define NORM_REC_K 16
+template <bool REG>
+__global__ __launch_bounds__(256) void k_obs_norm_record(const NormRecordArgs A) {
+  __shared__ double sh[4];
+  constexpr int K = REG ? NORM_REC_K : 1;
+  const int i = blockIdx.x, tid = threadIdx.x, o = A.o;
+  auto rows = [&](auto f) {   // f(k, r) for this thread's rows r, k = the row's register slot
+    if constexpr (REG) {
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (tid + 256 * k < A.n_env) f(k, tid + 256 * k);
+    } else {
+      for (int r = tid; r < A.n_env; r += 256) f(0, r);
+    }
+  };
+  float x_next[K], x_cur[K], x_in[K];   // nobs, obs_cur and the policy input of the row
+  int len[K];
+  if constexpr (REG)
+    rows([&](int k, int r) { const size_t at = (size_t)r * o + i; x_next[k] = A.nobs[at]; x_cur[k] = A.obs_cur[at]; x_in[k] = A.obs_n[at]; len[k] = A.ep_len[r]; });
+  auto nobs_of = [&](int k, int r) { return REG ? x_next[k] : A.nobs[(size_t)r * o + i]; };
+  auto cur_of = [&](int k, int r) { return REG ? x_cur[k] : A.obs_cur[(size_t)r * o + i]; };
+  auto len_of = [&](int k, int r) { return REG ? len[k] : A.ep_len[r]; };
+  auto bsum = [&](double v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    __syncthreads();
+    if ((tid & 63) == 0) sh[tid >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+  };
+  // RunningMeanStd.update with the step's observations (ended == false) or with the reset observations of the envs whose episode ended;
+  // every thread carries the column's statistics (all of them hold the same sums)
+  double mean = A.rms->mean[i], var = A.rms->var[i], count = A.rms->count[i];
+  auto update = [&](bool ended) {
+    double s = 0.0, n = 0.0;
+    rows([&](int k, int r) {
+      if (!ended || len_of(k, r) == 0) { s += (double)(ended ? cur_of(k, r) : nobs_of(k, r)); n += 1.0; }
+    });
+    s = bsum(s); n = bsum(n);
+    if (n == 0.0) return;   // block-uniform
+    const double bm = s / n;
+    double ss = 0.0;
+    rows([&](int k, int r) {
+      if (!ended || len_of(k, r) == 0) { const double d = (double)(ended ? cur_of(k, r) : nobs_of(k, r)) - bm; ss += d * d; }
+    });
+    ss = bsum(ss);
+    const double bv = ss / n, delta = bm - mean, tot = count + n;
+    const double m2 = var * count + bv * n + delta * delta * count * n / tot;
+    mean = mean + delta * n / tot;
+    var = m2 / tot;
+    count = tot;
+  };
+  auto normalize = [](float x, double m, double v) {   // k_obs_normalize's expression
+    const double z = ((double)x - m) / sqrt(v + 1.1920928955078125e-07);
+    return (float)fmin(fmax(z, -10.0), 10.0);
+  };
+  if (A.update) update(false);
+  const double mean1 = mean, var1 = var;
+  const int next_off = o + A.a + 2;
+  rows([&](int k, int r) {
+    float* rec;
+    if (A.stage) {
+      const int l = len_of(k, r);
+      const int row = (l ? l : (A.flush_len[r] & ((1 << 30) - 1))) - 1;
+      if (row < 0 || row >= A.stage_len) return;   // (a stepper that flagged no length: nothing was staged)
+      rec = A.stage + ((size_t)r * A.stage_len + row) * A.rec;
+    } else {
+      long long slot = A.top + r;
+      if (slot >= A.cap) slot -= A.cap;
+      rec = A.ring + (size_t)slot * A.rec;
+    }
+    rec[i] = REG ? x_in[k] : A.obs_n[(size_t)r * o + i];
+    rec[next_off + i] = normalize(nobs_of(k, r), mean1, var1);
+  });
+  if (A.update) update(true);
+  rows([&](int k, int r) {   // a row that goes on is normalised exactly as its record's next observation was: the same bits
+    A.obs_n[(size_t)r * o + i] = len_of(k, r) == 0 ? normalize(cur_of(k, r), mean, var) : normalize(nobs_of(k, r), mean1, var1);
+  });
+  if (A.update && tid == 0) { A.rms->mean[i] = mean; A.rms->var[i] = var; A.rms->count[i] = count; }
+}
+
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double impedance_d(double r_abs, const double* solimp) {
   const double d0 = solimp[0], dmax = solimp[1], width = solimp[2];
@@ -1029,6 +1130,60 @@ static int env_after_step_norm(ilsx_vecenv* e) {
   ILSX_TRY(env_obs_norm(e, e->nobs, e->n_env, nullptr, nullptr, nullptr, 0));
   return env_obs_norm(e, e->obs_cur, e->n_env, e->ep_len, e->obs_cur, e->obs_n, e->n_env);
 }
+// the same after a step that recorded into a ring (A: the stepper's arguments): statistics, the records' normalised observation segments and
+// the next policy input in one launch (k_obs_norm_record)
+#ifdef ILSX_NORM_RECORD_CHAIN
+// Measurement build only (make VAR=chain VARFLAGS=-DILSX_NORM_RECORD_CHAIN, tools/bench_norm_rollout.py): the same step as four launches —
+// the two existing statistics updates around an element-parallel record fix-up, then the reset rows.  Timed against the single launch in
+// profiles/norm_rollout_bench.json; not part of the shipped library.
+__global__ __launch_bounds__(256) void k_norm_chain_fix(const NormRecordArgs A) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= A.n_env * A.o) return;
+  const int r = t / A.o, i = t - r * A.o;
+  float* rec;
+  if (A.stage) {
+    const int len = A.ep_len[r];
+    const int row = (len ? len : (A.flush_len[r] & ((1 << 30) - 1))) - 1;
+    if (row < 0 || row >= A.stage_len) return;
+    rec = A.stage + ((size_t)r * A.stage_len + row) * A.rec;
+  } else {
+    long long slot = A.top + r;
+    if (slot >= A.cap) slot -= A.cap;
+    rec = A.ring + (size_t)slot * A.rec;
+  }
+  const double z = ((double)A.nobs[t] - A.rms->mean[i]) / sqrt(A.rms->var[i] + 1.1920928955078125e-07);
+  const float nn = (float)fmin(fmax(z, -10.0), 10.0);
+  rec[i] = A.obs_n[t];
+  rec[A.o + A.a + 2 + i] = nn;
+  A.obs_n[t] = nn;
+}
+__global__ __launch_bounds__(256) void k_norm_chain_reset(const NormRecordArgs A) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= A.n_env * A.o) return;
+  const int r = t / A.o, i = t - r * A.o;
+  if (A.ep_len[r] != 0) return;
+  const double z = ((double)A.obs_cur[t] - A.rms->mean[i]) / sqrt(A.rms->var[i] + 1.1920928955078125e-07);
+  A.obs_n[t] = (float)fmin(fmax(z, -10.0), 10.0);
+}
+#endif
+static int env_norm_record(ilsx_vecenv* e, const EnvStepArgs& A) {
+  NormRecordArgs N;
+  N.nobs = e->nobs; N.obs_cur = e->obs_cur; N.obs_n = e->obs_n; N.ep_len = e->ep_len; N.flush_len = A.flush_len; N.rms = e->rms;
+  N.ring = A.replay; N.stage = A.stage; N.n_env = e->n_env; N.o = e->o; N.a = e->a; N.rec = A.rec; N.stage_len = A.stage_len;
+  N.update = e->update_rms ? 1 : 0; N.cap = A.cap; N.top = A.top;
+#ifdef ILSX_NORM_RECORD_CHAIN
+  const dim3 grid((e->n_env * e->o + 255) / 256);
+  if (N.update) hipLaunchKernelGGL(k_obs_rms_update, dim3(e->o), dim3(256), 0, e->ctx->stream, (const float*)e->nobs, e->n_env, e->o, (const int*)nullptr, e->rms);
+  hipLaunchKernelGGL(k_norm_chain_fix, grid, dim3(256), 0, e->ctx->stream, N);
+  if (N.update) hipLaunchKernelGGL(k_obs_rms_update, dim3(e->o), dim3(256), 0, e->ctx->stream, (const float*)e->obs_cur, e->n_env, e->o, (const int*)e->ep_len, e->rms);
+  hipLaunchKernelGGL(k_norm_chain_reset, grid, dim3(256), 0, e->ctx->stream, N);
+#else
+  if (e->n_env <= 256 * NORM_REC_K) hipLaunchKernelGGL(k_obs_norm_record<true>, dim3(e->o), dim3(256), 0, e->ctx->stream, N);
+  else hipLaunchKernelGGL(k_obs_norm_record<false>, dim3(e->o), dim3(256), 0, e->ctx->stream, N);
+#endif
+  HIPCHK(hipGetLastError());
+  return ILSX_OK;
+}
 
 // One iteration of BaseAlgorithm's sampling loop (base_algorithm.py:183-277) for ALL envs, on the device:
 // actions (policy or uniform random) -> physics -> transition record into the replay ring -> auto-reset.
@@ -1159,12 +1314,11 @@ static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, i
   HIPCHK(hipSetDevice(ctx->device));
   if (rb && (rb->o != e->o || rb->a != e->a)) ILSX_FAIL(ILSX_ERR_ARG, "replay dims (%d,%d) != env dims (%d,%d)", rb->o, rb->a, e->o, e->a);
   if (rb && e->n_env > rb->cap) ILSX_FAIL(ILSX_ERR_ARG, "n_env exceeds the replay capacity");
-  // the fused record holds the env's RAW observations while the policy acts on the normalised ones (policy_obs()): an
-  // off-policy learner fed from this ring would train on a different observation scale than it acts on.  The reference
-  // stores what step() returned, i.e. normalised observations (vecenvs.py:251-257); no shipped spec combines the two.
-  if (rb && e->norm_obs)
-    ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_rollout_step: norm_obs=1 with a replay ring is not supported (the fused insert records raw "
-              "observations); use the on-policy rollout (ilsx_ppo_rollout) or turn norm_obs off");
+  // The stepper's fused insert records the env's RAW observations while the policy acts on the normalised ones (policy_obs()).  The reference
+  // stores what step() returned, i.e. normalised observations (vecenvs.py:251-257): with a ring, env_norm_record rewrites the two observation
+  // segments of the step's records after the stepper.  (A goal env cannot have norm_obs on: ilsx_vecenv_obs_norm refuses it.)
+  const bool norm_record = rb && e->norm_obs;
+  if (norm_record && e->goal_dobs > 0) ILSX_FAIL(ILSX_ERR_UNSUPPORTED, "ilsx_rollout_step: norm_obs=1 with a replay ring is not available for goal envs");
   const unsigned long long step = ++e->step_ctr;
   if (random_actions && e->discrete_n > 0) {   // Discrete(n).sample()
     hipLaunchKernelGGL(k_random_discrete_actions, dim3((e->n_env + 255) / 256), dim3(256), 0, ctx->stream, e->act, e->n_env, e->discrete_n,
@@ -1188,6 +1342,7 @@ static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, i
   }
   const bool paths = rb && e->path_mode;
   ILSX_TRY(launch_env_step(e, A));
+  if (norm_record) ILSX_TRY(env_norm_record(e, A));   // before finished episodes move from the staging area into the ring
   if (paths) {
     HIPCHK(hipMemcpyAsync(e->flush_host, e->flush_len, (size_t)e->n_env * 4, hipMemcpyDeviceToHost, ctx->stream));
     e->paths_pending = rb;
@@ -1195,7 +1350,7 @@ static int rollout_step_impl(ilsx_vecenv* e, ilsx_net* pi, ilsx_net* label_pi, i
   } else if (rb) {
     ILSX_TRY(replay_advance_device_rows(rb, e->n_env));
   }
-  return env_after_step_norm(e);
+  return norm_record ? ILSX_OK : env_after_step_norm(e);
 }
 
 extern "C" int ilsx_rollout_step(ilsx_vecenv* e, ilsx_net* pi, ilsx_replay* rb, int max_path_length, int random_actions,

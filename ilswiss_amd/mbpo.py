@@ -428,6 +428,9 @@ class MBPO(DeviceRLAlgorithm):
                  max_model_t=None, target_update_interval=1, **kwargs):
         if int(target_update_interval) != 1:
             raise NotImplementedError("MBPO(target_update_interval != 1): libilsx's SAC updates its targets every step")
+        if getattr(kwargs.get("training_env"), "norm_obs", False):
+            raise NotImplementedError("MBPO with a norm_obs training env: the device termination predicates and the model rollouts read "
+                                      "observation columns as raw quantities")
         self.model, self.algo, self.is_terminal = model, algo, is_terminal
         self._rollout_stat = OrderedDict()
         super().__init__(trainer=_MBPOTrainer(self), env=env, **kwargs)

@@ -875,7 +875,15 @@ int ilsx_ppo_rollout(ilsx_ppo* ppo, ilsx_vecenv* env, int T, int max_path_length
 /* One iteration of BaseAlgorithm's sampling loop for ALL envs on the device (base_algorithm.py:183-277):
  * actions (policy, or env.action_space.sample() when random_actions) -> physics -> one transition record per
  * env written straight into the replay ring (nullable) -> auto-reset on done or max_path_length.  no_terminal: the
- * stored terminal flag is forced to 0 (base_algorithm.py:195-196,208-210; the adv-IRL configs). */
+ * stored terminal flag is forced to 0 (base_algorithm.py:195-196,208-210; the adv-IRL configs).
+ * A normalising env (ilsx_vecenv_obs_norm, flat envs only) with a ring records what the policy saw, as the reference does
+ * (vecenvs.py:251-257): the record's observation is bit for bit the policy input of the step, its next observation is the
+ * step's observation normalised under the statistics updated with that batch, and for an env whose episode goes on that
+ * value IS the next policy input (never re-normalised; old rows do not follow the statistics).  Envs whose episode ended
+ * feed their reset observations to the statistics next and are normalised under the newest ones.  update_obs_rms = 0:
+ * the same without the two updates.  The same holds for _begin / _end, _relabel (policy and expert both act on the
+ * normalised input) and the lock-step form, with and without path mode.  Without a ring the policy input is re-normalised
+ * as a whole after every step, as before. */
 int ilsx_rollout_step(ilsx_vecenv* env, ilsx_net* pi, ilsx_replay* rb, int max_path_length, int random_actions,
                       int deterministic, int no_terminal);
 /* Exploration strategies of deterministic policies on the device (rlkit/exploration_strategies/{gaussian,ou}_strategy.py behind

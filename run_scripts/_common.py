@@ -24,6 +24,21 @@ def flatten_spec(spec):
     return next(variants(spec))
 
 
+def vec_env_kwargs_of(variant, who=None, raw_obs_reason=None):
+    """env_specs.vec_env_kwargs (sac_alpha_exp_script.py:49-66): norm_obs / update_obs_rms for get_envs.  Refused here, before the library is
+    entered: norm_obs in a split run (every rank would normalise by the statistics of its own shard of the envs) and, with `raw_obs_reason`,
+    norm_obs in an algorithm that reads observation columns as raw quantities."""
+    kw = dict((variant.get("env_specs") or {}).get("vec_env_kwargs") or {})
+    if kw.get("norm_obs"):
+        if raw_obs_reason:
+            raise SystemExit(f"{who}: env_specs.vec_env_kwargs.norm_obs is not supported ({raw_obs_reason})")
+        g = int((variant.get("rl_alg_params") or {}).get("split_ranks", 1) or 1)
+        if g > 1 or _SPLIT is not None:
+            raise SystemExit("env_specs.vec_env_kwargs.norm_obs does not combine with rl_alg_params.split_ranks: each rank would normalise by "
+                             "its own shard's statistics")
+    return kw
+
+
 def make_envs(variant, ctx, **vec_kwargs):
     """training env (env_num / training_env_num envs) + a small eval env (its paths are walked on the host)."""
     seed = int(variant.get("seed", 0))

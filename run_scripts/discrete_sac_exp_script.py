@@ -7,7 +7,7 @@ discrete_sac_exp_script.py:43-49).  Several runs per process (`-e a.yaml b.yaml`
 import argparse
 
 import yaml
-from _common import flatten_spec, ia, main, make_envs, split_ranks_of, start, train  # noqa: F401
+from _common import flatten_spec, ia, main, make_envs, split_ranks_of, start, train, vec_env_kwargs_of  # noqa: F401
 
 from ilswiss_amd.algorithm import DeviceRLAlgorithm
 from ilswiss_amd.discrete_sac import DiscreteSoftActorCritic
@@ -17,8 +17,9 @@ from ilswiss_amd.envs.vecenv import Discrete
 def experiment(variant, gpu=0, log_dir=None):
     if split_ranks_of(variant):
         raise SystemExit("discrete SAC: rl_alg_params.split_ranks > 1 is not supported (no split discrete SAC step)")
+    vec_kwargs = vec_env_kwargs_of(variant)   # env_specs.vec_env_kwargs: norm_obs / update_obs_rms
     ctx = start(variant, gpu)
-    training_env, eval_env, env = make_envs(variant, ctx)
+    training_env, eval_env, env = make_envs(variant, ctx, **vec_kwargs)
     if not isinstance(env.action_space, Discrete):   # discrete_sac_exp_script.py:41
         raise SystemExit(f"discrete SAC needs a Discrete action space; {variant['env_specs']['env_name']} has {type(env.action_space).__name__}")
     obs_dim, action_dim = training_env.obs_dim, env.action_space.n

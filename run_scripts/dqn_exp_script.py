@@ -8,7 +8,7 @@ run_experiment.py --group) and split runs (rl_alg_params.split_ranks > 1) are re
 import argparse
 
 import yaml
-from _common import flatten_spec, ia, main, make_envs, split_ranks_of, start, train  # noqa: F401
+from _common import flatten_spec, ia, main, make_envs, split_ranks_of, start, train, vec_env_kwargs_of  # noqa: F401
 
 from ilswiss_amd.algorithm import DeviceRLAlgorithm
 from ilswiss_amd.envs.vecenv import Discrete
@@ -17,8 +17,9 @@ from ilswiss_amd.envs.vecenv import Discrete
 def experiment(variant, gpu=0, log_dir=None):
     if split_ranks_of(variant):
         raise SystemExit("DQN: rl_alg_params.split_ranks > 1 is not supported (no split DQN step)")
+    vec_kwargs = vec_env_kwargs_of(variant)   # env_specs.vec_env_kwargs: norm_obs / update_obs_rms
     ctx = start(variant, gpu)
-    training_env, eval_env, env = make_envs(variant, ctx)
+    training_env, eval_env, env = make_envs(variant, ctx, **vec_kwargs)
     if not isinstance(env.action_space, Discrete):
         raise SystemExit(f"DQN needs a Discrete action space; {variant['env_specs']['env_name']} has {type(env.action_space).__name__}")
     hid = variant["num_hidden_layers"] * [variant["net_size"]]

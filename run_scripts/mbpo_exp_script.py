@@ -5,7 +5,7 @@ seed / exp_name / exp_id (load_params resumes).  The planar tasks (hopper, walke
 tasks of the reference's Ant / Humanoid specs (ant_trunc_obs, humanoid_trunc_obs: qpos[2:] | qvel), at any BNN width up to 400.
 Plain `ant` / `humanoid` are refused: the terminal predicates are written for the truncated layout, and a model over the 111- /
 376-wide observations is not wanted."""
-from _common import flatten_spec, ia, main, make_envs, start, train  # noqa: F401
+from _common import flatten_spec, ia, main, make_envs, start, train, vec_env_kwargs_of  # noqa: F401
 
 from ilswiss_amd.envs.terminals import get_terminal_func
 from ilswiss_amd.mbpo import BNN, MBPO, BNNTrainer
@@ -20,8 +20,9 @@ def experiment(variant, gpu=0, log_dir=None):
     if name not in TERMINALS:
         hint = f" (use {name}_trunc_obs, the task the reference's MBPO spec names)" if name in ("ant", "humanoid") else ""
         raise NotImplementedError(f"MBPO on env_name={name!r}: the device model rollout covers {sorted(TERMINALS)}{hint}")
+    vec_kwargs = vec_env_kwargs_of(variant, "MBPO", "its device termination predicates and model rollouts read observation columns as raw quantities")
     ctx = start(variant, gpu)
-    training_env, eval_env, env = make_envs(variant, ctx)
+    training_env, eval_env, env = make_envs(variant, ctx, **vec_kwargs)
     obs_dim, action_dim = training_env.obs_dim, training_env.act_dim
     sac_params = dict(variant["sac_params"])
     net_size, num_hidden = sac_params.pop("net_size"), sac_params.pop("num_hidden_layers")

@@ -4,14 +4,15 @@ run_scripts/sac_alpha_exp_script.py:25-156: `python run_scripts/sac_alpha_exp_sc
 variant keys env_specs / net_size / num_hidden_layers / sac_params / rl_alg_params / seed / exp_name / exp_id.
 Accepts either a flat variant (what run_experiment.py writes per grid point) or a full exp_spec with
 meta_data / variables / constants (the first grid point is taken)."""
-from _common import flatten_spec, ia, main, make_envs, split_info, start, train  # noqa: F401
+from _common import flatten_spec, ia, main, make_envs, split_info, start, train, vec_env_kwargs_of  # noqa: F401
 
 from ilswiss_amd.algorithm import DeviceRLAlgorithm
 
 
 def experiment(variant, gpu=0, log_dir=None):
+    vec_kwargs = vec_env_kwargs_of(variant)   # env_specs.vec_env_kwargs: norm_obs / update_obs_rms (refusals come before the device is opened)
     ctx = start(variant, gpu)
-    training_env, eval_env, env = make_envs(variant, ctx)
+    training_env, eval_env, env = make_envs(variant, ctx, **vec_kwargs)
     obs_dim, action_dim = training_env.obs_dim, training_env.act_dim
     net_size, num_hidden = variant["net_size"], variant["num_hidden_layers"]
     qf1 = ia.FlattenMlp(hidden_sizes=num_hidden * [net_size], input_size=obs_dim + action_dim, output_size=1, ctx=ctx)
