@@ -14,6 +14,7 @@
 #include "../../include/ilsx.h"
 #include "dev_owner.h"
 #include "kernels.h"
+#include "switches.h"
 
 #define ILSX_FAIL(code, ...)   \
   do {                         \
@@ -67,6 +68,11 @@ struct ilsx_ctx {
   uint64_t prof_n[ILSX_K_COUNT] = {0};
   const char* prof_name[ILSX_K_COUNT] = {nullptr};   // source spelling of the kernel last launched under each slot
 };
+// Is this a split run (gradient all-reduce between backward and the optimiser step)?  cfg.grad_world > 1 — or, for tests, ILSX_SPLIT_FORCE on a
+// context that carries a communicator: one rank then takes the split-run code path.  run_split_forced_ok: such a stand-in communicator of one
+// rank also serves an object configured for more (its arena holds this rank's share).
+inline bool run_is_split(const ilsx_ctx* c, int grad_world) { return grad_world > 1 || (c->comm != nullptr && sw::ILSX_SPLIT_FORCE()); }
+inline bool run_split_forced_ok(const ilsx_ctx* c) { return c->comm && c->comm_n == 1 && sw::ILSX_SPLIT_FORCE(); }
 
 // RAII bracket around ONE kernel launch.  When profiling, the launch goes through hipExtLaunchKernelGGL, which stamps the two
 // events with the dispatch's own begin / end timestamps (what rocprofv3's kernel trace reports) instead of bracketing it

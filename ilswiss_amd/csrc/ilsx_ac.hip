@@ -84,7 +84,7 @@ static int ac_init(AcAgent* g, ilsx_ctx* ctx, ilsx_net* const* nets, int nnets, 
   g->ctx = g->own.ctx = ctx; g->nnets = nnets; g->max_batch = max_batch; g->o = o; g->a = a;
   const ilsx_mlp_cfg& c0 = nets[0]->lay.cfg;
   g->H = c0.hidden; g->act = c0.act;
-  g->cs = getenv("ILSX_NO_SPLIT") ? 1 : mlp2_split_factor(c0.n_hidden, c0.hidden);
+  g->cs = sw::ILSX_NO_SPLIT() ? 1 : mlp2_split_factor(c0.n_hidden, c0.hidden);
   for (int i = 0; i < nnets; ++i) {
     const ilsx_mlp_cfg& c = nets[i]->lay.cfg;
     if (nets[i]->ctx != ctx) ILSX_FAIL(ILSX_ERR_ARG, "a network belongs to another ctx");

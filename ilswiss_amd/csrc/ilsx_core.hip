@@ -70,9 +70,9 @@ extern "C" int ilsx_ctx_create(int hip_device, void* hip_stream, uint64_t seed, 
   ilsx_ctx* c = new ilsx_ctx();
   c->device = hip_device;
   c->seed = seed;
-  if (const char* e = getenv("ILSX_XCD_SHIFT")) c->xcd_shift = atoi(e);
-  if (const char* e = getenv("ILSX_RT")) c->rt_single = std::max(1, atoi(e));
-  if (const char* e = getenv("ILSX_RT_GROUPED")) c->rt_grouped = std::max(1, atoi(e));
+  c->xcd_shift = sw::ILSX_XCD_SHIFT();
+  c->rt_single = std::max(1, sw::ILSX_RT());
+  c->rt_grouped = std::max(1, sw::ILSX_RT_GROUPED());
   if (hip_stream) {
     c->stream = (hipStream_t)hip_stream;
   } else {
@@ -508,16 +508,14 @@ bool phase_fits(ilsx_ctx* ctx, int rows, int H, int cs, int ntasks, bool own_row
 // compiler that takes the kernel past 256 registers costs this mapping, not the phase path).  ILSX_PHASE_OWN_ROWS=0 keeps them on the
 // workgroups of the policy rows; read per call, as ILSX_NO_PHASE is: tests switch it.
 bool phase_own_rows(ilsx_ctx* ctx, int rows, int H, int cs, int ntasks) {
-  const char* e = getenv("ILSX_PHASE_OWN_ROWS");
-  return !(e && atoi(e) == 0) && phase_fits(ctx, rows, H, cs, ntasks, true);
+  return sw::ILSX_PHASE_OWN_ROWS() && phase_fits(ctx, rows, H, cs, ntasks, true);
 }
 
 // ---- the phase kernels' descriptor blocks in constant memory (kernels.h g_phase_a_tab / g_phase_c_tab)
 static std::vector<bool> g_phase_slots[16];   // [device][slot] in use
 static std::mutex g_phase_slots_mu;           // agents are built and destroyed from more than one host thread (grouped runs, evaluation threads)
 int phase_const_alloc(int device) {
-  static const bool off = []() { const char* e = getenv("ILSX_PHASE_CT"); return e && atoi(e) == 0; }();
-  if (off || device < 0 || device >= 16) return -1;
+  if (!sw::ILSX_PHASE_CT() || device < 0 || device >= 16) return -1;
   std::lock_guard<std::mutex> lock(g_phase_slots_mu);
   auto& u = g_phase_slots[device];
   if (u.empty()) u.assign(PHASE_CONST_SLOTS, false);
@@ -624,8 +622,7 @@ int launch_phase_a(ilsx_ctx* ctx, const PhaseAArgs& P0, int H, int act, int KPma
   const bool use_ct = ct && phase_const_ready(ctx, ct, P, key, ct->a, ct->valid_a, ct->key_a, HIP_SYMBOL(g_phase_a_tab));
   if (upload_only) return ILSX_OK;
   const int slot = use_ct ? ct->slot : 0;
-  static const bool trace = getenv("ILSX_PHASE_CT_TRACE") != nullptr;
-  if (trace) { hipStreamCaptureStatus cap = hipStreamCaptureStatusNone; hipStreamIsCapturing(ctx->stream, &cap);
+  if (sw::ILSX_PHASE_CT_TRACE()) { hipStreamCaptureStatus cap = hipStreamCaptureStatusNone; hipStreamIsCapturing(ctx->stream, &cap);
                fprintf(stderr, "launch_phase_a: %s, slot %d, capturing %d\n", use_ct ? "constant table" : "kernel arguments", ct ? ct->slot : -9, (int)cap); }
   ProfScope ps(ctx, ILSX_K_SAC_PHASE_A);
 #define PHASE_A(HH, AA, CC) do { if (use_ct) ILSX_LAUNCH(ps, (k_sac_phase_a<HH, AA, CC, true>), grid, block, lds, ctx->stream, P, slot); \
@@ -739,8 +736,7 @@ int launch_bwd_dw(ilsx_ctx* ctx, DevOwner& owner, const DwArgs& table, int rows,
   if (rows >= DW_SPLIT_MIN_ROWS && D.g_lo && !stacked) {   // large batch: split the contraction over row ranges
     // >= DW_BIG_MIN_ROWS rows: the LDS-staged 128 x 128 block kernel (k_dw_big), row ranges of >= 512 rows, up to 64 of them (its heavy
     // blocks — the hidden -> hidden matrix — are 4 per range: 256 of them fill the chip).  ILSX_DW_BIG = 0 keeps the tile kernel (A/B, tests)
-    static const int big_env = []() { const char* e = getenv("ILSX_DW_BIG"); return e ? atoi(e) : 1; }();
-    const bool big = big_env && rows >= DW_BIG_MIN_ROWS;
+    const bool big = sw::ILSX_DW_BIG() && rows >= DW_BIG_MIN_ROWS;
     int splits, rps;
     dw_split_plan(rows, big, &splits, &rps);
     const size_t span = (size_t)(D.g_hi - D.g_lo);
@@ -778,8 +774,7 @@ int launch_bwd_dw(ilsx_ctx* ctx, DevOwner& owner, const DwArgs& table, int rows,
   if (D.gtiles) {
     const int gnh = D.tile_nh ? D.tile_nh : 2, gkt = D.tile_kt ? D.tile_kt : 4;
     // two 16-wave workgroups per CU (the <= 64-register instance) once the launch has more tiles than CUs: ILSX_DW_GRP_LOW = 0 / 1 pins it
-    const char* low_e = getenv("ILSX_DW_GRP_LOW");   // read per launch: tests switch it
-    const int low_env = low_e ? atoi(low_e) : -1;
+    const int low_env = sw::ILSX_DW_GRP_LOW();   // read per launch: tests switch it
     const bool low = low_env >= 0 ? low_env != 0 : D.ntiles > device_cus(ctx);
     if (gnh == 2 && gkt == 4 && low) ILSX_LAUNCH(ps, (k_mlp_bwd_dw_low<true, 2, 4>), dim3(D.ntiles << D.xs), dim3(1024), DW_LDS_BYTES_OF(2, 4), ctx->stream, D);
     else if (gnh == 2 && gkt == 4) ILSX_LAUNCH(ps, (k_mlp_bwd_dw<true, 2, 4>), dim3(D.ntiles << D.xs), dim3(1024), DW_LDS_BYTES_OF(2, 4), ctx->stream, D);
@@ -790,8 +785,7 @@ int launch_bwd_dw(ilsx_ctx* ctx, DevOwner& owner, const DwArgs& table, int rows,
     // small batches (one 256-row trip per wave): the table's 32 x 64 tiles are a few dozen 16-wave workgroups, each CU's 4 waves per
     // SIMD then share one MFMA pipe and one issue port while most of the chip idles; smaller tiles give the same waves (same
     // arithmetic, same order) to more CUs
-    const char* shape_env = getenv("ILSX_DW_TILE");   // "NH KT" digits (24, 12, 11); unset / 0 = by size.  Read per launch: tests switch it
-    const int shape = shape_env ? atoi(shape_env) : 0;
+    const int shape = sw::ILSX_DW_TILE();   // "NH KT" digits (24, 12, 11); unset / 0 = by size.  Read per launch: tests switch it
     int nh = 2, kt = 4;
     auto retile = [&](int nh_, int kt_) {
       D.ntiles = 0;

@@ -421,7 +421,7 @@ static int disc_setup_mlp(ilsx_disc* d) {
   const ilsx_disc_cfg* cfg = &d->cfg;
   ilsx_mlp_cfg mc = {d->D, d->nblk, cfg->hid_dim, 1, 1, cfg->hid_act};
   ILSX_TRY(net_layout_build(mc, &d->L));
-  d->cs = (getenv("ILSX_NO_SPLIT") || d->nblk != 2) ? 1 : mlp2_split_factor(2, cfg->hid_dim);
+  d->cs = (sw::ILSX_NO_SPLIT() || d->nblk != 2) ? 1 : mlp2_split_factor(2, cfg->hid_dim);
   d->rng_stream = d->ctx->next_rng_stream++;
   const size_t n = d->L.n_int, B = (size_t)cfg->max_batch, H = (size_t)cfg->hid_dim, KP = (size_t)d->L.KP;
   auto A = [&](float** p, size_t cnt) { return d->own.alloc(p, cnt); };
@@ -652,9 +652,7 @@ __global__ void k_disc_inj_layer(const float* __restrict__ Wnext, int H, const f
 // Weight gradients + Adam(lr, betas = (disc_momentum, 0.999)).  One rank: Adam in the epilogue of the weight-gradient tiles (kernels.h AdamFuse:
 // same expressions as k_adam_polyak, one launch and one pass over the arena less).  Split run (cfg.grad_world = G, SURVEY section 8e "Disc: same"):
 // backward | all-reduce(gradient arena) | Adam as a launch of its own.  ILSX_SPLIT_FORCE=1 (tests): the split path on a one-rank communicator.
-static bool disc_is_split(const ilsx_disc* d) {
-  return d->cfg.grad_world > 1 || (d->ctx->comm != nullptr && getenv("ILSX_SPLIT_FORCE") != nullptr);
-}
+static bool disc_is_split(const ilsx_disc* d) { return run_is_split(d->ctx, d->cfg.grad_world); }
 static int disc_dw_adam(ilsx_disc* d, int rows) {
   ilsx_ctx* ctx = d->ctx;
   AdamFuse F;
@@ -664,7 +662,7 @@ static int disc_dw_adam(ilsx_disc* d, int rows) {
   F.step_size = &d->scal->adam_step; F.bc2_sqrt = &d->scal->adam_bc2s;
   if (!disc_is_split(d)) return launch_bwd_dw(ctx, d->own, d->jobs, rows, &F);
   if (d->cfg.grad_world > 1 && (!ctx->comm || ctx->comm_n != d->cfg.grad_world) &&
-      !(ctx->comm && ctx->comm_n == 1 && getenv("ILSX_SPLIT_FORCE")))   // (tests: a one-rank communicator stands in, the arena holds this rank's share)
+      !run_split_forced_ok(ctx))   // (tests: a one-rank communicator stands in, the arena holds this rank's share)
     ILSX_FAIL(ILSX_ERR_STATE, "discriminator step: grad_world=%d needs a communicator of that many ranks on the ctx (ilsx_comm_init; found %d)",
               d->cfg.grad_world, ctx->comm ? ctx->comm_n : 0);
   ILSX_TRY(launch_bwd_dw(ctx, d->own, d->jobs, rows, nullptr));
@@ -893,7 +891,7 @@ extern "C" int ilsx_advirl_train(ilsx_disc* d, ilsx_sac* sac, ilsx_replay* exper
                                  ilsx_sac_stats* sac_stats, float* rew_stats4) {
   if (!d || !sac || !expert_rb || !policy_rb || loops < 0) ILSX_FAIL(ILSX_ERR_ARG, "ilsx_advirl_train: bad argument");
   HIPCHK(hipSetDevice(d->ctx->device));
-  static const bool no_window = getenv("ILSX_ADVIRL_NO_WINDOW") != nullptr;
+  const bool no_window = sw::ILSX_ADVIRL_NO_WINDOW();
   const bool checkpoint = !no_window && !d->bn && policy_batch >= 1 && sac_window_may_use_phase(sac, policy_batch);
   const size_t n = d->L.n_int;
   const unsigned long long c_e = expert_rb->sample_ctr, c_p = policy_rb->sample_ctr, c_d = d->step_ctr;
@@ -935,8 +933,7 @@ static int advirl_train_once(ilsx_disc* d, ilsx_sac* sac, ilsx_replay* expert_rb
   if (expert_rb->o != o || policy_rb->o != o || expert_rb->a != a || (!so && a != d->cfg.act_dim))
     ILSX_FAIL(ILSX_ERR_ARG, "replay dims do not match the discriminator");
   bool first_disc = true, first_pol = true, in_window = false;
-  static const bool no_window_env = getenv("ILSX_ADVIRL_NO_WINDOW") != nullptr;
-  const bool no_window = no_window_env || d->bn != nullptr;   // (the BatchNorm discriminator's state is not part of the window checkpoint)
+  const bool no_window = sw::ILSX_ADVIRL_NO_WINDOW() || d->bn != nullptr;   // (the BatchNorm discriminator's state is not part of the window checkpoint)
   struct WindowGuard { ilsx_sac* s; bool* on; ~WindowGuard() { if (*on) sac_window_end(s, /*teardown=*/true); } } window_guard{sac, &in_window};   // error paths
   for (int it = 0; it < loops; ++it) {
     for (int k = 0; k < disc_updates; ++k) {   // adv_irl.py:133-216

@@ -1377,8 +1377,7 @@ extern "C" int ilsx_rollout_step_end(ilsx_vecenv* e) {
 // Can the K runs' steps go out as ONE launch per stage?  Planar steppers of one kernel instantiation with the same env count, plain
 // observations, policies of one shape (the generic forward takes up to four tasks per launch), everything on one device.
 static bool rollout_runs_groupable(ilsx_vecenv* const* envs, ilsx_net* const* pis, int n_runs) {
-  static const bool off = getenv("ILSX_ROLLOUT_NO_GROUP") != nullptr;
-  if (off || n_runs < 2) return false;
+  if (sw::ILSX_ROLLOUT_NO_GROUP() || n_runs < 2) return false;
   const ilsx_vecenv* e0 = envs[0];
   const ilsx_net* p0 = pis[0];
   if (e0->engine != 0 || e0->ctx->prof_on) return false;

@@ -462,12 +462,10 @@ extern "C" int ilsx_ppo_gae(ilsx_ppo* p, const float* obs, const float* act, con
 
 // Split run (cfg.grad_world = G > 1): see ilsx_ppo_cfg.  ILSX_SPLIT_FORCE=1 (tests): an agent with grad_world = 1 whose ctx carries a one-rank
 // communicator takes the split-run code path — dW without the fused optimiser, all-reduce, Adam as launches of their own.
-static bool ppo_is_split(const ilsx_ppo* p) {
-  return p->cfg.grad_world > 1 || (p->ctx->comm != nullptr && getenv("ILSX_SPLIT_FORCE") != nullptr);
-}
+static bool ppo_is_split(const ilsx_ppo* p) { return run_is_split(p->ctx, p->cfg.grad_world); }
 static int ppo_check_world(const ilsx_ppo* p) {
   if (p->cfg.grad_world == 1) return ILSX_OK;
-  if (p->ctx->comm && p->ctx->comm_n == 1 && getenv("ILSX_SPLIT_FORCE")) return ILSX_OK;   // tests: a one-rank communicator stands in, the arena holds this rank's share
+  if (run_split_forced_ok(p->ctx)) return ILSX_OK;   // tests: a one-rank communicator stands in, the arena holds this rank's share
   if (!p->ctx->comm || p->ctx->comm_n != p->cfg.grad_world)
     ILSX_FAIL(ILSX_ERR_STATE, "ilsx_ppo_train: grad_world=%d needs a communicator of that many ranks on the ctx (ilsx_comm_init; found %d)",
               p->cfg.grad_world, p->ctx->comm ? p->ctx->comm_n : 0);

@@ -483,7 +483,7 @@ extern "C" int ilsx_replay_sample_many(ilsx_replay* rb, int n_batches, int B, fl
   ProfScope ps(rb->ctx, ILSX_K_REPLAY_SAMPLE_MANY);
   // non-temporal output stores (written once, read by whoever consumes the batch later: keeps the ring, not the output, in the L2 / Infinity
   // Cache) — measured 41.3 -> 39.7 us (Hopper records), 86.1 -> 77.0 us (Walker2d); ILSX_REPLAY_NT=0 for A/B
-  static const bool nt = []() { const char* e = getenv("ILSX_REPLAY_NT"); return !e || atoi(e) != 0; }();
+  const bool nt = sw::ILSX_REPLAY_NT();
 #define SM_LAUNCH(R4, N) ILSX_LAUNCH(ps, (k_replay_sample_many<R4, N>), dim3((unsigned)blocks), dim3(256), 0, rb->ctx->stream, (const float4*)rb->data, \
                                      rec4, rb->dstate, rb->seed, rb->rng_stream, rb->sample_ctr + 1, B, rows, (float4*)out_records)
   if (rec4 == 8) { if (nt) SM_LAUNCH(8, true); else SM_LAUNCH(8, false); }

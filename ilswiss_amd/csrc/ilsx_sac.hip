@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include "host_common.h"
+#include "sac_form.h"
 
 enum { W_PI = 0, W_Q1 = 1, W_Q2 = 2, W_TQ1 = 3, W_TQ2 = 4 };
 
@@ -53,7 +54,6 @@ struct SacCollector { std::vector<SacLaunch> L; };
 struct ilsx_sac {
   ilsx_ctx* ctx = nullptr;
   DevOwner own;   // the slab and the lazily allocated records (tail_dev, snap, vote)
-  SacCollector* col = nullptr;
   ilsx_sac_cfg cfg;
   ilsx_net *pi = nullptr, *q1 = nullptr, *q2 = nullptr;
   NetLayout Lq, Lp;
@@ -64,20 +64,18 @@ struct ilsx_sac {
   DevScalars* scal = nullptr;
   SacWs ws;
   DwArgs jobs_q, jobs_p;     // dW tables (critics / policy), passed by value in the kernel arguments
-  ilsx_replay* gather_rb = nullptr;  // train_from_replay: the first forward launch draws its rows from this ring
-  bool fuse_now = false;     // this step applies Adam(+Polyak) inside the dW epilogue (not in split-run phases)
   int cs = 1;                // column-split factor of the 2-hidden-layer fast path (1 = generic kernels)
   float* h0scr = nullptr;    // non-null: two-phase forward for wide inputs (layer 0 in its own launch); [4 tasks][max_batch][H] scratch
   int B = 0;                 // rows of the batch currently staged
   bool eps_explicit = false;
   float target_entropy = 0.f;
   uint32_t rng_stream = 0;
-  // hipGraph cache for train_from_replay
+  // hipGraph cache for train_from_replay: one step of this form on B rows
   hipGraphExec_t graph = nullptr;
-  ilsx_replay* graph_rb = nullptr;
+  SacStepForm graph_form;
   int graph_B = 0;
-  bool graph_defer = false, graph_phase = false, graph_own = false;
-  // deferred tail (TailLite, kernels.h): active inside ilsx_sac_train_from_replay on the column-split path
+  // window state, written by window begin and end only (sac_defer_begin / sac_defer_end, sac_snapshot_take / sac_phase_check): defer_tail,
+  // tail_B, tail_split, snap_valid.  Deferred tail (TailLite, kernels.h): the steps of the open window hand their tail to the next step's first launch
   bool defer_tail = false;
   TailLite* tail_dev = nullptr;
   int tail_B = 0;
@@ -87,12 +85,9 @@ struct ilsx_sac {
   unsigned* phase_flags = nullptr;   // PHASE_NFLAGS arrival counters, one 128-byte line each (zeroed by the dW launches)
   int* phase_err = nullptr;          // set by a workgroup whose wait timed out
   PhaseConst pct;                    // the phase kernels' descriptor blocks in constant memory (host_common.h)
-  bool phase_args_only = false;      // dry pass: build the two blocks, upload them, launch nothing (sac_phase_const_prime)
-  bool phase_now = false;            // this step runs on the phase kernels
   bool phase_broken = false;         // a timeout was seen once: stay on the 8-launch path
   bool phase_last = false;           // the last window of steps ran on the phase kernels
   bool debug_break = false;          // ilsx_sac_debug_break_phase
-  bool phase_check_only = false;     // with phase_args_only: the blocks are only held against what the kernels are compiled for, nothing is uploaded
   int static_heads = -1;             // sac_static_heads_ok: -1 = not yet asked, else its answer
   int phase_fallbacks = 0;           // windows rolled back and re-run (ilsx_sac_phase_state)
   float* vote = nullptr;             // split run: the ranks' agreement on a roll-back (sac_phase_check), one device float
@@ -270,8 +265,7 @@ static void sac_plan_ws(ilsx_sac* s, Slab& L) {
   A(&w.dhp, B * 2 * a);
   // wide inputs (Humanoid: KP = 396 against 16 for the planar tasks): every column slice recomputing layer 0 costs 6x its own layer-1
   // work, so the forward becomes two launches (kernels.h, k_mlp2_fwd_split PH 1 / 2).  ILSX_L0_SPLIT_KP moves the threshold.
-  const char* e = getenv("ILSX_L0_SPLIT_KP");
-  const int thr = e ? atoi(e) : 65;   // KP is a multiple of 16: the planar tasks (KP 16 / 32) keep the one-launch form, Ant (128) and Humanoid (396) do not
+  const int thr = sw::ILSX_L0_SPLIT_KP();   // default 65.  KP is a multiple of 16: the planar tasks (KP 16 / 32) keep the one-launch form, Ant (128) and Humanoid (396) do not
   if (s->cs == 4 && H == 256 && std::max(s->Lq.KP, s->Lp.KP) >= thr) A(&s->h0scr, 4 * B * H);
 }
 
@@ -330,7 +324,7 @@ extern "C" int ilsx_sac_create(ilsx_ctx* ctx, const ilsx_sac_cfg* cfg, ilsx_net*
   s->Lq = q1->lay; s->Lp = pi->lay;
   s->o = cp.in_dim; s->a = cp.out_dim;
   s->nq = s->Lq.n_int; s->np = s->Lp.n_int;
-  s->cs = getenv("ILSX_NO_SPLIT") ? 1 : mlp2_split_factor(cp.n_hidden, cp.hidden);
+  s->cs = sw::ILSX_NO_SPLIT() ? 1 : mlp2_split_factor(cp.n_hidden, cp.hidden);
   s->target_entropy = cfg->has_target_entropy ? cfg->target_entropy : -(float)s->a / 2.0f;  // sac_alpha.py:56-58
   s->rng_stream = ctx->next_rng_stream;
   ctx->next_rng_stream += 2;
@@ -410,53 +404,55 @@ static void sac_q_task(ilsx_sac* s, FwdTask& q, int which, const float* obs, con
   if (s->cs > 1) q.part = out; else q.out = out;
 }
 
-static int sac_fwd(ilsx_sac* s, const FwdArgs& A0, int H, int act, int KP, int cs) {
+static int sac_fwd(ilsx_sac* s, SacCollector* col, const FwdArgs& A0, int H, int act, int KP, int cs) {
   FwdArgs A = A0;
   if (s->h0scr) {   // wide inputs: two-phase forward (k_mlp2_fwd_split PH 1 / 2); tasks that do not save layer 0 get scratch for it
     A.l0_split = 1;
     for (int t = 0; t < A.ntasks; ++t)
       if (!A.t[t].hsave[0]) A.t[t].hsave[0] = s->h0scr + (size_t)t * s->cfg.max_batch * H;
   }
-  if (!s->col) return launch_fwd(s->ctx, A, H, act, KP, cs);
+  if (!col) return launch_fwd(s->ctx, A, H, act, KP, cs);
   SacLaunch l; memset(&l, 0, sizeof l); l.kind = 0; l.f = A; l.KP = KP;
-  s->col->L.push_back(l);
+  col->L.push_back(l);
   return ILSX_OK;
 }
-static int sac_bwd(ilsx_sac* s, const BwdArgs& A, int H, int act, int cs) {
-  if (!s->col) return launch_bwd_dx(s->ctx, A, H, act, cs);
+static int sac_bwd(ilsx_sac* s, SacCollector* col, const BwdArgs& A, int H, int act, int cs) {
+  if (!col) return launch_bwd_dx(s->ctx, A, H, act, cs);
   SacLaunch l; memset(&l, 0, sizeof l); l.kind = 1; l.b = A;
-  s->col->L.push_back(l);
+  col->L.push_back(l);
   return ILSX_OK;
 }
-static int sac_dw(ilsx_sac* s, const DwArgs& table, int rows, const AdamFuse* F) {
-  if (!s->col) return launch_bwd_dw(s->ctx, s->own, table, rows, F);
+static int sac_dw(ilsx_sac* s, SacCollector* col, const DwArgs& table, int rows, const AdamFuse* F) {
+  if (!col) return launch_bwd_dw(s->ctx, s->own, table, rows, F);
   SacLaunch l; memset(&l, 0, sizeof l); l.kind = 2; l.d = table; l.F = *F;
-  s->col->L.push_back(l);
+  col->L.push_back(l);
   return ILSX_OK;
 }
 
 // What the phase launches' descriptor blocks are built from besides the agent's fixed allocations: the ring they draw from, the batch, and the
-// step-form flags.  Two builds under the same key give the same blocks (PhaseConst::key_a / key_c); never 0.
-static bool sac_own_rows(const ilsx_sac* s) { return phase_own_rows(s->ctx, s->B, s->Lq.cfg.hidden, s->cs, 4); }   // phase A's mapping for the step being built
-static unsigned long long sac_phase_key(const ilsx_sac* s) {
+// step's form.  Two builds under the same key give the same blocks (PhaseConst::key_a / key_c); never 0.
+static unsigned long long sac_phase_key(const ilsx_sac* s, const SacStepForm& f) {
   unsigned long long k = 1469598103934665603ull;
   auto mix = [&k](unsigned long long v) { k = (k ^ v) * 1099511628211ull; };
-  const ilsx_replay* rb = s->gather_rb;
+  const ilsx_replay* rb = f.ring;
   mix((unsigned long long)(uintptr_t)rb); mix(rb ? (unsigned long long)(uintptr_t)rb->data : 0); mix(rb ? (unsigned long long)(uintptr_t)rb->dstate : 0);
   mix(rb ? (unsigned long long)rb->rec : 0); mix(rb ? (unsigned long long)rb->seed : 0); mix(rb ? (unsigned long long)rb->rng_stream : 0);
-  mix((unsigned long long)s->B); mix(s->defer_tail ? 1 : 0); mix(s->eps_explicit ? 1 : 0); mix(s->fuse_now ? 1 : 0); mix((unsigned long long)s->cs);
+  mix((unsigned long long)s->B); mix(f.defer_tail ? 1 : 0); mix(s->eps_explicit ? 1 : 0); mix(f.fuse ? 1 : 0); mix((unsigned long long)s->cs);
   mix((unsigned long long)(uintptr_t)s->tail_dev); mix((unsigned long long)(uintptr_t)s->slab);
-  mix(sac_own_rows(s) ? 1 : 0);
+  mix(f.own_rows ? 1 : 0);
   return k ? k : 1;
 }
 
-static int sac_critic_backward(ilsx_sac* s) {
+// explicit noise belongs to the staged batch; the check asks about the agent's descriptors, whatever batch happens to be staged
+static bool sac_eps_explicit(const ilsx_sac* s, const SacStepForm& f) { return s->eps_explicit && f.mode != SAC_FORM_CHECK; }
+
+static int sac_critic_backward(ilsx_sac* s, const SacStepForm& f) {
   const SacWs& w = s->ws;
   const int B = s->B, H = s->Lq.cfg.hidden, act = s->Lq.cfg.act, cs = s->cs;
-  const float* eps1 = s->eps_explicit ? w.eps1 : nullptr;
-  const float* eps2 = s->eps_explicit ? w.eps2 : nullptr;
+  const float* eps1 = sac_eps_explicit(s, f) ? w.eps1 : nullptr;
+  const float* eps2 = sac_eps_explicit(s, f) ? w.eps2 : nullptr;
   PhaseAArgs PA;
-  if (s->phase_now) memset(&PA, 0, sizeof PA);
+  if (f.phase) memset(&PA, 0, sizeof PA);
   {  // fwd: pi(s') with eps_next ; Q1(s,a) ; Q2(s,a) ; pi(s) with eps_cur (its weights do not change before the actor
      // phase reads it, so its trunk rides along here and one dependent launch disappears from the step)
     FwdArgs A;
@@ -466,8 +462,8 @@ static int sac_critic_backward(ilsx_sac* s) {
     sac_policy_task(s, A.t[3], w.s, eps2, s->rng_stream + 1, true, w.an, w.logp, w.ppart2);
     sac_q_task(s, A.t[1], W_Q1, w.s, w.a, w.q1, true, true, 0);
     sac_q_task(s, A.t[2], W_Q2, w.s, w.a, w.q2, true, true, 1);
-    if (s->gather_rb && cs > 1) {  // fused sample+index: rows are drawn from the ring inside this launch
-      ilsx_replay* rb = s->gather_rb;
+    if (f.ring && cs > 1) {  // fused sample+index: rows are drawn from the ring inside this launch
+      ilsx_replay* rb = f.ring;
       GatherSpec& G = A.gather;
       G.records = rb->data; G.st = rb->dstate; G.rec = rb->rec; G.seed = rb->seed; G.stream = rb->rng_stream;
       G.o = s->o; G.adim = s->a; G.on = 1;
@@ -477,9 +473,9 @@ static int sac_critic_backward(ilsx_sac* s) {
       A.t[2].g0_off = 0; A.t[2].g1_off = s->o; A.t[2].publish = 0;
       A.t[3].g0_off = 0; A.t[3].publish = 0;                              // pi reads obs
     }
-    if (s->defer_tail) { A.tail = s->tail_dev; A.tail_mode = 1; A.tail_n = 1; }
-    if (s->phase_now) PA.f1 = A;
-    else ILSX_TRY(sac_fwd(s, A, H, act, std::max(s->Lq.KP, s->Lp.KP), cs));
+    if (f.defer_tail) { A.tail = s->tail_dev; A.tail_mode = 1; A.tail_n = 1; }
+    if (f.phase) PA.f1 = A;
+    else ILSX_TRY(sac_fwd(s, f.col, A, H, act, std::max(s->Lq.KP, s->Lp.KP), cs));
   }
   {  // fwd: TQ1(s',a'), TQ2(s',a')
     FwdArgs A;
@@ -488,8 +484,8 @@ static int sac_critic_backward(ilsx_sac* s) {
     sac_q_task(s, A.t[0], W_TQ1, w.s2, w.a2, w.tq1, false, false, 0);
     sac_q_task(s, A.t[1], W_TQ2, w.s2, w.a2, w.tq2, false, false, 1);
     sac_policy_fin(s, A, eps1, s->rng_stream, false, w.a2, w.logp2, w.ppart);
-    if (s->defer_tail) { A.tail = s->tail_dev; A.tail_mode = 2; A.tail_n = 1; }
-    if (s->phase_now) {
+    if (f.defer_tail) { A.tail = s->tail_dev; A.tail_mode = 2; A.tail_n = 1; }
+    if (f.phase) {
       // stage 2 of the phase launch: next_obs is the copy the policy task of stage 1 published (w.s2, read after the tile's hand-off);
       // pi(s') is finished under the replay-draw counter (== the step counter once the pending tail has run; the tail runs
       // concurrently in this launch)
@@ -497,7 +493,7 @@ static int sac_critic_backward(ilsx_sac* s) {
       A.tail_mode = 0;
       PA.f2 = A;
     } else {
-      ILSX_TRY(sac_fwd(s, A, H, act, s->Lq.KP, cs));
+      ILSX_TRY(sac_fwd(s, f.col, A, H, act, s->Lq.KP, cs));
     }
   }
   {  // bwd_dx with the TD-target loss head
@@ -515,34 +511,34 @@ static int sac_critic_backward(ilsx_sac* s) {
       t.q = s->pv(i == 0 ? w.q1 : w.q2); t.tq1 = s->pv(w.tq1); t.tq2 = s->pv(w.tq2);
       t.logp_next = w.logp2; t.rew = w.r; t.done = w.d;
     }
-    if (s->phase_now) {
+    if (f.phase) {
       PA.b1 = A; PA.flags = s->phase_flags; PA.err = s->phase_err;
-      PA.own_rows = sac_own_rows(s) ? 1 : 0;
+      PA.own_rows = f.own_rows ? 1 : 0;
       {   // pi(s) is finished inside this launch (kernels.h policy_fin_tile): the policy phase starts from finished actions
         FwdArgs Fz;
         memset(&Fz, 0, sizeof Fz);
         sac_policy_fin(s, Fz, eps2, s->rng_stream + 1, true, w.an, w.logp, w.ppart2);
         PA.fin_pi = Fz.fin; PA.fin_pi.use_gather_step = 1; PA.fin_pi_on = 1;
       }
-      ILSX_TRY(launch_phase_a(s->ctx, PA, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, s->phase_check_only ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
-      if (s->phase_args_only) return ILSX_OK;
+      ILSX_TRY(launch_phase_a(s->ctx, PA, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, f.mode == SAC_FORM_CHECK ? nullptr : &s->pct, sac_phase_key(s, f), f.mode != SAC_FORM_LAUNCH));
+      if (f.mode != SAC_FORM_LAUNCH) return ILSX_OK;
     } else {
-      ILSX_TRY(sac_bwd(s, A, H, act, cs));
+      ILSX_TRY(sac_bwd(s, f.col, A, H, act, cs));
     }
   }
   AdamFuse F;
   memset(&F, 0, sizeof F);
-  if (s->fuse_now) {
+  if (f.fuse) {
     F.on = 1; F.Gbase = s->G; F.P = s->P; F.M = s->M; F.V = s->V; F.T = s->base(W_TQ1);
     F.b1 = s->cfg.beta_1; F.b2 = 0.999f; F.eps = 1e-8f; F.tau = s->cfg.soft_target_tau;
     F.step_size = &s->scal->adam_q_step; F.bc2_sqrt = &s->scal->adam_q_bc2s;
-    if (s->phase_now) F.T = nullptr;   // the target update rides in the policy phase launch (PhaseCArgs::polyak_*)
+    if (f.phase) F.T = nullptr;   // the target update rides in the policy phase launch (PhaseCArgs::polyak_*)
   }
-  return sac_dw(s, s->jobs_q, B, &F);
+  return sac_dw(s, f.col, s->jobs_q, B, &F);
 }
 
-static int sac_critic_update(ilsx_sac* s) {
-  if (s->fuse_now) return ILSX_OK;  // already applied by the dW epilogue
+static int sac_critic_update(ilsx_sac* s, const SacStepForm& f) {
+  if (f.fuse) return ILSX_OK;  // already applied by the dW epilogue
   AdamArgs A;
   A.p = s->P; A.g = s->G; A.m = s->M; A.v = s->V; A.tgt = s->base(W_TQ1);
   A.n = (int)(2 * s->nq);
@@ -552,12 +548,12 @@ static int sac_critic_update(ilsx_sac* s) {
 }
 
 static StatsArgs sac_stats_args(ilsx_sac* s);
-static int sac_actor_backward(ilsx_sac* s) {
+static int sac_actor_backward(ilsx_sac* s, const SacStepForm& f) {
   const SacWs& w = s->ws;
   const int B = s->B, H = s->Lq.cfg.hidden, act = s->Lq.cfg.act, cs = s->cs;
-  const float* eps2 = s->eps_explicit ? w.eps2 : nullptr;
+  const float* eps2 = sac_eps_explicit(s, f) ? w.eps2 : nullptr;
   PhaseCArgs PC;
-  if (s->phase_now) memset(&PC, 0, sizeof PC);
+  if (f.phase) memset(&PC, 0, sizeof PC);
   // (pi(s) with eps_cur ran as the 4th task of the step's first forward launch, sac_critic_backward)
   {  // fwd Q1(s,a~), Q2(s,a~) with the just-updated critics (sac_alpha.py:144-146)
     FwdArgs A;
@@ -565,9 +561,9 @@ static int sac_actor_backward(ilsx_sac* s) {
     A.rows = B; A.ntasks = 2; A.seed = s->ctx->seed; A.scal = s->scal; A.part_stride = s->cfg.max_batch;
     sac_q_task(s, A.t[0], W_Q1, w.s, w.an, w.q1n, false, true, 0);
     sac_q_task(s, A.t[1], W_Q2, w.s, w.an, w.q2n, false, true, 1);
-    if (!s->phase_now) sac_policy_fin(s, A, eps2, s->rng_stream + 1, true, w.an, w.logp, w.ppart2);   // phase steps: finished in phase A already
-    if (s->phase_now) { A.tail = s->tail_dev; PC.f3 = A; }   // the extra row of the phase launch advances the replay-draw counter
-    else ILSX_TRY(sac_fwd(s, A, H, act, s->Lq.KP, cs));
+    if (!f.phase) sac_policy_fin(s, A, eps2, s->rng_stream + 1, true, w.an, w.logp, w.ppart2);   // phase steps: finished in phase A already
+    if (f.phase) { A.tail = s->tail_dev; PC.f3 = A; }   // the extra row of the phase launch advances the replay-draw counter
+    else ILSX_TRY(sac_fwd(s, f.col, A, H, act, s->Lq.KP, cs));
   }
   {  // bwd_dx through both critics to the action columns
     BwdArgs A;
@@ -580,8 +576,8 @@ static int sac_actor_backward(ilsx_sac* s) {
       t.loss = LOSS_SAC_ACTORQ; t.which = i; t.q1n = s->pv(w.q1n); t.q2n = s->pv(w.q2n);
       t.dx = w.ga[i]; t.dx_col0 = s->o; t.dx_cols = s->a;
     }
-    if (s->phase_now) PC.b2 = A;
-    else ILSX_TRY(sac_bwd(s, A, H, act, cs));
+    if (f.phase) PC.b2 = A;
+    else ILSX_TRY(sac_bwd(s, f.col, A, H, act, cs));
   }
   {  // bwd_dx of the policy with the tanh-Gaussian loss head
     BwdArgs A;
@@ -595,30 +591,30 @@ static int sac_actor_backward(ilsx_sac* s) {
     t.dhead = w.dhp;
     t.loss = LOSS_SAC_POLICY;
     t.raw = w.raw; t.eps = w.epss; t.action = w.an; t.ga1 = w.ga[0]; t.ga2 = w.ga[1];
-    if (s->phase_now) {
+    if (f.phase) {
       PC.b3 = A; PC.flags = s->phase_flags; PC.err = s->phase_err;
-      if (s->fuse_now) { PC.polyak_T = s->base(W_TQ1); PC.polyak_P = s->base(W_Q1); PC.polyak_n = (int)(2 * s->nq); PC.polyak_tau = s->cfg.soft_target_tau; }
+      if (f.fuse) { PC.polyak_T = s->base(W_TQ1); PC.polyak_P = s->base(W_Q1); PC.polyak_n = (int)(2 * s->nq); PC.polyak_tau = s->cfg.soft_target_tau; }
       else {   // split run: this rank's alpha-gradient partial lands in the arena's slot before the actor all-reduce (the tail is deferred)
         PC.aslot = s->G + 2 * s->nq + s->np; PC.aslot_logp = w.logp; PC.aslot_B = B; PC.aslot_te = s->target_entropy; PC.aslot_invB = sac_inv_B(s);
       }
-      ILSX_TRY(launch_phase_c(s->ctx, PC, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, s->phase_check_only ? nullptr : &s->pct, sac_phase_key(s), s->phase_args_only));
-      if (s->phase_args_only) return ILSX_OK;
+      ILSX_TRY(launch_phase_c(s->ctx, PC, H, act, std::max(s->Lq.KP, s->Lp.KP), cs, f.mode == SAC_FORM_CHECK ? nullptr : &s->pct, sac_phase_key(s, f), f.mode != SAC_FORM_LAUNCH));
+      if (f.mode != SAC_FORM_LAUNCH) return ILSX_OK;
     } else {
-      ILSX_TRY(sac_bwd(s, A, H, act, cs));
+      ILSX_TRY(sac_bwd(s, f.col, A, H, act, cs));
     }
   }
   {
     AdamFuse F;
     memset(&F, 0, sizeof F);
-    if (s->fuse_now) {  // pi has no target network; its arena offset is handled by the job pointers (Gbase = G)
+    if (f.fuse) {  // pi has no target network; its arena offset is handled by the job pointers (Gbase = G)
       F.on = 1; F.Gbase = s->G; F.P = s->P; F.M = s->M; F.V = s->V; F.T = nullptr;
       F.b1 = s->cfg.beta_1; F.b2 = 0.999f; F.eps = 1e-8f; F.tau = 0.f;
       F.step_size = &s->scal->adam_pi_step; F.bc2_sqrt = &s->scal->adam_pi_bc2s;
     }
-    ILSX_TRY(sac_dw(s, s->jobs_p, B, &F));
+    ILSX_TRY(sac_dw(s, f.col, s->jobs_p, B, &F));
   }
-  if (s->fuse_now) return ILSX_OK;  // stats run inside k_sac_tail (sac_actor_update)
-  if (s->phase_now && s->defer_tail) return ILSX_OK;   // split run on the phase kernels: the slot came from phase C, statistics from the flushed tail
+  if (f.fuse) return ILSX_OK;  // stats run inside k_sac_tail (sac_actor_update)
+  if (f.phase && f.defer_tail) return ILSX_OK;   // split run on the phase kernels: the slot came from phase C, statistics from the flushed tail
   StatsArgs S = sac_stats_args(s);
   ProfScope ps(s->ctx, ILSX_K_SAC_STATS);
   ILSX_LAUNCH(ps, k_sac_stats, dim3(1), dim3(256), 0, s->ctx->stream, S);
@@ -642,22 +638,22 @@ static StatsArgs sac_stats_args(ilsx_sac* s) {
   return S;
 }
 
-static int sac_actor_update(ilsx_sac* s) {
+static int sac_actor_update(ilsx_sac* s, const SacStepForm& f) {
   AdamArgs A;
   const size_t off = 2 * s->nq;
   A.p = s->P + off; A.g = s->G + off; A.m = s->M + off; A.v = s->V + off; A.tgt = nullptr;
   A.n = (int)s->np;
   A.b1 = s->cfg.beta_1; A.b2 = 0.999f; A.eps = 1e-8f; A.tau = 0.f;
   A.step_size = &s->scal->adam_pi_step; A.bc2_sqrt = &s->scal->adam_pi_bc2s;
-  if (s->fuse_now && s->col) {
+  if (f.fuse && f.col) {
     SacLaunch l; memset(&l, 0, sizeof l); l.kind = 3;
     l.t.S = sac_stats_args(s); l.t.train_alpha = s->cfg.train_alpha; l.t.lr = s->cfg.alpha_lr; l.t.b1 = s->cfg.beta_1;
     l.t.b2 = 0.999f; l.t.eps = 1e-8f; l.t.qf_lr = s->cfg.qf_lr; l.t.policy_lr = s->cfg.policy_lr;
-    s->col->L.push_back(l);
+    f.col->L.push_back(l);
     return ILSX_OK;
   }
-  if (s->fuse_now && s->defer_tail) return ILSX_OK;   // the next step's first launch (or sac_flush_tail) runs it
-  if (s->fuse_now) {
+  if (f.fuse && f.defer_tail) return ILSX_OK;   // the next step's first launch (or sac_flush_tail) runs it
+  if (f.fuse) {
     ProfScope ps(s->ctx, ILSX_K_SAC_FINISH);
     ILSX_LAUNCH(ps, k_sac_tail, dim3(1), dim3(256), 0, s->ctx->stream, sac_stats_args(s), s->cfg.train_alpha,
                        s->cfg.alpha_lr, s->cfg.beta_1, 0.999f, 1e-8f, s->cfg.qf_lr, s->cfg.policy_lr, /*deferred=*/0);
@@ -665,7 +661,7 @@ static int sac_actor_update(ilsx_sac* s) {
     return ILSX_OK;
   }
   ILSX_TRY(launch_adam(s->ctx, A));
-  if (s->phase_now && s->defer_tail) return ILSX_OK;   // split run on the phase kernels: the next step's phase A (or sac_flush_tail) finishes
+  if (f.phase && f.defer_tail) return ILSX_OK;   // split run on the phase kernels: the next step's phase A (or sac_flush_tail) finishes
   ProfScope ps(s->ctx, ILSX_K_SAC_FINISH);
   ILSX_LAUNCH(ps, k_sac_finish, dim3(1), dim3(1), 0, s->ctx->stream, s->scal, (const float*)(s->G + 2 * s->nq + s->np),
                      s->cfg.train_alpha, s->cfg.alpha_lr, s->cfg.beta_1, 0.999f, 1e-8f, s->cfg.qf_lr, s->cfg.policy_lr);
@@ -680,10 +676,50 @@ static int sac_refresh_adam(ilsx_sac* s) {
   return ILSX_OK;
 }
 
+// Split run (cfg.grad_world = G > 1, SURVEY §8e): this rank holds B/G rows; the gradient arena is summed over the ranks between
+// backward and the optimiser step with RCCL on the ctx stream (segment 0 = critics, 1 = actor | alpha slot: two messages
+// because the actor loss is evaluated with the post-update critics, sac_alpha.py:142-146).
+// ILSX_SPLIT_FORCE=1 (tests): a run with grad_world = 1 whose ctx carries a one-rank communicator takes the split-run code path
+// too — un-fused phases with ncclAllReduce between them — so the collective plumbing is exercised on a single-GPU box.
+static bool sac_is_split(const ilsx_sac* s) { return run_is_split(s->ctx, s->cfg.grad_world); }
+
+// The phase kernels' descriptors must be what the kernels are compiled for (static heads: loss kind per stage, one head output per critic,
+// slab counts, the tanh-Gaussian epilogue with one element per thread, no explicit noise).  Asked once per agent, of the blocks themselves: a
+// pass in check mode builds them as a step would and launch_phase_a / _c hold them against phase_a_static_ok / phase_c_static_ok.  An agent
+// whose blocks are refused stays on one launch per stage.
+static bool sac_static_heads_ok(ilsx_sac* s) {
+  if (s->static_heads < 0) {
+    SacStepForm f;
+    f.phase = true; f.fuse = !sac_is_split(s); f.mode = SAC_FORM_CHECK;
+    int rc = sac_critic_backward(s, f);
+    if (rc == ILSX_OK) rc = sac_actor_backward(s, f);
+    s->static_heads = rc == ILSX_OK ? 1 : 0;
+  }
+  return s->static_heads == 1;
+}
+// The form of a step is decided by sac_form.h and nowhere else.  What the decision rests on for a batch of B rows ...
+static SacFormInputs sac_form_inputs(ilsx_sac* s, int B) {
+  SacFormInputs in;
+  in.cs = s->cs; in.wide_l0 = s->h0scr != nullptr; in.phase_broken = s->phase_broken; in.xcd_shift = s->ctx->xcd_shift;
+  in.split = sac_is_split(s); in.no_phase = sw::ILSX_NO_PHASE(); in.no_fuse = sw::ILSX_NO_FUSE();
+  in.phase_fits = [s, B] { return phase_fits(s->ctx, B, s->Lq.cfg.hidden, s->cs, 4); };
+  in.static_heads = [s] { return sac_static_heads_ok(s); };
+  in.phase_own_rows = [s, B] { return phase_own_rows(s->ctx, B, s->Lq.cfg.hidden, s->cs, 4); };
+  return in;
+}
+// ... the window-level answer (checkpoints are taken under it: ilsx_advirl_train) ...
+bool sac_window_may_use_phase(ilsx_sac* s, int B) { return sac_window_may_phase(sac_form_inputs(s, B)); }
+// ... and the form of the next step on the staged B rows: inside the open window (s->defer_tail is the window's decision), or a lone step
+// (no window: no deferred tail, hence never the phase kernels).  `col`: the step is collected for a grouped build.
+static SacStepForm sac_decide(ilsx_sac* s, ilsx_replay* ring, SacCollector* col = nullptr) {
+  SacFormInputs in = sac_form_inputs(s, s->B);
+  in.collecting = col != nullptr;
+  return sac_step_form(in, s->defer_tail, ring, col);
+}
+
 // Deferred tail: see TailLite in kernels.h.  Enabled for the duration of one train_from_replay call when the whole step runs on
 // the fused column-split path (no gradient all-reduce between the phases, no XCD confinement); the last step's tail is flushed
 // by the ordinary tail kernel, so no tail is ever pending when the call returns.
-static bool sac_is_split(const ilsx_sac* s);
 static TailLite sac_tail_lite(ilsx_sac* s, int B) {
   TailLite t;
   memset(&t, 0, sizeof t);
@@ -708,10 +744,10 @@ static TailLite sac_tail_lite(ilsx_sac* s, int B) {
 // occupancy and environment variables, which need not match across ranks, and one rank deciding differently would deadlock the job inside
 // RCCL: every rank contributes "I cannot" (0 / 1) to a one-float all-reduce and the window runs on the phase kernels only if nobody said so.
 static int sac_split_on_phase(ilsx_sac* s, int B, bool* on) {
-  const bool mine = getenv("ILSX_SPLIT_NO_PHASE") == nullptr && sac_window_may_use_phase(s, B);
+  const bool mine = !sw::ILSX_SPLIT_NO_PHASE() && sac_window_may_use_phase(s, B);
   *on = mine;
   if (!(s->ctx->comm && s->ctx->comm_n > 1)) return ILSX_OK;
-  if (getenv("ILSX_SPLIT_PHASE") == nullptr) { *on = false; return ILSX_OK; }
+  if (!sw::ILSX_SPLIT_PHASE()) { *on = false; return ILSX_OK; }
   hipStream_t st = s->ctx->stream;
   if (!s->vote) ILSX_TRY(s->own.alloc(&s->vote, 4));
   float v = mine ? 0.0f : 1.0f;
@@ -722,11 +758,12 @@ static int sac_split_on_phase(ilsx_sac* s, int B, bool* on) {
   *on = v == 0.0f;
   return ILSX_OK;
 }
+// Window begin: decides whether the window's steps defer their tail and records it in s->defer_tail, where every step's form takes it from
+// (sac_decide); sac_defer_end closes the window.  No other code writes s->defer_tail.
 static int sac_defer_begin(ilsx_sac* s, int B) {
-  static const bool off = getenv("ILSX_NO_DEFER_TAIL") != nullptr || getenv("ILSX_NO_FUSE") != nullptr;
   s->defer_tail = false;
   const bool split = sac_is_split(s);
-  if (off || s->cs <= 1 || s->col) return ILSX_OK;
+  if (sw::ILSX_NO_DEFER_TAIL() || sw::ILSX_NO_FUSE() || s->cs <= 1) return ILSX_OK;
   if (split) {
     bool on = false;
     ILSX_TRY(sac_split_on_phase(s, B, &on));
@@ -742,6 +779,11 @@ static int sac_defer_begin(ilsx_sac* s, int B) {
   s->defer_tail = true;
   return ILSX_OK;
 }
+static bool sac_defer_end(ilsx_sac* s) {   // window end: what the window had decided
+  const bool deferred = s->defer_tail;
+  s->defer_tail = false;
+  return deferred;
+}
 static int sac_flush_tail(ilsx_sac* s, bool deferred) {   // the pending tail of the call's last step (+ its statistics if requested)
   if (!deferred) return ILSX_OK;
   ProfScope ps(s->ctx, ILSX_K_SAC_FINISH);
@@ -753,14 +795,6 @@ static int sac_flush_tail(ilsx_sac* s, bool deferred) {   // the pending tail of
   return ILSX_OK;
 }
 
-// Split run (cfg.grad_world = G > 1, SURVEY §8e): this rank holds B/G rows; the gradient arena is summed over the ranks between
-// backward and the optimiser step with RCCL on the ctx stream (segment 0 = critics, 1 = actor | alpha slot: two messages
-// because the actor loss is evaluated with the post-update critics, sac_alpha.py:142-146).
-// ILSX_SPLIT_FORCE=1 (tests): a run with grad_world = 1 whose ctx carries a one-rank communicator takes the split-run code path
-// too — un-fused phases with ncclAllReduce between them — so the collective plumbing is exercised on a single-GPU box.
-static bool sac_is_split(const ilsx_sac* s) {
-  return s->cfg.grad_world > 1 || (s->ctx->comm != nullptr && getenv("ILSX_SPLIT_FORCE") != nullptr);
-}
 static int sac_allreduce(ilsx_sac* s, int segment) {
   if (!sac_is_split(s)) return ILSX_OK;
   if (segment == 0) return comm_allreduce_sum(s->ctx, s->G, 2 * s->nq);
@@ -774,17 +808,13 @@ static int sac_check_world(const ilsx_sac* s, const char* who) {
   return ILSX_OK;
 }
 
-static int sac_full_step(ilsx_sac* s) {
-  static const bool no_fuse = getenv("ILSX_NO_FUSE") != nullptr;
-  s->fuse_now = !no_fuse && !sac_is_split(s);
-  int rc = sac_critic_backward(s);
-  if (rc == ILSX_OK) rc = sac_allreduce(s, 0);
-  if (rc == ILSX_OK) rc = sac_critic_update(s);
-  if (rc == ILSX_OK) rc = sac_actor_backward(s);
-  if (rc == ILSX_OK) rc = sac_allreduce(s, 1);
-  if (rc == ILSX_OK) rc = sac_actor_update(s);
-  s->fuse_now = false;
-  return rc;
+static int sac_full_step(ilsx_sac* s, const SacStepForm& f) {
+  ILSX_TRY(sac_critic_backward(s, f));
+  ILSX_TRY(sac_allreduce(s, 0));
+  ILSX_TRY(sac_critic_update(s, f));
+  ILSX_TRY(sac_actor_backward(s, f));
+  ILSX_TRY(sac_allreduce(s, 1));
+  return sac_actor_update(s, f);
 }
 
 static int sac_request_stats(ilsx_sac* s, hipStream_t st = nullptr) {  // ordered on the stream before the step that must produce them
@@ -844,14 +874,13 @@ int sac_staged_batch(ilsx_sac* s, int B, float** obs, float** act, float** rew, 
 int sac_step_staged(ilsx_sac* s, ilsx_sac_stats* stats) {
   ILSX_TRY(sac_check_world(s, "ilsx_advirl_train"));
   if (stats) ILSX_TRY(sac_request_stats(s));
-  ILSX_TRY(sac_full_step(s));
+  ILSX_TRY(sac_full_step(s, sac_decide(s, nullptr)));
   if (stats) return sac_read_stats(s, stats);
   return ILSX_OK;
 }
 int sac_dims(const ilsx_sac* s, int* o, int* a) { *o = s->o; *a = s->a; return ILSX_OK; }
 // A window of steps on batches the caller stages in place (sac_staged_batch): the deferred tail and the merged phase kernels, as inside
 // one ilsx_sac_train_from_replay call — the rows just come from the batch arrays instead of the in-kernel replay draw.
-static bool sac_phase_ok(ilsx_sac* s, int B);
 static int sac_phase_check(ilsx_sac* s, int B, bool deferred, const char* who, bool teardown = false);
 int sac_window_begin(ilsx_sac* s, int B) {
   ILSX_TRY(sac_check_world(s, "ilsx_advirl_train"));
@@ -859,16 +888,12 @@ int sac_window_begin(ilsx_sac* s, int B) {
   return sac_defer_begin(s, B);
 }
 int sac_window_step(ilsx_sac* s) {
-  s->gather_rb = nullptr;
-  s->phase_now = sac_phase_ok(s, s->B);
-  s->phase_last = s->phase_now;
-  const int rc = sac_full_step(s);
-  s->phase_now = false;
-  return rc;
+  const SacStepForm f = sac_decide(s, nullptr);
+  s->phase_last = f.phase;
+  return sac_full_step(s, f);
 }
 int sac_window_end(ilsx_sac* s, bool teardown) {
-  const bool deferred = s->defer_tail;
-  s->defer_tail = false;
+  const bool deferred = sac_defer_end(s);
   ILSX_TRY(sac_flush_tail(s, deferred));
   return sac_phase_check(s, s->B, deferred, "ilsx_advirl_train", teardown);
 }
@@ -879,7 +904,7 @@ int sac_window_end(ilsx_sac* s, bool teardown) {
     if (s->B < 1) ILSX_FAIL(ILSX_ERR_STATE, #name ": no batch staged (ilsx_sac_set_batch)"); \
     HIPCHK(hipSetDevice(s->ctx->device));                                          \
     s->stats_cached = false; /* phases driven by hand: ilsx_sac_last_stats reads the device */ \
-    return fn(s);                                                                  \
+    return fn(s, SacStepForm{}); /* the plain form: staged rows, one launch per stage, Adam and tail as launches of their own */ \
   }
 SAC_PHASE(ilsx_sac_critic_backward, sac_critic_backward)
 SAC_PHASE(ilsx_sac_critic_update, sac_critic_update)
@@ -901,41 +926,11 @@ extern "C" int ilsx_sac_train_step(ilsx_sac* s, const float* obs, const float* a
   if (s) ILSX_TRY(sac_check_world(s, "ilsx_sac_train_step"));
   ILSX_TRY(ilsx_sac_set_batch(s, obs, act, rew, done, nobs, B, eps_next, eps_cur));
   if (stats) ILSX_TRY(sac_request_stats(s));
-  ILSX_TRY(sac_full_step(s));
+  ILSX_TRY(sac_full_step(s, sac_decide(s, nullptr)));
   if (stats) return sac_read_stats(s, stats);
   return ILSX_OK;
 }
 
-// The merged phase kernels need: the column-split path on narrow inputs, the fused in-kernel replay draw, the deferred tail, no
-// gradient all-reduce between the phases, no per-workgroup stamps, and every workgroup of a phase launch resident at once.
-// And the stages' descriptors are what the phase kernels are compiled for (static heads: loss kind per stage, one head output per critic,
-// slab counts, the tanh-Gaussian epilogue with one element per thread, no explicit noise).  Asked once per agent, of the blocks themselves:
-// a dry pass builds them as a step would and launch_phase_a / _c hold them against phase_a_static_ok / phase_c_static_ok (nothing is
-// uploaded or launched).  An agent whose blocks are refused stays on one launch per stage.  (Asked last: the dry pass needs a shape the
-// phase kernels exist for.)
-static bool sac_static_heads_ok(ilsx_sac* s) {
-  if (s->static_heads < 0) {
-    const bool phase_now = s->phase_now, fuse_now = s->fuse_now, eps_explicit = s->eps_explicit;
-    ilsx_replay* const rb = s->gather_rb;
-    s->gather_rb = nullptr; s->phase_now = true; s->fuse_now = !sac_is_split(s); s->eps_explicit = false;
-    s->phase_args_only = s->phase_check_only = true;
-    int rc = sac_critic_backward(s);
-    if (rc == ILSX_OK) rc = sac_actor_backward(s);
-    s->phase_args_only = s->phase_check_only = false;
-    s->gather_rb = rb; s->phase_now = phase_now; s->fuse_now = fuse_now; s->eps_explicit = eps_explicit;
-    s->static_heads = rc == ILSX_OK ? 1 : 0;
-  }
-  return s->static_heads == 1;
-}
-static bool sac_phase_ok(ilsx_sac* s, int B) {
-  const bool off = getenv("ILSX_NO_PHASE") != nullptr;
-  return !off && !s->phase_broken && s->cs > 1 && !s->h0scr && !s->col && s->defer_tail &&
-         s->ctx->xcd_shift == 0 && phase_fits(s->ctx, B, s->Lq.cfg.hidden, s->cs, 4) && sac_static_heads_ok(s);   // (a split run defers its tail only for the phase kernels: sac_defer_begin)
-}
-static bool sac_phase_possible(ilsx_sac* s, int B) {   // as sac_phase_ok, for the state a train_from_replay call ran in (defer_tail already cleared)
-  const bool off = getenv("ILSX_NO_PHASE") != nullptr;   // read per call: tests switch between the two paths in one process
-  return !off && s->cs > 1 && !s->h0scr && phase_fits(s->ctx, B, s->Lq.cfg.hidden, s->cs, 4) && sac_static_heads_ok(s);
-}
 // Checkpoint / roll-back of everything a gradient step mutates — device scalars (log alpha and its moments, step / Philox counters,
 // Adam scalars), parameters + targets, gradients, Adam moments: one contiguous range of the agent's slab (ilsx_sac_create adds them
 // in this order).  Taken at the start of every window that may run on the merged phase kernels (~3 MB device-to-device, once per
@@ -956,7 +951,6 @@ int sac_snapshot_restore(ilsx_sac* s) {
   HIPCHK(hipMemsetAsync(s->phase_flags, 0, (size_t)PHASE_FLAG_WORDS * sizeof(unsigned), s->ctx->stream));
   return ILSX_OK;
 }
-bool sac_window_may_use_phase(ilsx_sac* s, int B) { return !s->phase_broken && s->cs > 1 && !s->col && sac_phase_possible(s, B) && s->ctx->xcd_shift == 0; }
 // After a window of steps that may have run on the merged phase kernels: a workgroup that gave up waiting, or a row tile whose workgroups
 // sat on two XCDs, left a mark — the window's updates are then not to be trusted.  Returns ILSX_RETRY_WINDOW: the caller rolls the window
 // back (sac_snapshot_restore) and runs it again; the agent stays on one launch per stage from here on.
@@ -966,7 +960,7 @@ static int sac_phase_check(ilsx_sac* s, int B, bool deferred, const char* who, b
   struct SnapGuard { ilsx_sac* s; bool keep = false; ~SnapGuard() { if (!keep) s->snap_valid = false; } } snap_guard{s};
   // teardown: the window is being closed on an error path (ilsx_advirl_train's guard) — this rank's peers are inside some other collective,
   // so no vote is issued (a mismatched all-reduce hangs instead of returning the error) and nothing is re-run: the caller already fails
-  if (deferred && s->snap_valid && !teardown) {   // == the window began with sac_window_may_use_phase (the one predicate: the checkpoint is taken under it)
+  if (deferred && s->snap_valid && !teardown) {   // == the window's steps could take the phase kernels (sac_step_may_phase: the checkpoint is taken under the predicate the launch is chosen under)
     // a phase-kernel workgroup that gave up waiting left a mark: the steps of this call are not to be trusted
     int err = 0;
     unsigned masks[PHASE_MAX_TILES * 32];
@@ -991,7 +985,7 @@ static int sac_phase_check(ilsx_sac* s, int B, bool deferred, const char* who, b
       s->phase_broken = true;
       if (s->graph) { hipGraphExecDestroy(s->graph); s->graph = nullptr; }
       HIPCHK(hipMemsetAsync(s->phase_err, 0, sizeof(int), st));
-      if (getenv("ILSX_PHASE_VERBOSE"))
+      if (sw::ILSX_PHASE_VERBOSE())
         fprintf(stderr, "[ilsx] %s: a merged phase kernel %s; the window is rolled back and re-run, this agent stays on one launch per stage\n", who,
                 (err & 1) ? "timed out waiting for the workgroups of its tile (other kernels sharing this GPU?)"
                 : (err & 2) ? "found the workgroups of one row tile on different XCDs" : "broke on another rank of this split run");
@@ -1003,34 +997,22 @@ static int sac_phase_check(ilsx_sac* s, int B, bool deferred, const char* who, b
   return ILSX_OK;
 }
 
-// The two phase launches' descriptor blocks, built exactly as the step that follows will build them (same agent state) and put into this agent's
-// constant-memory slots — a dry pass that launches nothing, run before a capture begins (launch_phase_a / _c then find the slots current).
-static int sac_phase_const_prime(ilsx_sac* s, ilsx_replay* rb) {
+// The two phase launches' descriptor blocks, built exactly as the step that follows will build them (the same form, in upload mode) and put into
+// this agent's constant-memory slots — a dry pass that launches nothing, run before a capture begins (launch_phase_a / _c then find the slots current).
+static int sac_phase_const_prime(ilsx_sac* s, const SacStepForm& step) {
   phase_const_prepare(s->ctx, &s->pct);
   if (s->pct.slot < 0 || s->cs <= 1) return ILSX_OK;
-  static const bool no_fuse = getenv("ILSX_NO_FUSE") != nullptr;
-  s->gather_rb = rb; s->phase_now = true; s->fuse_now = !no_fuse && !sac_is_split(s);
-  s->phase_args_only = true;
-  int rc = sac_critic_backward(s);
-  if (rc == ILSX_OK) rc = sac_actor_backward(s);
-  s->phase_args_only = false;
-  s->gather_rb = nullptr; s->phase_now = false; s->fuse_now = false;
-  return rc;
+  SacStepForm f = step;
+  f.mode = SAC_FORM_UPLOAD;
+  ILSX_TRY(sac_critic_backward(s, f));
+  return sac_actor_backward(s, f);
 }
 
-static int sac_sample_and_step(ilsx_sac* s, ilsx_replay* rb, int B) {
+static int sac_sample_and_step(ilsx_sac* s, const SacStepForm& f) {
   const SacWs& w = s->ws;
-  if (s->cs > 1) {
-    s->gather_rb = rb;   // sampling is fused into the first forward launch
-    s->phase_now = sac_phase_ok(s, B);
-    s->phase_last = s->phase_now;
-    const int rc = sac_full_step(s);
-    s->gather_rb = nullptr;
-    s->phase_now = false;
-    return rc;
-  }
-  ILSX_TRY(replay_launch_sample(rb, B, nullptr, s->scal, 0, w.s, w.a, w.r, w.d, w.s2, nullptr));
-  return sac_full_step(s);
+  if (s->cs == 1)   // (the column-split path draws its rows inside the first forward launch)
+    ILSX_TRY(replay_launch_sample(f.ring, s->B, nullptr, s->scal, 0, w.s, w.a, w.r, w.d, w.s2, nullptr));
+  return sac_full_step(s, f);
 }
 
 static int sac_train_from_replay_once(ilsx_sac* s, ilsx_replay* rb, int n_steps, int B, ilsx_sac_stats* stats);
@@ -1086,50 +1068,45 @@ static int sac_train_from_replay_once(ilsx_sac* s, ilsx_replay* rb, int n_steps,
   s->eps_explicit = false;
   // split runs replay the step from a hipGraph only on request: RCCL calls inside a capture are the one part of this path
   // that could not be exercised with more than one rank on the development box
-  static const bool split_graph = getenv("ILSX_SPLIT_GRAPH") != nullptr;
-  static const bool no_graph_env = getenv("ILSX_NO_GRAPH") != nullptr;
-  const bool no_graph = no_graph_env || (sac_is_split(s) && !split_graph);
+  const bool no_graph = sw::ILSX_NO_GRAPH() || (sac_is_split(s) && !sw::ILSX_SPLIT_GRAPH());
   if (n_steps == 0) return stats ? sac_read_stats(s, stats) : ILSX_OK;
   ILSX_TRY(sac_defer_begin(s, B));
-  struct DeferGuard { ilsx_sac* s; ~DeferGuard() { s->defer_tail = false; } } guard{s};   // never left on, whatever path returns
+  struct WindowGuard { ilsx_sac* s; ~WindowGuard() { sac_defer_end(s); } } guard{s};   // closed on whatever path returns
   const bool deferred = s->defer_tail;
-  if (deferred && sac_window_may_use_phase(s, B)) ILSX_TRY(sac_snapshot_take(s));   // the roll-back point of this window
+  const SacStepForm form = sac_decide(s, rb);   // of every step of this window (phase A's mapping included: the cached graph holds its grid and descriptor)
+  s->phase_last = form.phase;
+  if (form.phase) ILSX_TRY(sac_snapshot_take(s));   // the roll-back point of this window
   if (no_graph || s->ctx->prof_on) {
     for (int i = 0; i < n_steps; ++i) {
       if (stats && i == n_steps - 1) ILSX_TRY(sac_request_stats(s));
-      const int rc = sac_sample_and_step(s, rb, B);
-      if (rc != ILSX_OK) return rc;
+      ILSX_TRY(sac_sample_and_step(s, form));
     }
   } else {
-    const bool phase = sac_phase_ok(s, B);
-    s->phase_last = phase;
-    const bool own = phase && sac_own_rows(s);   // phase A's mapping is part of what the cached graph holds (grid, descriptor)
     // The phase kernels' descriptor blocks into this agent's constant-memory slots — before a capture begins, and before EVERY replay of a
     // cached graph too: between two calls another step form of the same agent (an explicit-batch step, the adversarial-IRL loop, a profiled
     // window: direct launches under another state key) may have put ITS blocks there, and the graph's launches would read those.  The dry pass
     // costs a few host microseconds when the slots are current.
-    static const bool no_reprime = getenv("ILSX_PHASE_CT_NO_REPRIME") != nullptr;   // test aid: shows what the re-prime is for (tests/test_hip_parity.py)
-    const bool rebuild = !s->graph || s->graph_rb != rb || s->graph_B != B || s->graph_defer != s->defer_tail || s->graph_phase != phase || s->graph_own != own;
-    if (phase && (rebuild || !no_reprime)) ILSX_TRY(sac_phase_const_prime(s, rb));
+    const bool rebuild = !s->graph || s->graph_B != B || s->graph_form != form;
+    if (form.phase && (rebuild || !sw::ILSX_PHASE_CT_NO_REPRIME())) ILSX_TRY(sac_phase_const_prime(s, form));   // (the switch is a test aid: it shows what the re-prime is for, tests/test_hip_parity.py)
     if (rebuild) {
       if (s->graph) { hipGraphExecDestroy(s->graph); s->graph = nullptr; }
       hipGraph_t g = nullptr;
       HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      int rc = sac_sample_and_step(s, rb, B);
+      int rc = sac_sample_and_step(s, form);
       hipError_t e = hipStreamEndCapture(st, &g);
       if (rc != ILSX_OK) { if (g) hipGraphDestroy(g); return rc; }
       if (e != hipSuccess) ILSX_FAIL(ILSX_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
       e = hipGraphInstantiate(&s->graph, g, nullptr, nullptr, 0);
       hipGraphDestroy(g);
       if (e != hipSuccess) { s->graph = nullptr; ILSX_FAIL(ILSX_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e)); }
-      s->graph_rb = rb; s->graph_B = B; s->graph_defer = s->defer_tail; s->graph_phase = phase; s->graph_own = own;
+      s->graph_form = form; s->graph_B = B;
     }
     for (int i = 0; i < n_steps; ++i) {
       if (stats && i == n_steps - 1) ILSX_TRY(sac_request_stats(s));
       HIPCHK(hipGraphLaunch(s->graph, st));
     }
   }
-  s->defer_tail = false;
+  sac_defer_end(s);
   ILSX_TRY(sac_flush_tail(s, deferred));
   ILSX_TRY(sac_phase_check(s, B, deferred, "ilsx_sac_train_from_replay"));
   if (stats) return sac_read_stats(s, stats);
@@ -1364,15 +1341,12 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
   std::vector<SacCollector> cols(K);
   for (int k = 0; k < K; ++k) {
     ilsx_sac* s = g->agents[k];
-    s->B = B; s->eps_explicit = false; s->col = &cols[k]; s->gather_rb = rbs[k];
-    const int rc = sac_full_step(s);
-    s->col = nullptr; s->gather_rb = nullptr;
-    if (rc != ILSX_OK) return rc;
+    s->B = B; s->eps_explicit = false;
+    ILSX_TRY(sac_full_step(s, sac_decide(s, rbs[k], &cols[k])));
     if (cols[k].L.size() != cols[0].L.size()) ILSX_FAIL(ILSX_ERR_STATE, "agents of a group must produce the same launch sequence");
   }
   group_release_tables(g);
-  const char* ce = getenv("ILSX_GRP_CONST");   // 0: descriptor records from the device-memory tables only (A/B)
-  const bool use_const = !(ce && atoi(ce) == 0);
+  const bool use_const = sw::ILSX_GRP_CONST();   // 0: descriptor records from the device-memory tables only (A/B)
   const size_t nst = cols[0].L.size();
   g->stages.resize(nst);
   for (size_t i = 0; i < nst; ++i) {
@@ -1423,8 +1397,7 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
       int tiles = 0, nmat = 0;
       // tile shape: as for single launches (launch_bwd_dw) the smallest that keeps the launch within ~3 workgroups per CU — it only
       // matters for small groups (K = 1, 2: +4 %); at K >= 4 the launch is bound elsewhere and every shape measures the same
-      const char* gse = getenv("ILSX_DW_TILE_GRP");   // "NH KT" digits (24, 12, 11), unset / 0 = by size; read per group build
-      const int gshape = gse ? atoi(gse) : 0;
+      const int gshape = sw::ILSX_DW_TILE_GRP();   // "NH KT" digits (24, 12, 11), unset / 0 = by size; read per group build
       int gnh = 2, gkt = 4;
       if (gshape) { gnh = gshape / 10; gkt = gshape % 10; }
       else {
@@ -1474,7 +1447,8 @@ static int group_build(ilsx_sac_group* g, ilsx_replay* const* rbs, int B) {
   g->rbs.assign(rbs, rbs + K);
   g->B = B;
   // ILSX_GRP_LATE = 0 | 1 pins the "late weights" launch shape off / on (kernels.h GRP == 3); by default each launch decides from its size
-  if (const char* e = getenv("ILSX_GRP_LATE")) g->late = atoi(e) ? 1 : 0; else g->late = -1;
+  const int late = sw::ILSX_GRP_LATE();
+  g->late = late < 0 ? -1 : late ? 1 : 0;
   return ILSX_OK;
 }
 
@@ -1577,8 +1551,7 @@ extern "C" int ilsx_sac_group_train_from_replay(ilsx_sac_group* g, ilsx_replay* 
   struct FenceOut { ilsx_sac_group* g; ~FenceOut() { group_fence_out(g); } } fence_out{g};   // on every path out of this call
   if (rebuild) ILSX_TRY(group_build(g, rbs, B));
   hipStream_t st = g->ctx->stream;
-  static const bool no_graph = getenv("ILSX_NO_GRAPH") != nullptr;
-  static const bool no_defer = getenv("ILSX_NO_DEFER_TAIL") != nullptr;
+  const bool no_graph = sw::ILSX_NO_GRAPH(), no_defer = sw::ILSX_NO_DEFER_TAIL();
   const bool use_graph = !(no_graph || g->ctx->prof_on);
   if (n_steps == 0) return ILSX_OK;
   if (g->defer != !no_defer && g->graph) { hipGraphExecDestroy(g->graph); g->graph = nullptr; }

@@ -370,6 +370,108 @@ def _check(ctx, rc):
     _lib.check(rc)
 
 
+def _interleaved_forms(B):
+    """Every form a SAC step can take on ONE agent, one after the other: a window from the ring, a lone step on an explicit batch with
+    explicit noise, the four phases driven by hand on a staged batch, a window whose first step computes statistics, a last window.
+    Returns the agent's whole state (parameters, targets, Adam moments, log_alpha, counters) and what ilsx_sac_phase_state says at the end."""
+    import ilswiss_amd as ia
+    o, a, hidden, N = 11, 3, [256, 256], 4096
+    rng = np.random.default_rng(1000 + B)
+    params = _init(rng, o, a, hidden)
+    data = _ring_data(rng, N, o, a)
+    batches = [dict(observations=s, actions=ac, rewards=r.reshape(B, 1), terminals=d.astype(np.float32).reshape(B, 1), next_observations=s2)
+               for s, ac, r, d, s2 in (_ring_data(rng, B, o, a) for _ in range(2))]
+    e1, e2 = rng.normal(0, 1, (B, a)).astype(np.float32), rng.normal(0, 1, (B, a)).astype(np.float32)
+    ctx = ia.Context(0, seed=4242)
+    rb = ia.SimpleReplayBuffer(N, o, a, random_seed=5, ctx=ctx)
+    rb.add_rows(*data)
+    tr = _agent(ia, ctx, o, a, hidden, params, SAC_KW, B)
+    tr.eval_statistics = {}
+    tr.train_from_replay(rb, 3, B)
+    tr.train_step(batches[0], e1, e2)
+    tr.set_batch(batches[1])
+    tr.critic_backward(), tr.critic_update(), tr.actor_backward(), tr.actor_update()
+    tr.eval_statistics = None
+    tr.train_from_replay(rb, 3, B)
+    stats = dict(tr.get_eval_statistics())
+    tr.eval_statistics = {}
+    tr.train_from_replay(rb, 2, B)
+    snap, ps, steps = tr.get_snapshot(), tr.phase_state(), tr.rng_step
+    ctx.close()
+    return snap, stats, ps, steps
+
+
+def _digest(snap, stats, steps):
+    import hashlib
+    h = hashlib.sha256()
+    for k in NETS:
+        h.update(np.ascontiguousarray(snap[k]).tobytes())
+    for k in ("policy_optimizer", "qf1_optimizer", "qf2_optimizer"):
+        h.update(np.ascontiguousarray(snap[k]["exp_avg"]).tobytes()), h.update(np.ascontiguousarray(snap[k]["exp_avg_sq"]).tobytes())
+    h.update(repr((snap["log_alpha"], sorted(snap["alpha_optimizer"].items()), sorted(stats.items()), steps)).encode())
+    return h.hexdigest()
+
+
+_FORMS_CHILD = r"""
+import json, sys
+sys.path.insert(0, "tests")
+import test_fused_parity as T
+out = {}
+for B in (37, 256):
+    snap, stats, ps, steps = T._interleaved_forms(B)
+    out[B] = [T._digest(snap, stats, steps), ps["last_window_on_phase"]]
+print(json.dumps(out))
+"""
+
+
+@pytest.fixture(scope="module")
+def forms_without_graph():
+    """_interleaved_forms in a fresh child process with ILSX_NO_GRAPH=1 (read once per process): every window launched directly."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k != "ILSX_NO_PHASE"}
+    r = subprocess.run([sys.executable, "-c", _FORMS_CHILD], cwd=root, env=dict(env, ILSX_NO_GRAPH="1"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.parametrize("B", [37, 256])
+def test_step_forms_do_not_leak_into_each_other_on_one_agent(B, forms_without_graph):
+    """The form of a step is a value decided per step or per window (csrc/sac_form.h), not flags left on the agent: windows on the merged
+    phase kernels, a lone explicit step, the hand-driven phases and a statistics window, interleaved on one agent, must leave it bit for
+    bit where the same sequence on one launch per stage (ILSX_NO_PHASE=1, read per call) leaves an agent of equal seeds — and where the
+    sequence without the captured graph leaves it.  B = 37: a ragged last tile; 256: the benchmarked shape."""
+    import os
+    runs = []
+    for no_phase in (False, True):
+        if no_phase:
+            os.environ["ILSX_NO_PHASE"] = "1"
+        else:
+            os.environ.pop("ILSX_NO_PHASE", None)
+        try:
+            runs.append(_interleaved_forms(B))
+        finally:
+            os.environ.pop("ILSX_NO_PHASE", None)
+    (s0, st0, ps0, r0), (s1, st1, ps1, r1) = runs
+    assert r0 == r1 == 10   # 3 + 1 + 1 + 3 + 2 gradient steps
+    assert ps0["last_window_on_phase"] and not ps0["disabled"] and ps0["fallbacks"] == 0, ps0
+    assert not ps1["last_window_on_phase"] and ps1["fallbacks"] == 0, ps1
+    for k in NETS:
+        np.testing.assert_array_equal(s0[k], s1[k], err_msg=k)
+    assert s0["log_alpha"] == s1["log_alpha"] and s0["alpha_optimizer"] == s1["alpha_optimizer"]
+    for k in ("policy_optimizer", "qf1_optimizer", "qf2_optimizer"):
+        np.testing.assert_array_equal(s0[k]["exp_avg"], s1[k]["exp_avg"], err_msg=k)
+        np.testing.assert_array_equal(s0[k]["exp_avg_sq"], s1[k]["exp_avg_sq"], err_msg=k)
+        assert s0[k]["step"] == s1[k]["step"] == 10, k
+    for k, v in st0.items():
+        assert v == st1[k] or (np.isnan(v) and np.isnan(st1[k])), (k, v, st1[k])
+    digest, on_phase = forms_without_graph[str(B)]
+    assert digest == _digest(s0, st0, r0) == _digest(s1, st1, r1) and on_phase
+
+
 _SHARED_GPU_SCRIPT = r"""
 import hashlib, json, sys
 import numpy as np
