@@ -15,6 +15,7 @@ import pickle
 import sys
 import time
 from collections import OrderedDict
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -89,6 +90,8 @@ def sync_eval_obs_rms(alg):
 class DeviceRLAlgorithm:
     """TorchRLAlgorithm(trainer, env, training_env, eval_env, exploration_policy, **rl_alg_params)."""
 
+    EVAL_BETWEEN_EPOCHS = None   # a subclass whose epoch loop cannot evaluate beside the next epoch says why here (eval_async then falls back)
+
     def __init__(self, trainer, env, training_env, eval_env, exploration_policy, *, batch_size, num_train_steps_per_train_call,
                  num_epochs=100, num_steps_per_epoch=10000, num_steps_between_train_calls=20, num_steps_per_eval=1000,
                  max_path_length=1000, min_steps_before_training=5000, replay_buffer_size=10000, no_terminal=False,
@@ -145,7 +148,6 @@ class DeviceRLAlgorithm:
         # (2) the exploration-noise stream from epoch 1 on: a blocking evaluation advances the policy context's act-call counter
         # (ilsx_policy_act keys its Philox draw with it), the frozen copy advances its own context's — same distribution, other draws.
         self.eval_async = self._eval_async_setup() if eval_async else None
-        self._eval_pending = None
         self._n_env_steps_total = self._n_train_steps_total = self._n_prev_train_env_steps = self._n_grad_steps_total = 0
         self._n_rollouts_total, self.best_statistic_so_far = 0, -np.inf
         self._t_sample = self._t_train = self._t_eval = 0.0
@@ -159,30 +161,20 @@ class DeviceRLAlgorithm:
         """The on-policy branch (torch_rl_algorithm.py:30-32): every `num_steps_between_train_calls` env steps the trainer
         consumes ALL samples collected since the last call and the buffer is cleared.  Here the samples never leave the
         device: trainer.train_from_rollout runs the vec steps, GAE and the minibatch epochs."""
-        ctx = self.trainer.ctx
+        loop = DeviceRLAlgorithmGroup([self])
         horizon = max(1, self.num_steps_between_train_calls // self.env_num)
-        t_start = time.perf_counter()
         for epoch in range(start_epoch, self.num_epochs + 1):
-            t_epoch = time.perf_counter()
-            self.training_env.rollout_stats(reset=True)
+            loop.begin_epoch()
             steps = 0
             while steps < self.num_env_steps_per_epoch:
                 steps += self.trainer.train_from_rollout(self.training_env, horizon, self.max_path_length,
                                                          bootstrap=self.bootstrap_open_segments)
                 self._n_train_steps_total += 1
                 self._n_grad_steps_total += self.num_train_steps_per_train_call
-            ctx.sync()
             self._n_env_steps_total += steps
-            self._t_train = time.perf_counter() - t_epoch   # rollout + update are one device pipeline here
-            self._t_sample = 0.0
-            if hasattr(self.eval_env, "sync_obs_rms"):
-                self.eval_env.sync_obs_rms()
-            t0 = time.perf_counter()
-            self.evaluate(epoch, time.perf_counter() - t_epoch, time.perf_counter() - t_start)
-            self._t_eval = time.perf_counter() - t0
-            self.trainer.end_epoch()
+            loop.end_epoch(epoch)
 
-    # ---- the pieces of one off-policy epoch (base_algorithm.py:183-286), shared by train() and DeviceRLAlgorithmGroup
+    # ---- what one run does in an off-policy epoch (base_algorithm.py:183-286); DeviceRLAlgorithmGroup schedules it
     def _vec_step(self, begin_only=False):
         """One sampling iteration of all envs: policy -> physics -> replay record -> auto-reset.  begin_only: enqueue it and return; the
         caller ends it with _vec_step_end() (which, with insert_at_episode_end, waits for the step and inserts the finished episodes)."""
@@ -210,45 +202,14 @@ class DeviceRLAlgorithm:
         self._n_train_steps_total += 1                                   # the reference counts CALLS here (:298)
         self._n_grad_steps_total += self.num_train_steps_per_train_call
 
+    def _train_call(self):
+        """what this run does at a train call"""
+        self.trainer.train_from_replay(self.replay_buffer, self.num_train_steps_per_train_call, self.batch_size)
+
     def train(self, start_epoch=0):
         if self.on_policy:
             return self._train_on_policy(start_epoch)
-        ctx = self.trainer.ctx
-        pool = None
-        t_start = time.perf_counter()
-        for epoch in range(start_epoch, self.num_epochs + 1):  # num_epochs + 1 (base_algorithm.py:64)
-            t_epoch = time.perf_counter()
-            self._t_sample = self._t_train = 0.0
-            self.training_env.rollout_stats(reset=True)
-            for _ in range(self.num_env_steps_per_epoch // self.env_num):
-                t0 = time.perf_counter()
-                self._vec_step()
-                if self._train_due():
-                    ctx.sync()
-                    t1 = time.perf_counter()
-                    self._t_sample += t1 - t0
-                    if self._can_train():
-                        self._count_train_call()
-                        self.trainer.train_from_replay(self.replay_buffer, self.num_train_steps_per_train_call, self.batch_size)
-                        ctx.sync()
-                    self._t_train += time.perf_counter() - t1
-                else:
-                    self._t_sample += time.perf_counter() - t0
-            ctx.sync()
-            t0 = time.perf_counter()
-            if self.eval_async is not None:
-                if pool is None:
-                    from concurrent.futures import ThreadPoolExecutor
-                    pool = ThreadPoolExecutor(max_workers=1)
-                self._eval_async_start(pool, epoch, t0 - t_epoch, t0 - t_start)
-            else:
-                sync_eval_obs_rms(self)
-                self.evaluate(epoch, time.perf_counter() - t_epoch, time.perf_counter() - t_start)
-                self._t_eval = time.perf_counter() - t0
-            self.trainer.end_epoch()
-        if pool is not None:
-            self._eval_async_join()
-            pool.shutdown()
+        return DeviceRLAlgorithmGroup([self]).train(start_epoch)   # num_epochs + 1 epochs (base_algorithm.py:64)
 
     def _eval_collect(self):
         """The evaluation rollouts (device work + host waits, no logging): what evaluate() reduces and logs."""
@@ -260,10 +221,13 @@ class DeviceRLAlgorithm:
     def _eval_async_setup(self):
         """(frozen policy copy, sampler on it) when this run can evaluate beside its training: a deterministic device evaluation
         (MakeDeterministic over a network of this library) whose env lives on a context — a stream — of its own (the run scripts build it
-        there when rl_alg_params.eval_async is set).  None, with the reason printed, otherwise: the evaluation then blocks as always."""
+        there when rl_alg_params.eval_async is set) and whose loop takes the overlapped form.  None, with the reason printed, otherwise: the
+        evaluation then blocks as always, and neither the copy nor the second sampler is built."""
         s = self.eval_sampler
-        why = None
-        if type(s) is not DeviceEvalSampler:
+        why = self.EVAL_BETWEEN_EPOCHS
+        if why is not None:
+            pass
+        elif type(s) is not DeviceEvalSampler:
             why = "the evaluation is not a DeviceEvalSampler"
         else:
             pi, ppo, det = s._handles()
@@ -283,53 +247,27 @@ class DeviceRLAlgorithm:
         a = self.eval_async
         a["frozen"].set_flat_params(a["live"].get_flat_params())
 
-    def _eval_begin(self, epoch, epoch_time, total_time):
-        """Everything evaluate() logs that is NOT the evaluation rollouts, read at the end of the epoch: trainer statistics, the epoch's
-        exploration episodes, counters, times, and the snapshot an asynchronous evaluation will save under its own result."""
-        pre = dict(epoch=epoch, epoch_time=epoch_time, total_time=total_time, ts=self.trainer.get_eval_statistics())
+    def _eval_begin(self, epoch, epoch_time, total_time, ts):
+        """Everything a row holds that is NOT the evaluation rollouts, read at the end of the epoch: the trainer statistics `ts`, the epoch's
+        exploration episodes, counters, times.  "snapshot" / "extra" are callables: _eval_finish downloads what it saves and nothing else; an
+        evaluation that runs beside the next epoch replaces them with what they return now."""
+        pre = dict(epoch=epoch, epoch_time=epoch_time, total_time=total_time, ts=ts)
         pre["exploration"] = self.training_env.rollout_stats(reset=True)
         self._n_rollouts_total += int(pre["exploration"][0])
         pre["counters"] = (self._n_train_steps_total, self._n_grad_steps_total, self._n_env_steps_total * self.split_world, self._n_rollouts_total)
         pre["times"] = (self._t_train, self._t_eval, self._t_sample)
+        pre["snapshot"], pre["extra"] = self.get_epoch_snapshot, lambda: self.get_extra_data_to_save(epoch)
         return pre
 
-    def _eval_async_start(self, pool, epoch, epoch_time, total_time):
-        """End of an epoch in the asynchronous form: log the evaluation that ran beside this epoch, freeze the policy, take what the row and
-        the snapshots need, start this epoch's evaluation.  Returns after the hand-over; the training loop goes on."""
-        self._eval_async_join()
-        sync_eval_obs_rms(self)    # (after the join: the evaluation that ran beside this epoch used the statistics it was started with)
-        self._eval_freeze()
-        pre = self._eval_begin(epoch, epoch_time, total_time)
-        pre["snapshot"] = self.get_epoch_snapshot()
-        pre["extra"] = self.get_extra_data_to_save(epoch)
-        pre["t0"] = time.perf_counter()
-        sampler = self.eval_async["sampler"]
-
-        def run():
-            out = sampler.obtain_statistics(stat_prefix="Test")
-            return out, time.perf_counter() - pre["t0"]
-        self._eval_pending = (pre, pool.submit(run))
-
-    def _eval_async_join(self):
-        if self._eval_pending is not None:
-            pre, fut = self._eval_pending
-            self._eval_pending = None
-            collected, self._t_eval = fut.result()
-            self._eval_finish(pre, collected)
-
     def evaluate(self, epoch, epoch_time, total_time, collected=None):
-        pre = dict(epoch=epoch, epoch_time=epoch_time, total_time=total_time, ts=self.trainer.get_eval_statistics())
+        """The blocking form, in the reference's order of reads: trainer statistics, the evaluation rollouts, the exploration episodes."""
+        ts = self.trainer.get_eval_statistics()
         if collected is None:
             collected = self._eval_collect()
-        pre["exploration"] = self.training_env.rollout_stats(reset=True)
-        self._n_rollouts_total += int(pre["exploration"][0])
-        pre["counters"] = (self._n_train_steps_total, self._n_grad_steps_total, self._n_env_steps_total * self.split_world, self._n_rollouts_total)
-        pre["times"] = (self._t_train, self._t_eval, self._t_sample)
-        return self._eval_finish(pre, collected)
+        return self._eval_finish(self._eval_begin(epoch, epoch_time, total_time, ts), collected)
 
     def _eval_finish(self, pre, collected):
-        """Reduce and log one epoch's row, save its snapshots (base_algorithm.py:302-348, 599-656).  pre: _eval_begin's dict (+ "snapshot" /
-        "extra" taken at the end of the epoch when the evaluation ran beside the next one)."""
+        """Reduce and log one epoch's row, save its snapshots (base_algorithm.py:302-348, 599-656).  pre: _eval_begin's dict."""
         epoch, epoch_time, total_time = pre["epoch"], pre["epoch_time"], pre["total_time"]
         st = OrderedDict()
         ts = pre["ts"]
@@ -366,7 +304,7 @@ class DeviceRLAlgorithm:
         lg.record_tabular("Epoch", epoch)
         lg.dump_tabular()
         snap = dict(epoch=epoch, statistics=dict(st))
-        snapshot = (lambda: pre["snapshot"]) if "snapshot" in pre else self.get_epoch_snapshot   # the state the evaluated policy belongs to
+        snapshot = pre["snapshot"]   # the state the evaluated policy belongs to
         if self.freq_saving and epoch % self.freq_saving == 0:
             lg.save("params.pkl", dict(snap, **snapshot()))
         if self.save_epoch:   # base_algorithm.py:647-649
@@ -375,9 +313,8 @@ class DeviceRLAlgorithm:
             self.best_statistic_so_far = st[self.best_key]
             if self.save_best and epoch >= self.save_best_starting_from_epoch:   # :650-656
                 lg.save("best.pkl", dict(snap, **snapshot()))
-        extra = pre["extra"] if "extra" in pre else self.get_extra_data_to_save(epoch)
-        if "extra" in pre:
-            extra["best_statistic_so_far"] = self.best_statistic_so_far
+        extra = pre["extra"]()
+        extra["best_statistic_so_far"] = self.best_statistic_so_far   # (extra data taken before the evaluation was in holds the earlier best)
         lg.save("extra_data.pkl", extra)
         return st
 
@@ -427,7 +364,11 @@ class DeviceRLAlgorithmGroup:
     The K runs share the schedule (epochs, steps per epoch, env_num, train trigger); whether a run CAN train at a trigger is its own matter
     (`insert_at_episode_end`: its ring fills when ITS episodes end) — runs that cannot yet are skipped, exactly as their own process would.
     Trainers that are not SoftActorCritic (or differ in shape) are stepped one after the other on the shared stream.  The time columns are the
-    group's wall time for the phase (all K runs advance in it)."""
+    group's wall time for the phase (all K runs advance in it).
+
+    This is THE off-policy epoch loop: DeviceRLAlgorithm.train is a group of one (plain vec steps, no lock-step library call, no evaluation
+    threads).  The on-policy loop and MBPO.train keep loops of their own and build a group of one for its pieces (begin_epoch,
+    sample_then_train, end_epoch)."""
 
     SCHEDULE = ("num_epochs", "num_env_steps_per_epoch", "env_num", "num_steps_between_train_calls", "num_train_steps_per_train_call",
                 "batch_size", "on_policy")
@@ -441,18 +382,20 @@ class DeviceRLAlgorithmGroup:
             for k in self.SCHEDULE:
                 if getattr(a, k) != getattr(a0, k):
                     raise ValueError(f"DeviceRLAlgorithmGroup: the runs of a group share one schedule; {k} differs ({getattr(a, k)} vs {getattr(a0, k)})")
-        if a0.on_policy:
-            raise NotImplementedError("DeviceRLAlgorithmGroup steps off-policy runs (the on-policy branch is one device pipeline per run)")
         self.ctx = a0.trainer.ctx
+        self._ctxs = list({id(a.trainer.ctx): a.trainer.ctx for a in self.algs}.values())   # sync() waits once per distinct context
         self._lockstep_args = self._plain_rollouts()
         self._groups = {}   # subset of run indices -> SoftActorCriticGroup (the whole set in steady state; subsets only while rings fill)
+        self.t_start = None
+        self._pool = self._apool = self._pending = None   # train()'s evaluation threads and the evaluation running beside the epoch
 
     def _plain_rollouts(self):
         """ctypes arrays for ilsx_rollout_steps_lockstep when every run samples through the plain fused rollout (a HIP vec env, a device
-        policy, a device ring, no expert relabelling, one max_path_length / no_terminal for all); None otherwise."""
+        policy, a device ring, no expert relabelling, one max_path_length / no_terminal for all); None otherwise, and for a single run, which
+        takes its own rollout_step per vec step."""
         import ctypes as C
         algs, a0 = self.algs, self.algs[0]
-        ok = all(hasattr(a.training_env, "h") and hasattr(a.exploration_policy, "h") and hasattr(a.replay_buffer, "h") and
+        ok = len(algs) > 1 and all(hasattr(a.training_env, "h") and hasattr(a.exploration_policy, "h") and hasattr(a.replay_buffer, "h") and
                  getattr(a.trainer, "expert_policy", None) is None and a.max_path_length == a0.max_path_length and
                  a.no_terminal == a0.no_terminal and type(a.training_env).rollout_step is type(a0.training_env).rollout_step and
                  not hasattr(a.exploration_policy, "_ppo") and not hasattr(a.exploration_policy, "before_rollout_step") for a in algs)
@@ -520,110 +463,131 @@ class DeviceRLAlgorithmGroup:
             grp.train_from_replay([self.algs[i].replay_buffer for i in idx], n, B)
         else:
             for i in idx:
-                self.algs[i].trainer.train_from_replay(self.algs[i].replay_buffer, n, B)
+                self.algs[i]._train_call()
 
     def sync(self):
+        for ctx in self._ctxs:
+            ctx.sync()
+
+    # ---- the pieces of an epoch: train() below is made of them, the on-policy loop uses the first and the last, MBPO.train all three
+    def begin_epoch(self):
+        self.t_epoch = time.perf_counter()
+        if self.t_start is None:
+            self.t_start = self.t_epoch
+        self.t_sample = self.t_train = 0.0
         for a in self.algs:
-            a.trainer.ctx.sync()
-        self.ctx.sync()
+            a.training_env.rollout_stats(reset=True)
+
+    def sample_then_train(self, t0, left=1):
+        """Vec steps of every run until the first run's train trigger (at least one, at most `left`), then a train call for the runs that are
+        due and can train.  Books the time since t0 as sample time up to the wait at the trigger and as train time from there; returns the
+        number of vec steps taken."""
+        algs, a0 = self.algs, self.algs[0]
+        n, due = 0, []
+        while not due and n < max(left, 1):
+            if self._lockstep_args is not None:   # every run samples through the plain fused rollout: one library call for the whole stretch
+                k = max(1, min(left, min(-(-(a.num_steps_between_train_calls - (a._n_env_steps_total - a._n_prev_train_env_steps)) // a.env_num)
+                                         for a in algs)))
+                envs, pis, rbs, mins, lib = self._lockstep_args
+                from . import _lib
+                _lib.check(lib.ilsx_rollout_steps_lockstep(envs, pis, rbs, len(algs), k, int(a0.max_path_length), mins, 0, int(a0.no_terminal)))
+                for a in algs:
+                    a._n_env_steps_total += k * a.env_num
+            elif len(algs) == 1:
+                k = 1
+                a0._vec_step()
+            else:
+                k = 1
+                for a in algs:          # enqueue every run's vec step on its own stream ...
+                    a._vec_step(begin_only=True)
+                for a in algs:          # ... then do the host part of each (insert_at_episode_end: wait + insert the finished episodes)
+                    a._vec_step_end()
+            n += k
+            due = [i for i, a in enumerate(algs) if a._train_due()]
+        if due:
+            self.sync()
+            t1 = time.perf_counter()
+            self.t_sample += t1 - t0
+            can = [i for i in due if algs[i]._can_train()]
+            if can:
+                self._train(can)
+                self.sync()
+            self.t_train += time.perf_counter() - t1
+        else:
+            self.t_sample += time.perf_counter() - t0
+        return n
+
+    def end_epoch(self, epoch):
+        """Wait for the epoch's work; write the rows of an evaluation that ran beside it; evaluate — blocking, or (train() with eval_async on
+        every run) on the frozen copies beside the next epoch —; end the trainers' epoch.  `(Previous) Eval Time (s)` of the next row: from
+        the end of the wait to after the K rows and snapshots are written, or the duration of the evaluation job."""
+        algs = self.algs
+        self.sync()
+        t0 = time.perf_counter()
+        if algs[0].on_policy:   # rollout + update are one device pipeline there: the epoch up to here is train time
+            self.t_train = t0 - self.t_epoch
+        self._eval_join()
+        for a in algs:
+            sync_eval_obs_rms(a)    # (after the join: the evaluation that ran beside this epoch used the statistics it was started with)
+            a._t_sample, a._t_train = self.t_sample, self.t_train
+        when = (epoch, t0 - self.t_epoch, t0 - self.t_start)
+        if self._apool is not None:
+            pres = []
+            for a in algs:
+                a._eval_freeze()
+                pre = a._eval_begin(*when, a.trainer.get_eval_statistics())
+                snapshot, extra = pre["snapshot"](), pre["extra"]()    # the state the frozen policy belongs to
+                pre["snapshot"], pre["extra"] = (lambda s=snapshot: s), (lambda x=extra: x)
+                pres.append(pre)
+                a.trainer.end_epoch()
+            self._pending = (pres, self._apool.submit(self._eval_job, [a.eval_async["sampler"] for a in algs]))
+            return
+        collected = self._eval_lockstep()
+        if collected is None:   # (one run collects inside evaluate(), between its reads)
+            collected = list(self._pool.map(lambda a: a._eval_collect(), algs)) if self._pool else [None]
+        for a, c in zip(algs, collected):
+            a.evaluate(*when, c)
+            a.trainer.end_epoch()
+        for a in algs:
+            a._t_eval = time.perf_counter() - t0
+
+    def _eval_job(self, samplers):
+        t0 = time.perf_counter()
+        collected = self._eval_lockstep(samplers)
+        if collected is None:
+            collected = list((self._pool.map if self._pool else map)(lambda s_: s_.obtain_statistics(stat_prefix="Test"), samplers))
+        return collected, time.perf_counter() - t0
+
+    def _eval_join(self):
+        if self._pending is not None:
+            (pres, fut), self._pending = self._pending, None
+            collected, t_eval = fut.result()
+            for a, pre, c in zip(self.algs, pres, collected):
+                a._t_eval = t_eval
+                a._eval_finish(pre, c)
 
     def train(self, start_epoch=0):
-        from concurrent.futures import ThreadPoolExecutor
         algs, a0 = self.algs, self.algs[0]
+        if a0.on_policy:
+            raise NotImplementedError("DeviceRLAlgorithmGroup steps off-policy runs (the on-policy branch is one device pipeline per run)")
         # the runs' evaluation rollouts are host-driven loops of small launches (one C call per rollout round, a wait every 32 vec steps): one
         # thread per run, each on its run's stream — ctypes drops the GIL inside the calls, the K evaluations overlap on the GPU
-        pool = ThreadPoolExecutor(max_workers=len(algs)) if len(algs) > 1 else None
+        self._pool = ThreadPoolExecutor(max_workers=len(algs)) if len(algs) > 1 else None
         # eval_async on every run: the K evaluations of an epoch run (in lock-step, on the frozen copies and the eval envs' own streams) beside
         # the next epoch's sampling and training; their K rows are written when they are in
-        use_async = all(getattr(a, "eval_async", None) is not None for a in algs)
-        apool = ThreadPoolExecutor(max_workers=1) if use_async else None
-        pending = None
-
-        def join(pending):
-            if pending is not None:
-                pres, fut = pending
-                collected, t_ev = fut.result()
-                for a, pre, c in zip(algs, pres, collected):
-                    a._t_eval = t_ev
-                    a._eval_finish(pre, c)
-            return None
-        t_start = time.perf_counter()
-        for epoch in range(start_epoch, a0.num_epochs + 1):
-            t_epoch = time.perf_counter()
-            t_sample = t_train = 0.0
-            for a in algs:
-                a.training_env.rollout_stats(reset=True)
+        if all(getattr(a, "eval_async", None) is not None for a in algs):
+            self._apool = ThreadPoolExecutor(max_workers=1)
+        for epoch in range(start_epoch, a0.num_epochs + 1):   # num_epochs + 1 (base_algorithm.py:64)
+            self.begin_epoch()
             left = a0.num_env_steps_per_epoch // a0.env_num
             while left > 0:
-                t0 = time.perf_counter()
-                # vec steps until the first run's train trigger (at least one): one library call for the whole stretch when every run
-                # samples through the plain fused rollout, else step by step from here
-                n = max(1, min(left, min(-(-(a.num_steps_between_train_calls - (a._n_env_steps_total - a._n_prev_train_env_steps)) // a.env_num)
-                                         for a in algs)))
-                if self._lockstep_args is not None:
-                    envs, pis, rbs, mins, lib = self._lockstep_args
-                    from . import _lib
-                    _lib.check(lib.ilsx_rollout_steps_lockstep(envs, pis, rbs, len(algs), n, int(a0.max_path_length), mins, 0, int(a0.no_terminal)))
-                    for a in algs:
-                        a._n_env_steps_total += n * a.env_num
-                else:
-                    n = 1
-                    for a in algs:          # enqueue every run's vec step on its own stream ...
-                        a._vec_step(begin_only=True)
-                    for a in algs:          # ... then do the host part of each (insert_at_episode_end: wait + insert the finished episodes)
-                        a._vec_step_end()
-                left -= n
-                due = [i for i, a in enumerate(algs) if a._train_due()]
-                if due:
-                    self.sync()
-                    t1 = time.perf_counter()
-                    t_sample += t1 - t0
-                    can = [i for i in due if algs[i]._can_train()]
-                    if can:
-                        self._train(can)
-                        self.sync()
-                    t_train += time.perf_counter() - t1
-                else:
-                    t_sample += time.perf_counter() - t0
-            self.sync()
-            t_eval0 = time.perf_counter()
-            if use_async:
-                pending = join(pending)
-            for a in algs:
-                sync_eval_obs_rms(a)
-            if use_async:
-                pres = []
-                for a in algs:
-                    a._t_sample, a._t_train = t_sample, t_train
-                    a._eval_freeze()
-                    pre = a._eval_begin(epoch, t_eval0 - t_epoch, t_eval0 - t_start)
-                    pre["snapshot"], pre["extra"] = a.get_epoch_snapshot(), a.get_extra_data_to_save(epoch)
-                    pres.append(pre)
-                    a.trainer.end_epoch()
-                samplers = [a.eval_async["sampler"] for a in algs]
-
-                def run(samplers=samplers, t0=t_eval0):
-                    collected = self._eval_lockstep(samplers)
-                    if collected is None:
-                        collected = list(pool.map(lambda s_: s_.obtain_statistics(stat_prefix="Test"), samplers)) if pool else \
-                            [samplers[0].obtain_statistics(stat_prefix="Test")]
-                    return collected, time.perf_counter() - t0
-                pending = (pres, apool.submit(run))
-                continue
-            collected = self._eval_lockstep()
-            if collected is None:
-                collected = list(pool.map(lambda a: a._eval_collect(), algs)) if pool else [algs[0]._eval_collect()]
-            t_eval = time.perf_counter() - t_eval0
-            for a, c in zip(algs, collected):
-                a._t_sample, a._t_train = t_sample, t_train
-                a.evaluate(epoch, t_eval0 - t_epoch, t_eval0 - t_start, collected=c)
-                a._t_eval = t_eval
-                a.trainer.end_epoch()
-        join(pending)
-        if apool:
-            apool.shutdown()
-        if pool:
-            pool.shutdown()
+                left -= self.sample_then_train(time.perf_counter(), left)
+            self.end_epoch(epoch)
+        self._eval_join()
+        for pool in (self._apool, self._pool):
+            if pool is not None:
+                pool.shutdown()
+        self._pool = self._apool = None
 
     def close(self):
         for g in self._groups.values():

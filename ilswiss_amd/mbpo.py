@@ -14,7 +14,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .algorithm import DeviceRLAlgorithm
+from .algorithm import DeviceRLAlgorithm, DeviceRLAlgorithmGroup
 from .device import get_context, host_ptr
 from .replay import EnvReplayBuffer, SimpleReplayBuffer
 from .trainer import check_swallowed_kwargs
@@ -423,6 +423,8 @@ class MBPO(DeviceRLAlgorithm):
     """MBPO(env, model: BNNTrainer, algo: SoftActorCritic, is_terminal, ...) — mbpo.py:23-68; the rest of the keys are
     DeviceRLAlgorithm's (training_env, eval_env, exploration_policy, batch_size, ...)."""
 
+    EVAL_BETWEEN_EPOCHS = "MBPO's epoch loop does not overlap the evaluation with the next epoch"
+
     def __init__(self, env, model, algo, is_terminal, model_replay_buffer=None, model_replay_buffer_size=10000, deterministic=False,
                  model_train_freq=250, model_retrain_epochs=1, rollout_batch_size=int(1e5), real_ratio=0.1, rollout_schedule=None,
                  max_model_t=None, target_update_interval=1, **kwargs):
@@ -514,15 +516,15 @@ class MBPO(DeviceRLAlgorithm):
                     _lib.check(lib.ilsx_replay_sample(rb.h, cnt, None, *ptrs, None))
             self.algo._call("train_step", *[x.ptr for x in st], B, None, None)
 
-    # ---- mbpo.py:70-162
+    def _train_call(self):
+        self._do_training()
+
+    # ---- mbpo.py:70-162: the model-training block and the step count that ends an epoch; the rest is the shared loop's
     def train(self, start_epoch=0):
-        ctx = self.algo.ctx
-        t_start = time.perf_counter()
+        loop = DeviceRLAlgorithmGroup([self])
         self.logger.log(f"MBPO | Presampling for {self.min_steps_before_training} steps")
         for epoch in range(start_epoch, self.num_epochs):   # MBPO.start_training: range(start_epoch, num_epochs)
-            t_epoch = time.perf_counter()
-            self._t_sample = self._t_train = 0.0
-            self.training_env.rollout_stats(reset=True)
+            loop.begin_epoch()
             start_env_steps, last_block = self._n_env_steps_total, None
             while True:
                 t0 = time.perf_counter()
@@ -535,33 +537,18 @@ class MBPO(DeviceRLAlgorithm):
                     block = cur // self.model_train_freq if cur >= 0 else None
                     if block is not None and block != last_block and self.real_ratio < 1.0:
                         last_block = block
-                        ctx.sync()
+                        loop.sync()
                         self._train_model()
                         self._set_rollout_length(epoch)
                         self._extend_model_replay_buffer()
                         self._rollout_stat = self._rollout_model(self.deterministic)
-                        ctx.sync()
-                        self._t_train += time.perf_counter() - t0
+                        loop.sync()
+                        loop.t_train += time.perf_counter() - t0
                         t0 = time.perf_counter()
                 else:
                     start_env_steps = self._n_env_steps_total
-                self._vec_step()
-                if self._train_due():
-                    ctx.sync()
-                    t1 = time.perf_counter()
-                    self._t_sample += t1 - t0
-                    if self._can_train():
-                        self._count_train_call()
-                        self._do_training()
-                        ctx.sync()
-                    self._t_train += time.perf_counter() - t1
-                else:
-                    self._t_sample += time.perf_counter() - t0
-            ctx.sync()
-            t0 = time.perf_counter()
-            self.evaluate(epoch, time.perf_counter() - t_epoch, time.perf_counter() - t_start)
-            self._t_eval = time.perf_counter() - t0
-            self.trainer.end_epoch()
+                loop.sample_then_train(t0)
+            loop.end_epoch(epoch)
 
 
 def rollout_length_at(schedule, epoch):

@@ -241,6 +241,7 @@ def test_group_loop_schedule_on_stub_runs():
     class Run:   # the attributes and pieces of DeviceRLAlgorithm the group drives
         _train_due = DeviceRLAlgorithm._train_due
         _count_train_call = DeviceRLAlgorithm._count_train_call
+        _train_call = DeviceRLAlgorithm._train_call
 
         def __init__(self, fills_after):
             self.trainer, self.replay_buffer, self.training_env = Trainer(), Ring(), Env()
