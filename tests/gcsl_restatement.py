@@ -124,11 +124,16 @@ class _Net(nn.Module):
 class _Restatement:
     bn = True
 
-    def __init__(self, flat, D, H, nblk, n, lr=3e-4):
+    def __init__(self, flat, D, H, nblk, n, lr=3e-4, dtype=torch.float32):
         torch.manual_seed(0)
-        self.net = _Net(D, H, nblk, n, self.bn)
+        self.net = _Net(D, H, nblk, n, self.bn).to(dtype)
+        self.dtype = dtype
         self.set_flat(flat)
         self.opt = torch.optim.Adam(self.net.params_in_order(), lr=lr)
+
+    def _x(self, a):
+        """a float32 input array in the precision of the net"""
+        return torch.from_numpy(np.asarray(a, F32)).to(self.dtype)
 
     def set_flat(self, flat):
         off = 0
@@ -159,7 +164,7 @@ class _Restatement:
 class CatRestatement(_Restatement):
     def train_step(self, X, y):
         self.net.train()
-        logits = self.net(torch.from_numpy(X))
+        logits = self.net(self._x(X))
         yt = torch.from_numpy(np.asarray(y, np.int64))
         loss = nn.CrossEntropyLoss()(logits, yt)
         acc = (torch.argmax(torch.softmax(logits, -1), -1) == yt).float().mean()
@@ -168,18 +173,62 @@ class CatRestatement(_Restatement):
         self.opt.step()
         return loss.item(), acc.item()
 
+    WRONG = ("bn_const", "running_fwd", "no_inv_b", "label_shift", "bo_mean")
+
+    def gradients(self, X, y, wrong=None):
+        """One train-mode batch WITHOUT an optimiser step, in the precision the restatement was built with: dict(grad = the gradient of every
+        parameter in the flat layout, ce, acc, probs [B, n] = the train-mode softmax, running_mean / running_var [nblk, H] after this one
+        batch, dead = dead_bias_mask()).  The right step runs the modules themselves (nn.BatchNorm1d in train mode); `wrong` computes a
+        deliberately wrong one from a forward written out here (tests: the bounds tell it from the right one):
+          bn_const    — BatchNorm's backward with the batch mean and variance held constant;
+          running_fwd — the running statistics (0 / 1 at the start) normalise the training forward;
+          no_inv_b    — the cross-entropy summed, not averaged (dlogit without its 1/B);
+          label_shift — the one-hot at y + 1 mod n;
+          bo_mean     — the output bias's gradient as a mean over the rows instead of a sum."""
+        assert wrong is None or wrong in self.WRONG, wrong
+        net, n = self.net, self.net.last.out_features
+        x, yt = self._x(X), torch.from_numpy(np.asarray(y, np.int64))
+        B = x.shape[0]
+        net.train()
+        for p in net.parameters():
+            p.grad = None
+        if wrong in ("bn_const", "running_fwd"):
+            h = x
+            for fc, bn in zip(net.fcs, net.bns):
+                z = fc(h)
+                if wrong == "bn_const":
+                    mean, var = z.mean(0).detach(), z.var(0, unbiased=False).detach()
+                else:
+                    mean, var = bn.running_mean, bn.running_var
+                h = torch.relu(bn.weight * (z - mean) / torch.sqrt(var + bn.eps) + bn.bias)
+            logits = net.last(h)
+        else:
+            logits = net(x)
+        if wrong == "label_shift":
+            yt = (yt + 1) % n
+        loss = nn.CrossEntropyLoss(reduction="sum" if wrong == "no_inv_b" else "mean")(logits, yt)
+        loss.backward()
+        if wrong == "bo_mean":
+            net.last.bias.grad /= B
+        probs = torch.softmax(logits, -1).detach()
+        ce = nn.CrossEntropyLoss()(logits, yt).item()
+        acc = (torch.argmax(probs, -1) == yt).double().mean().item()
+        grad = np.concatenate([(torch.zeros_like(p) if p.grad is None else p.grad).numpy().ravel() for p in net.params_in_order()])
+        rm, rv = (np.stack([getattr(b, k).numpy().copy() for b in net.bns]) for k in ("running_mean", "running_var"))
+        return dict(grad=grad, ce=ce, acc=acc, probs=probs.numpy(), running_mean=rm, running_var=rv, dead=self.dead_bias_mask())
+
     def probs(self, X):
         self.net.eval()
         with torch.no_grad():
-            return torch.softmax(self.net(torch.from_numpy(X)), -1).numpy()
+            return torch.softmax(self.net(self._x(X)), -1).numpy()
 
 
 class MseRestatement(_Restatement):
     bn = False
 
     def train_step(self, X, a, max_act=1.0):
-        pred = max_act * torch.tanh(self.net(torch.from_numpy(X)))
-        loss = torch.sum((pred - torch.from_numpy(a)) ** 2, -1).mean()
+        pred = max_act * torch.tanh(self.net(self._x(X)))
+        loss = torch.sum((pred - self._x(a)) ** 2, -1).mean()
         self.opt.zero_grad()
         loss.backward()
         self.opt.step()
